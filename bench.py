@@ -8,16 +8,25 @@ shifted warm start, solve, read-back / fallback, plant integration, Jacobi excha
 takes one `cfz_loop_step` launch per iteration instead).  Inputs are resident in HBM before the timed
 region.  N GPUs = N independent shards of scenarios (weak scaling, no data-path collective).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, `roofline`
+Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit, `ms_per_step`, `roofline`
 (algorithmic HBM bytes of SURVEY.md 8d / measured solver-kernel time, plus the FP64 and VALU-active fractions),
 `value` = CONVERGED solves per second (status 0; `value_all` counts every solve of the timed region, also those that did no work:
-`config.status_counts`), `cold_step` (the first MPC iteration, cold multipliers), `extra.seeds` (the same measurement on three sampler
-seeds, outside the timed region: the launch lasts as long as its slowest scenario, a maximum of 1024 draws), `extra.all_moving` (no
-parked vehicle in the sample; `config.parked_fraction` says how many solves of the headline are for one) and `cpu_baseline`
-(oracle/cfz_port.c, the plain-C port, running the SAME closed loop on this host's usable cores; N=1 only).
+`config.status_counts`), `cold_step` (the first MPC iteration, cold multipliers: the first warm-up launch).
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs, print the line.  `--full` adds what is measured or
+checked beyond the headline: `config.infeasible_starts` / `config.redrawn_scenarios` (what the sampler handed out) and, after the timed
+region, `extra.seeds` (the same measurement on three sampler seeds: the launch lasts as long as its slowest scenario, a maximum of 1024 draws),
+`extra.all_moving` (no parked vehicle in the sample; `config.parked_fraction` says how many solves of the headline are for one), the
+planning lines `extra["configs[1]"]` / `extra["configs[3]"]` and `cpu_baseline` (oracle/cfz_port.c, the plain-C port, running the SAME
+closed loop on this host's usable cores; N=1 only).  `--no-seeds`, `--no-extras` and `--no-cpu-baseline` drop parts of it again.
+
+`--dump-outputs DIR` writes what the timed closed loop hands a caller after its last step (`Engine.loop_get`: `state` [S,V,5],
+`pred` [S,V,7,N], `status` and `iters` [S,V]) as DIR/<name>.npy in float64 (about 7 MB at the default size), `_rank<r>` appended to
+the names when there are several ranks.  The inputs are fixed by the arguments (seeded sampler), so two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -577,6 +586,25 @@ def planning_cpu_baseline(agents, sets, paths, fh):
              "sample": f"one four-vehicle joint plan, {rj['iters']} iterations, status {rj['status']}, {t2 - t1:.1f} s"})
 
 
+DUMP_BYTES_MAX = 60 * 10**6  # --dump-outputs writes at most 64 MB, .npy headers included
+
+
+def dump_outputs(d, arrays, suffix=""):
+    """--dump-outputs: every array (axis 0 = scenario) as d/<name><suffix>.npy in float64.  Above DUMP_BYTES_MAX in all, the same
+    seeded sample of scenarios is taken from every array (sorted) and its indices written as d/scenario_index<suffix>.npy."""
+    arrays = {k: np.asarray(a, dtype=np.float64) for k, a in arrays.items()}
+    S = next(iter(arrays.values())).shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        keep = int(S * (DUMP_BYTES_MAX - 8 * S) // total)
+        idx = np.sort(np.random.default_rng(0).choice(S, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["scenario_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, f"{k}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -584,7 +612,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--scenarios", type=int, default=1024, help="scenarios per GPU (x4 vehicles)")
     ap.add_argument("--max-iter", type=int, default=600, help="IPM iteration limit (reference: 600)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need (after the timed region): the sampler's counts, the "
+                         "three-seed and all-moving repetitions, the planning extras (configs[1], configs[3]) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the closed loop's arrays after the last timed step (state, pred, status, iters) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--seed", type=int, default=2024, help="scenario sampler seed of rank 0 (rank r uses seed + r)")
     ap.add_argument("--n-obs", type=int, default=6, help="static obstacles (reference map: 6); fewer = experiments only")
     ap.add_argument("--extras-only", action="store_true", help="only the planning extras (configs[1], configs[3]): the command tools/gpu_profile_extras.sh profiles")
@@ -604,10 +637,10 @@ def main():
                          "collocation plan, VehicleFollower.plan_single_path) of the synthetic strategy, SURVEY.md 8d config 3; state_ws: "
                          "data/refs_4v.npz, the slower state_ws warm-start plans (the table of rounds 1-2); replan: build the planned table "
                          "at start-up with the GPU planning chain instead of loading it")
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[1] / configs[3] planning measurements after the timed region")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the configs[1] / configs[3] planning measurements")
     ap.add_argument("--option", action="append", default=[], metavar="KEY=VALUE",
                     help="experiments only: a field of cfz_options for the MPC engine (e.g. carry_duals=0, restoration=0); noted in config.options")
-    ap.add_argument("--no-seeds", action="store_true", help="skip the three-seed and all-moving repetitions of the headline after the timed region")
+    ap.add_argument("--no-seeds", action="store_true", help="with --full: skip the three-seed and all-moving repetitions of the headline")
     ap.add_argument("--raw-starts", action="store_true",
                     help="take the sampler's starts as they come (rounds 1-2); default: a scenario whose noisy start state is already "
                          "inside a clearance (an infeasible first NLP, status 4) is drawn again")
@@ -677,12 +710,12 @@ def main():
         eng = engine.Engine(spec, max_batch=S * V, device=local_rank, max_iter=args.max_iter, **opts)
         eng.loop_init(table, k0, noise)
 
-    # what the sampler handed out, counted on the starts that are actually used
-    infeasible_starts = None if single else int(((scenarios.start_clearances(spec, table, k0, noise) < spec.dmin - 0.01).any(1)
-                                                 | (scenarios.start_box_excess(spec, table, k0, noise) > 1e-2).any(1)).sum())
+    # what the sampler handed out, counted on the starts that are actually used; --full only
+    infeasible_starts = None if single or not args.full else int(((scenarios.start_clearances(spec, table, k0, noise) < spec.dmin - 0.01).any(1)
+                                                                  | (scenarios.start_box_excess(spec, table, k0, noise) > 1e-2).any(1)).sum())
 
     redrawn = None
-    if fspec is not None and not vehicle_sharded:
+    if fspec is not None and not vehicle_sharded and args.full:
         k0_raw, nz_raw = scenarios.sample_scenarios(len(k0), table, seed=args.seed + rank)
         redrawn = int(((k0_raw != k0) | (np.abs(nz_raw - noise).max((1, 2)) > 0.0)).sum())  # scenarios of the raw sampler that were drawn again (rounds 1-2 took them as they came)
 
@@ -755,6 +788,11 @@ def main():
         n_ok = int((got["status"] == 0).sum())
         iters_mean = float(got["iters"].mean())
         V_local = V
+    if args.dump_outputs:
+        if vehicle_sharded:
+            got = {k: getattr(vloop, k).cpu().numpy() for k in ("state", "pred", "status", "iters")}
+            got["status"], got["iters"] = (got[k].reshape(got["state"].shape[:2]) for k in ("status", "iters"))
+        dump_outputs(args.dump_outputs, got, "" if world == 1 else f"_rank{rank}")
 
     if dist is not None:
         import torch
@@ -852,7 +890,7 @@ def main():
         }
         if cold is not None:
             line["cold_step"] = cold
-        if world == 1 and persistent and not single and not vehicle_sharded and not args.no_seeds:
+        if args.full and world == 1 and persistent and not single and not vehicle_sharded and not args.no_seeds:
             # ---- the same measurement on other samples, OUTSIDE the timed region (same process, same engine) ------------------------
             def closed_loop_sample(k0_, noise_):
                 eng.loop_init(table, k0_, noise_)
@@ -883,12 +921,12 @@ def main():
                                                     f"(the shortest has {int(min(lengths_v))} samples) within the {args.warmup + args.steps} MPC iterations")
             except Exception as e:  # noqa: BLE001 - the headline must go out whatever happens here
                 extra["seeds_error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and not args.no_extras and not single and not vehicle_sharded:
+        if args.full and world == 1 and not args.no_extras and not single and not vehicle_sharded:
             try:
                 line.setdefault("extra", {}).update(planning_extras(device=local_rank, cpu=not args.no_cpu_baseline))
             except Exception as e:  # noqa: BLE001 - the headline must go out whatever happens here
                 line.setdefault("extra", {})["error"] = f"{type(e).__name__}: {e}"
-        if world == 1 and not args.no_cpu_baseline and not single:
+        if args.full and world == 1 and not args.no_cpu_baseline and not single:
             ref_kind = args.reference
             if args.reference == "replan":  # the workers get the table this run built, not the packaged one
                 import tempfile

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _run(extra):
         port = sk.getsockname()[1]
     env = dict(os.environ, CFZ_BENCH_FORCE_DIST="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--scenarios", "64",
-                          "--no-cpu-baseline", "--no-extras"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-extras"] + extra, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1  # ONE JSON line
@@ -57,6 +58,33 @@ def test_bench_line_through_torch_distributed(extra):
         assert sd["seeds"] == [2024, 2025, 2026] and sd["min"] <= sd["median"] <= sd["max"] and len(sd["runs"]) == 3
         assert all(sum(r_["status_counts"]) == 64 * 4 * 3 and r_["value"] <= r_["value_all"] for r_ in sd["runs"])
         assert am["parked_fraction"] == 0.0 and am["value"] > 1e3 and am["mean_ipm_iters"] > sd["runs"][0]["mean_ipm_iters"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no `--full`) prints the headline alone -- no `extra`, no `cpu_baseline`, no sampler counts -- and `--dump-outputs`
+    writes what the closed loop hands a caller after the last timed step, in float64, the status agreeing with the line; a second run
+    with the same arguments writes the same arrays bit for bit."""
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--scenarios", "64",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    b = run(tmp_path / "a")
+    assert b["steps"] == 3 and b["warmup"] == 2 and b["ms_per_step"] > 0.0 and b["value"] > 1e3 and b["dtype"] == "f64" and b["higher_is_better"]
+    assert "extra" not in b and "cpu_baseline" not in b and "gpu_vs_cpu" not in b and "cold_step" in b
+    assert b["config"]["infeasible_starts"] is None and b["config"]["redrawn_scenarios"] is None
+    shapes = {"state": (64, 4, 5), "pred": (64, 4, 7, 30), "status": (64, 4), "iters": (64, 4)}
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{k}.npy" for k in shapes)
+    assert all(got[k].dtype == np.float64 and got[k].shape == shapes[k] for k in shapes) and np.isfinite(got["pred"]).all()
+    assert set(np.unique(got["status"])) <= set(range(6)) and (got["iters"] >= 0).all() and (got["iters"] == np.round(got["iters"])).all()
+    assert abs((got["status"] == 0).mean() - b["config"]["converged_last_step"]) < 1e-12
+    assert abs(got["iters"].mean() - b["config"]["mean_ipm_iters_last_step"]) < 1e-12
+    run(tmp_path / "b")
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in shapes)
 
 
 def test_long_persistent_launch_at_4096_scenarios():

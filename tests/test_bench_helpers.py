@@ -82,3 +82,27 @@ def test_lane_sampler_and_elimination_info():
     four = engine.colloc_elimination_info([11, 7, 7, 9])
     assert four["kb"] == 51 and four["nk"] == engine.colloc_band_info([11, 7, 7, 9])[0] - 16 * 30 and four["workspace_bytes"] < 60e6
     assert bench.profiled_extras(0, require_current=False) is None or "traffic" in bench.profiled_extras(0, require_current=False)
+
+
+def test_dump_outputs_writes_float64_within_the_cap(tmp_path, monkeypatch):
+    """`bench.dump_outputs` (--dump-outputs): every array as <name>.npy in float64; above the cap the same seeded sample of scenarios
+    from every array, its indices beside them, the whole under the cap -- and the same sample on every call."""
+    import os
+
+    import numpy as np
+
+    S = 1000
+    arrays = {"state": np.arange(S * 4 * 5, dtype=np.float64).reshape(S, 4, 5), "status": np.arange(S * 4, dtype=np.int32).reshape(S, 4) % 6}
+    bench.dump_outputs(str(tmp_path / "all"), arrays, "_rank1")
+    assert sorted(os.listdir(tmp_path / "all")) == ["state_rank1.npy", "status_rank1.npy"]
+    st = np.load(tmp_path / "all" / "status_rank1.npy")
+    assert st.dtype == np.float64 and np.array_equal(st, arrays["status"]) and np.array_equal(np.load(tmp_path / "all" / "state_rank1.npy"), arrays["state"])
+    cap = 8 * S * 24 // 4  # a quarter of the arrays' float64 bytes
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", cap)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("state", "status", "scenario_index")}
+    idx = got["scenario_index"].astype(int)
+    assert 0 < len(idx) < S // 4 and np.all(np.diff(idx) > 0) and sum(a.nbytes for a in got.values()) <= cap
+    assert np.array_equal(got["state"], arrays["state"][idx]) and np.array_equal(got["status"], arrays["status"][idx])
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in got)

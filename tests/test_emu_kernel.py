@@ -127,7 +127,9 @@ for b in (0, 7, 11):
 print('sanitized ok')
 """
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"]).decode().strip()
-    env = dict(**__import__("os").environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0")
+    # the ASan runtime goes first in the preload list, ahead of (not instead of) whatever the environment already preloads
+    environ = __import__("os").environ
+    env = dict(environ, LD_PRELOAD=" ".join(filter(None, (asan, environ.get("LD_PRELOAD")))), ASAN_OPTIONS="detect_leaks=0")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "sanitized ok" in out.stdout, out.stderr[-2000:]
 

@@ -1,5 +1,6 @@
 import sys, os, time, tempfile
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from test_colloc import colloc_guess
 from conflict_rez_amd import engine, scenarios, strategy as strat

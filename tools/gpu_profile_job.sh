@@ -8,7 +8,7 @@ mkdir -p $O
 cd $R
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3
 timeout 900 python -m pytest tests -m gpu -x -q --timeout 300 2>&1 | grep -E "passed|failed|rror" | tail -3
-timeout 600 python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err; tail -c 1500 $O/${tag}_bench.json
+timeout 600 python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err; tail -c 1500 $O/${tag}_bench.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_$tag
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_$tag/trace -o t -- python3 $R/bench.py --no-cpu-baseline --no-extras --no-seeds > $O/${tag}_bench_traced.json 2>$O/${tag}_trace.err
