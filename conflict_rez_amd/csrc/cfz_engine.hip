@@ -10,7 +10,9 @@
 //   loop_prep      closed loop: parameters and shifted warm start of every vehicle from the
 //                  previous predictions (reference vehicle_follower.py:432-476, 636-637)
 //   loop_post      closed loop: read-back or shift fallback, plant integration, clock
-//                  (reference :484-563)
+//                  (reference :484-563), and the record of the realised trajectory when one is kept (:556-563)
+//   audit_kernel   signed distances, first contact and arrivals along a recorded trajectory (cfz_audit.inl), one
+//                  wavefront per scenario
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events.
@@ -29,6 +31,7 @@
 
 #include "../../include/confrez_hip.h"
 #include "cfz_solver.inl"
+#include "cfz_audit.inl"
 #include "cfz_common.h"
 
 thread_local std::string cfz_g_err;  // cfz_last_error(); shared with cfz_planning.hip (cfz_common.h)
@@ -81,9 +84,10 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
 }
 
 // ---- closed loop ------------------------------------------------------------------------------
-// pred[S][V][7][N] last predictions, state[S][V][5], kidx[S] reference sample index.
+// pred[S][V][7][N] last predictions, state[S][V][5], kidx[S] reference sample index.  ref_table[P][V][T][7] is a pool of plan
+// sets; scenario s follows set table_of[s].
 // One thread per (instance, stage).
-__global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, const int32_t *kidx,
+__global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, const int32_t *table_of, const int32_t *kidx,
                           const double *pred, const double *state, double *x0, double *ref, double *nbr,
                           double *zu) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -94,7 +98,8 @@ __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, c
   const int ka = (k + 1 < N) ? k + 1 : N - 1;  // _adv_onestep (:413-426)
   if (k < 5) x0[b * 5 + k] = state[b * 5 + k];
   int kr = kidx[s] + k; if (kr > T - 1) kr = T - 1;
-  for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = ref_table[((size_t)v * T + kr) * 7 + c];
+  const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
+  for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = tab[((size_t)v * T + kr) * 7 + c];
   for (int c = 0; c < 7; ++c) zu[((size_t)b * 7 + c) * N + k] = pred[((size_t)b * 7 + c) * N + ka];
   int o = 0;
   for (int u = 0; u < V; ++u) {
@@ -110,9 +115,11 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
   if (s < S) kidx[s] += K;
 }
 
-// One thread per instance: accept the solution or shift the old prediction, integrate the plant.
+// One thread per instance: accept the solution or shift the old prediction, integrate the plant.  rec (NULL: no record) is
+// this step's slice [S][V][7] of the record: state after the plant and the applied (a, w); rec_si its [2][S][V] status, iters.
 __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
-                          const double *zu, double *pred, double *state, int32_t *kidx) {
+                          const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
+                          int32_t *rec_si) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= S * V) return;
   double *pb = pred + (size_t)b * 7 * N;
@@ -127,6 +134,12 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
   cfz::rk4_step<false>(z, pb[5 * N], pb[6 * N], dt, wb, plant_substeps, out, nullptr);
   for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
   if (b % V == 0) kidx[b / V] += 1;
+  if (rec) {
+    double *r = rec + (size_t)b * 7;
+    for (int i = 0; i < 5; ++i) r[i] = out[i];
+    r[5] = pb[5 * N]; r[6] = pb[6 * N];
+    rec_si[b] = status[b]; rec_si[S * V + b] = iters[b];
+  }
 }
 
 // ---- vehicle-sharded closed loop (partitioning B: a rank owns n_own vehicles of S scenarios) ------------------------
@@ -215,11 +228,14 @@ __global__ __launch_bounds__(1024) void order_by_iters(int B, const int32_t *ite
 #else
 #define CFZ_MARK(c) do { } while (0)
 #endif
+//   ref_table[P][V][T][7], table_of[S]: the pool of plan sets and the one each scenario follows (as loop_prep)
+//   rec[K][S][V][7], rec_si[K][2][S][V]: the record of this launch's iterations (NULL: none; as loop_post)
 __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                        const double *ref_table, const int32_t *kidx0, int t_base,
+                                                        const double *ref_table, const int32_t *table_of, const int32_t *kidx0, int t_base,
                                                         double *pred, double *state, double *scratch, int32_t *qbuf,
                                                         int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                        double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag) {
+                                                        double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
+                                                        double *rec, int32_t *rec_si) {
   extern __shared__ double smem[];
   const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
   const int N = sp.N, nn = sp.n_nbr, B = S * V, tid = threadIdx.x, lane = tid & 63;
@@ -283,6 +299,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(cons
     const int s = b / V, v = b - s * V;
     const double *pin = pred + (size_t)(t & 1) * B * 7 * N;   // predictions after iteration t-1
     double *pout = pred + (size_t)((t + 1) & 1) * B * 7 * N;
+    const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
     // ---- parameters and shifted warm start (vehicle_follower.py:432-476), straight into the solver's workspace: measured
     // state, neighbours' poses with cos / sin, warm start (solve_instance's `preloaded` form); only the reference goes through
     // a global record (the solver reads it from there in every iteration)
@@ -290,7 +307,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(cons
     for (int k = tid; k < N; k += cfz::kNL) {
       const int ka = (k + 1 < N) ? k + 1 : N - 1;
       int kr = kidx0[s] + t_base + t + k; if (kr > T - 1) kr = T - 1;
-      for (int c = 0; c < 3; ++c) ref[c * N + k] = ref_table[((size_t)v * T + kr) * 7 + c];
+      for (int c = 0; c < 3; ++c) ref[c * N + k] = tab[((size_t)v * T + kr) * 7 + c];
       for (int c = 0; c < 7; ++c) smem[L.p + k * cfz::kNP + c] = pin[((size_t)b * 7 + c) * N + ka];
       int o = 0;
       for (int u = 0; u < V; ++u) {
@@ -324,6 +341,12 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(cons
       cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
       for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
       status[b] = oi[1]; iters[b] = oi[0];
+      if (rec) {
+        double *r = rec + ((size_t)t * B + b) * 7;
+        for (int i = 0; i < 5; ++i) r[i] = out[i];
+        r[5] = a0; r[6] = w0;
+        rec_si[(size_t)t * 2 * B + b] = oi[1]; rec_si[(size_t)(t * 2 + 1) * B + b] = oi[0];
+      }
       stats[b * 3] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
       atomicAdd(iter_sum, oi[0]);
       if (oi[1] == 0) atomicAdd(iter_sum + 1, 1);  // converged solves of this launch
@@ -488,18 +511,71 @@ __global__ void joint_dual_ws_kernel(const cfz::KSpec sp, int n, const double *p
 
 // first prediction = the planned trajectory at the horizon times, as get_current_ref seeds it
 // (:397-400); state = planned state at k0 + noise
-__global__ void loop_seed(int S, int V, int N, int T, const double *ref_table, const int32_t *kidx,
+__global__ void loop_seed(int S, int V, int N, int T, const double *ref_table, const int32_t *table_of, const int32_t *kidx,
                           const double *noise, double *pred, double *state) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= (long)S * V * N) return;
   const int k = (int)(tid % N);
   const int b = (int)(tid / N);
   const int s = b / V, v = b - s * V;
+  const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
   int kr = kidx[s] + k; if (kr > T - 1) kr = T - 1;
-  for (int c = 0; c < 7; ++c) pred[((size_t)b * 7 + c) * N + k] = ref_table[((size_t)v * T + kr) * 7 + c];
+  for (int c = 0; c < 7; ++c) pred[((size_t)b * 7 + c) * N + k] = tab[((size_t)v * T + kr) * 7 + c];
   if (k == 0)
     for (int c = 0; c < 5; ++c)
-      state[b * 5 + c] = ref_table[((size_t)v * T + kidx[s]) * 7 + c] + (noise ? noise[b * 5 + c] : 0.0);
+      state[b * 5 + c] = tab[((size_t)v * T + kidx[s]) * 7 + c] + (noise ? noise[b * 5 + c] : 0.0);
+}
+
+// goal[S][V][3]: the last sample (x, y, psi) of the table each scenario follows.  One thread per instance.
+__global__ void loop_goals(int S, int V, int T, const double *ref_table, const int32_t *table_of, double *goal) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= S * V) return;
+  const int s = b / V, v = b - s * V;
+  const double *last = ref_table + (((size_t)table_of[s] * V + v) * T + T - 1) * 7;
+  for (int c = 0; c < 3; ++c) goal[(size_t)b * 3 + c] = last[c];
+}
+
+// ---- audit of a recorded closed loop (cfz_audit.inl) ------------------------------------------------------------------
+// One wavefront per scenario; its lanes deal out the (step, item) pairs round-robin and keep the running minima in registers,
+// then a butterfly over the wavefront merges them (a minimum under a total order: the same result on every run).  traj[K][S][V][7]
+// from the window's first step, goal[S][V][3]; obs_in[n_obs] the obstacles with their normals and inverse edge lengths, il the
+// body's (both formed on the host: the loop has no sqrt and no division); clear[S][2] as audit_signed_key (the host takes the root),
+// where[S][6], first_contact[S], arrive[S][V].  Plain stores, no atomics.
+// cs[n][2]: cos and sin of the n = K S V headings of traj[n][7], one thread each (the audit loop itself has no transcendental)
+__global__ void audit_headings(long n, const double *traj, double *cs) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s, c;
+  sincos(traj[i * 7 + 2], &s, &c);
+  cs[i * 2] = c; cs[i * 2 + 1] = s;
+}
+
+__global__ __launch_bounds__(64) void audit_kernel(const KArgs *__restrict__ ka, int K, int S, int V, const double *traj,
+                                                   const double *cs, const double *goal, const cfz::AuditPoly *obs_in, double il0, double il1,
+                                                   double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
+                                                   int32_t *first_contact, int32_t *arrive) {
+  __shared__ cfz::AuditPoly obs[cfz::kMaxObs];
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int no = ka->sp.n_obs;
+  if (lane < no) obs[lane] = obs_in[lane];
+  double g[4];
+  for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
+  const double il[2] = {il0, il1};
+  __syncthreads();
+  cfz::AuditAcc acc;
+  cfz::audit_lane(acc, lane, 64, K, V, traj + (size_t)s * V * 7, (long)S * V * 7, goal + (size_t)s * V * 3, cs + (size_t)s * V * 2, no,
+                  obs, g, il, pos_tol, psi_tol, v_tol);
+  for (int off = 32; off > 0; off >>= 1) {
+    cfz::AuditAcc o;
+    o.vv = __shfl_xor(acc.vv, off, 64); o.vv_t = __shfl_xor(acc.vv_t, off, 64); o.vv_u = __shfl_xor(acc.vv_u, off, 64);
+    o.vv_w = __shfl_xor(acc.vv_w, off, 64);
+    o.vo = __shfl_xor(acc.vo, off, 64); o.vo_t = __shfl_xor(acc.vo_t, off, 64); o.vo_v = __shfl_xor(acc.vo_v, off, 64);
+    o.vo_j = __shfl_xor(acc.vo_j, off, 64);
+    o.first = __shfl_xor(acc.first, off, 64);
+    for (int v = 0; v < cfz::kAuditMaxV; ++v) o.arrive[v] = __shfl_xor(acc.arrive[v], off, 64);
+    cfz::audit_merge(acc, o);
+  }
+  if (lane == 0) cfz::audit_store(acc, V, clear + (size_t)s * 2, where + (size_t)s * 6, first_contact + s, arrive + (size_t)s * V);
 }
 
 }  // namespace
@@ -527,10 +603,14 @@ struct cfz_handle {
   double *x0 = nullptr, *ref = nullptr, *nbr = nullptr, *zu = nullptr, *stats = nullptr;
   int32_t *status = nullptr, *iters = nullptr;
   double *l = nullptr, *m = nullptr, *lam_ij = nullptr, *lam_ji = nullptr, *s = nullptr;
-  // closed loop
-  int S = 0, T = 0;
+  // closed loop: ref_table[P][V][T][7] the pool of plan sets, table_of[S] the set of each scenario
+  int S = 0, T = 0, P = 0;
   double *ref_table = nullptr, *pred = nullptr, *state = nullptr;
-  int32_t *kidx = nullptr, *order = nullptr;
+  int32_t *kidx = nullptr, *order = nullptr, *table_of = nullptr;
+  // record of the realised trajectory (cfz_loop_record): rec[rec_cap][S][V][7], rec_si[rec_cap][2][S][V]; rec_used steps written
+  double *rec = nullptr;
+  int32_t *rec_si = nullptr;
+  int rec_cap = 0, rec_used = 0;
   bool have_order = false;
   // persistent loop
   double *pred2 = nullptr, *scratch = nullptr;
@@ -709,7 +789,7 @@ int cfz_destroy(cfz_handle *h) {
   hipSetDevice(h->device);
   void *bufs[] = {h->x0, h->ref, h->nbr, h->zu, h->stats, h->status, h->iters, h->l, h->m, h->lam_ij, h->lam_ji, h->s,
                   h->ref_table, h->pred, h->state, h->kidx, h->order, h->pred2, h->scratch, h->queue, h->ctrl, h->done,
-                  h->iter_sum, h->obs_tab, h->wst, h->carry, h->slots, h->kargs};
+                  h->iter_sum, h->obs_tab, h->wst, h->carry, h->slots, h->kargs, h->table_of, h->rec, h->rec_si};
   for (void *p : bufs) if (p) hipFree(p);
   arena_destroy(h->arena);
   if (h->stage_host) hipHostFree(h->stage_host);
@@ -914,50 +994,185 @@ int cfz_joint_dual_ws(cfz_handle *h, int n, const double *poses_this, const doub
   return 0;
 }
 
-int cfz_loop_init(cfz_handle *h, int S, int T, const double *ref_table, const int32_t *k0, const double *noise) {
+}  // extern "C"
+
+namespace {
+void record_free(cfz_handle *h) {
+  if (h->rec) (void)hipFree(h->rec);
+  if (h->rec_si) (void)hipFree(h->rec_si);
+  h->rec = nullptr; h->rec_si = nullptr; h->rec_cap = h->rec_used = 0;
+}
+
+// room for `steps` more steps in the record (or no record at all)
+int record_room(cfz_handle *h, int steps) {
+  if (h->rec_cap && h->rec_used + steps > h->rec_cap) return fail("the step(s) would overflow the record (cfz_loop_record)");
+  return 0;
+}
+
+int audit_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const double *d_goal, double pos_tol, double psi_tol,
+                 double v_tol, double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive) {
+  // the obstacles with their face normals and inverse edge lengths, and the body's edge lengths, formed here (audit_kernel)
+  const int no = h->ks.n_obs;
+  std::vector<cfz::AuditPoly> ob((size_t)std::max(no, 1));
+  for (int j = 0; j < no; ++j) {
+    memcpy(ob[j].v, h->ks.V_obs[j], sizeof ob[j].v);
+    cfz::audit_poly_prepare(ob[j]);
+  }
+  const double *g = h->ks.g;
+  double *dc = nullptr, *dcs = nullptr;
+  int32_t *di = nullptr;
+  cfz::AuditPoly *dob = nullptr;
+  const long n = (long)K * S * V;
+  ARENA_ALLOC(h->arena, dc, (size_t)S * 2 * 8); ARENA_ALLOC(h->arena, di, (size_t)S * (7 + V) * 4);
+  ARENA_ALLOC(h->arena, dcs, (size_t)n * 2 * 8);
+  ARENA_ALLOC(h->arena, dob, ob.size() * sizeof(cfz::AuditPoly));
+  HIP_OK(hipMemcpyAsync(dob, ob.data(), ob.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice, h->stream));
+  int32_t *dw = di, *df = di + (size_t)S * 6, *da = di + (size_t)S * 7;
+  hipLaunchKernelGGL(audit_headings, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, d_traj, dcs);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(audit_kernel, dim3(S), dim3(64), 0, h->stream, h->kargs, K, S, V, d_traj, dcs, d_goal, dob, 1.0 / (g[0] + g[2]),
+                     1.0 / (g[1] + g[3]), pos_tol, psi_tol, v_tol, dc, dw, df, da);
+  HIP_OK(hipGetLastError());
+  if (clear) HIP_OK(hipMemcpyAsync(clear, dc, (size_t)S * 2 * 8, hipMemcpyDeviceToHost, h->stream));
+  if (where) HIP_OK(hipMemcpyAsync(where, dw, (size_t)S * 6 * 4, hipMemcpyDeviceToHost, h->stream));
+  if (first_contact) HIP_OK(hipMemcpyAsync(first_contact, df, (size_t)S * 4, hipMemcpyDeviceToHost, h->stream));
+  if (arrive) HIP_OK(hipMemcpyAsync(arrive, da, (size_t)S * V * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));  // (also keeps `ob` alive until its copy is done)
+  if (clear)
+    for (int i = 0; i < 2 * S; ++i) clear[i] = cfz::audit_key_distance(clear[i]);
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *tables, const int32_t *table_of, const int32_t *k0,
+                         const double *noise) {
   if (!h) return fail("null handle");
   const int V = h->ks.n_nbr + 1, N = h->ks.N;
   if (S < 1 || (long)S * V > h->max_batch) return fail("S * (n_nbr+1) exceeds max_batch");
-  if (T < 1 || !ref_table || !k0) return fail("bad reference table");
+  if (T < 1 || !tables || !k0) return fail("bad reference table");
+  if (P < 1) return fail("the pool needs at least one plan set (P >= 1)");
+  if (!table_of && P != S) return fail("table_of is NULL (scenario s follows set s), which needs P == S");
+  if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
+  std::vector<int32_t> tof((size_t)S);
+  for (int s = 0; s < S; ++s) {
+    tof[s] = table_of ? table_of[s] : s;
+    if (tof[s] < 0 || tof[s] >= P) return fail("table_of[s] outside [0, P)");
+  }
   HIP_OK(hipSetDevice(h->device));
-  for (void *p : {(void *)h->ref_table, (void *)h->pred, (void *)h->state, (void *)h->kidx, (void *)h->order}) if (p) hipFree(p);
-  h->ref_table = h->pred = h->state = nullptr; h->kidx = nullptr; h->order = nullptr; h->have_order = false;
-  h->S = S; h->T = T;
+  for (void *p : {(void *)h->ref_table, (void *)h->pred, (void *)h->state, (void *)h->kidx, (void *)h->order, (void *)h->table_of}) if (p) hipFree(p);
+  h->ref_table = h->pred = h->state = nullptr; h->kidx = nullptr; h->order = nullptr; h->table_of = nullptr; h->have_order = false;
+  record_free(h);  // a record belongs to one initialisation (its shape is that of S)
+  h->S = S; h->T = T; h->P = P;
   const size_t B = (size_t)S * V;
-  HIP_OK(hipMalloc(&h->ref_table, (size_t)V * T * 7 * 8)); HIP_OK(hipMalloc(&h->pred, B * 7 * N * 8));
+  HIP_OK(hipMalloc(&h->ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->pred, B * 7 * N * 8));
   HIP_OK(hipMalloc(&h->state, B * 5 * 8)); HIP_OK(hipMalloc(&h->kidx, (size_t)S * 4));
-  HIP_OK(hipMalloc(&h->order, B * 4));
+  HIP_OK(hipMalloc(&h->order, B * 4)); HIP_OK(hipMalloc(&h->table_of, (size_t)S * 4));
   HIP_OK(hipMemset(h->wst, 0, (size_t)h->max_batch * h->wst_stride * 8));  // first iteration: cold multipliers
   for (void *p : {(void *)h->pred2, (void *)h->scratch, (void *)h->queue, (void *)h->ctrl, (void *)h->done, (void *)h->iter_sum}) if (p) (void)hipFree(p);
   h->pred2 = h->scratch = nullptr; h->queue = h->ctrl = h->done = h->iter_sum = nullptr; h->queue_cap = 0; h->grid_blocks = 0; h->steps_done = 0;
-  HIP_OK(hipMemcpy(h->ref_table, ref_table, (size_t)V * T * 7 * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->ref_table, tables, (size_t)P * V * T * 7 * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->table_of, tof.data(), (size_t)S * 4, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(h->kidx, k0, (size_t)S * 4, hipMemcpyHostToDevice));
   double *dn = nullptr;
   if (noise) { if (arena_reset(h->arena)) return -1; ARENA_ALLOC(h->arena, dn, B * 5 * 8); HIP_OK(hipMemcpy(dn, noise, B * 5 * 8, hipMemcpyHostToDevice)); }
   const long nt = (long)B * N;
   hipLaunchKernelGGL(loop_seed, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, T, h->ref_table,
-                     h->kidx, dn, h->pred, h->state);
+                     h->table_of, h->kidx, dn, h->pred, h->state);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(h->stream));
   return 0;
 }
 
+int cfz_loop_init(cfz_handle *h, int S, int T, const double *ref_table, const int32_t *k0, const double *noise) {
+  if (!h) return fail("null handle");
+  if (S < 1 || (long)S * (h->ks.n_nbr + 1) > h->max_batch) return fail("S * (n_nbr+1) exceeds max_batch");
+  const std::vector<int32_t> zero((size_t)S, 0);  // one plan set, followed by every scenario
+  return cfz_loop_init_tables(h, S, 1, T, ref_table, zero.data(), k0, noise);
+}
+
+int cfz_loop_record(cfz_handle *h, int K) {
+  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (K < 0) return fail("K must not be negative");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  record_free(h);
+  if (K == 0) return 0;
+  const size_t B = (size_t)h->S * (h->ks.n_nbr + 1);
+  if ((size_t)K * B * 7 > ((size_t)1 << 31)) return fail("record too large");
+  HIP_OK(hipMalloc(&h->rec, (size_t)K * B * 7 * 8)); HIP_OK(hipMalloc(&h->rec_si, (size_t)K * 2 * B * 4));
+  h->rec_cap = K;
+  return 0;
+}
+
+int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status, int32_t *iters) {
+  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (t0 < 0 || K < 1 || t0 + K > h->rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  HIP_OK(hipSetDevice(h->device));
+  const size_t B = (size_t)h->S * (h->ks.n_nbr + 1);
+  if (traj) HIP_OK(hipMemcpy(traj, h->rec + (size_t)t0 * B * 7, (size_t)K * B * 7 * 8, hipMemcpyDeviceToHost));
+  if (status || iters) {
+    std::vector<int32_t> si((size_t)K * 2 * B);
+    HIP_OK(hipMemcpy(si.data(), h->rec_si + (size_t)t0 * 2 * B, si.size() * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < K; ++k) {
+      if (status) memcpy(status + (size_t)k * B, si.data() + (size_t)k * 2 * B, B * 4);
+      if (iters) memcpy(iters + (size_t)k * B, si.data() + ((size_t)k * 2 + 1) * B, B * 4);
+    }
+  }
+  return 0;
+}
+
+int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
+                   int32_t *first_contact, int32_t *arrive) {
+  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (t0 < 0 || K < 1 || t0 + K > h->rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  HIP_OK(hipSetDevice(h->device));
+  const int S = h->S, V = h->ks.n_nbr + 1;
+  const size_t B = (size_t)S * V;
+  if (arena_reset(h->arena)) return -1;
+  double *dg = nullptr;
+  ARENA_ALLOC(h->arena, dg, B * 3 * 8);
+  hipLaunchKernelGGL(loop_goals, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, h->T, h->ref_table, h->table_of, dg);
+  HIP_OK(hipGetLastError());
+  return audit_launch(h, K, S, V, h->rec + (size_t)t0 * B * 7, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
+}
+
+int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, double pos_tol, double psi_tol, double v_tol,
+              double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive) {
+  if (!h) return fail("null handle");
+  if (K < 1 || S < 1 || V < 1 || V > CFZ_MAX_NBR + 1) return fail("K, S must be positive and V in 1..CFZ_MAX_NBR+1");
+  if (!traj || !goal) return fail("null trajectory or goal");
+  if ((size_t)K * S * V * 7 > ((size_t)1 << 31)) return fail("trajectory too large");
+  HIP_OK(hipSetDevice(h->device));
+  if (arena_reset(h->arena)) return -1;
+  double *dt_ = nullptr, *dg = nullptr;
+  ARENA_ALLOC(h->arena, dt_, (size_t)K * S * V * 7 * 8); ARENA_ALLOC(h->arena, dg, (size_t)S * V * 3 * 8);
+  HIP_OK(hipMemcpyAsync(dt_, traj, (size_t)K * S * V * 7 * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(dg, goal, (size_t)S * V * 3 * 8, hipMemcpyHostToDevice, h->stream));
+  return audit_launch(h, K, S, V, dt_, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
+}
+
 int cfz_loop_step(cfz_handle *h) {
   if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (record_room(h, 1)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->S, B = S * V;
   const long nt = (long)B * N;
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
-                     h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu);
+                     h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu);
   HIP_OK(hipGetLastError());
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream,
                    h->have_order ? h->order : nullptr, 1)) return -1;
   hipLaunchKernelGGL(order_by_iters, dim3(1), dim3(1024), 0, h->stream, B, h->iters, h->order);
   HIP_OK(hipGetLastError());
   h->have_order = true;
+  double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
+  int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
-                     h->status, h->zu, h->pred, h->state, h->kidx);
+                     h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si);
   HIP_OK(hipGetLastError());
+  if (h->rec) h->rec_used += 1;
   HIP_OK(hipStreamSynchronize(h->stream));
   HIP_OK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
   h->ms_pending = false;
@@ -967,6 +1182,7 @@ int cfz_loop_step(cfz_handle *h) {
 int cfz_loop_run(cfz_handle *h, int K) {
   if (!h || !h->pred) return fail("cfz_loop_init has not been called");
   if (K < 1) return fail("K must be positive");
+  if (record_room(h, K)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->S, B = S * V;
   const size_t total = (size_t)B * K;
@@ -1011,11 +1227,14 @@ int cfz_loop_run(cfz_handle *h, int K) {
     HIP_OK(hipStreamSynchronize(h->stream));  // `first` and `ctrl0` are host temporaries
   }
   HIP_OK(hipEventRecord(h->ev0, h->stream));
+  double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
+  int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
   hipLaunchKernelGGL(loop_kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
-                     h->ref_table, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
+                     h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
                      h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride,
-                     std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0);
+                     std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0, rec, rec_si);
   HIP_OK(hipGetLastError());
+  if (h->rec) h->rec_used += K;
   HIP_OK(hipEventRecord(h->ev1, h->stream));
   // predictions after K iterations live in parity K%2; advance the scenario clocks by K
   HIP_OK(hipMemcpyAsync(h->pred, h->pred2 + (size_t)(K & 1) * B * 7 * N, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));

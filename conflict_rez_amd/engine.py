@@ -160,6 +160,11 @@ def load_library(path=None):
     lib.cfz_loop_last_converged.restype = C.c_long
     lib.cfz_loop_last_status_counts.argtypes = [vp, vp]
     lib.cfz_loop_get.argtypes = [vp, vp, vp, vp, vp]
+    lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.cfz_loop_record.argtypes = [vp, C.c_int]
+    lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.cfz_loop_audit.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.cfz_audit.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -167,8 +172,11 @@ def load_library(path=None):
 EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
-    "cfz_loop_get cfz_last_error"
+    "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit"
 ).split()
+
+# tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
+ARRIVE_TOL = dict(pos_tol=0.3, psi_tol=0.1, v_tol=0.1)
 
 
 def default_options(**overrides):
@@ -534,26 +542,89 @@ class Engine:
         return lam, mu, s, d
 
     # ---- batched closed loop ------------------------------------------------------------------------
-    def loop_init(self, ref_table, k0, noise=None):
-        """ref_table [V,T,7] (x,y,psi,v,delta,a,w), k0 int32 [S], noise [S,V,5] or None."""
+    def loop_init(self, ref_table, k0, noise=None, table_of=None):
+        """ref_table [V,T,7] (x,y,psi,v,delta,a,w) followed by every scenario (`cfz_loop_init`), or a pool of plan sets [P,V,T,7]
+        of which scenario s follows set table_of[s] (`cfz_loop_init_tables`; table_of None: set s, P == S); k0 int32 [S],
+        noise [S,V,5] or None."""
         V = self.spec.n_nbr + 1
         ref_table = np.ascontiguousarray(ref_table, dtype=np.float64)
-        T = ref_table.shape[1]
-        ref_table = _f64(ref_table, (V, T, 7))
         k0 = np.ascontiguousarray(k0, dtype=np.int32)
         S = k0.shape[0]
         if noise is not None:
             noise = _f64(noise, (S, V, 5))
+        if ref_table.ndim == 3:
+            if table_of is not None:
+                raise ValueError("table_of needs a pool of plan sets [P, V, T, 7]")
+            T = ref_table.shape[1]
+            ref_table = _f64(ref_table, (V, T, 7))
+            self._ck(self.lib.cfz_loop_init(self._h, S, T, _ptr(ref_table), _ptr(k0), _ptr(noise)), "cfz_loop_init")
+        else:
+            P, T = ref_table.shape[0], ref_table.shape[2]
+            ref_table = _f64(ref_table, (P, V, T, 7))
+            tof = None if table_of is None else np.ascontiguousarray(table_of, dtype=np.int32)
+            if tof is not None and tof.shape != (S,):
+                raise ValueError(f"table_of must have shape ({S},), got {tof.shape}")
+            self._ck(self.lib.cfz_loop_init_tables(self._h, S, P, T, _ptr(ref_table), _ptr(tof), _ptr(k0), _ptr(noise)),
+                     "cfz_loop_init_tables")
         self._S, self._V = S, V
-        self._ck(self.lib.cfz_loop_init(self._h, S, T, _ptr(ref_table), _ptr(k0), _ptr(noise)), "cfz_loop_init")
+        self._rec_cap, self._rec_used = 0, 0
 
     def loop_step(self):
         self._ck(self.lib.cfz_loop_step(self._h), "cfz_loop_step")
+        if self._rec_cap:
+            self._rec_used += 1
 
     def loop_run(self, K):
         """K closed-loop iterations in one persistent launch (same results as K x loop_step)."""
         self._ck(self.lib.cfz_loop_run(self._h, int(K)), "cfz_loop_run")
+        if self._rec_cap:
+            self._rec_used += int(K)
         return int(self.lib.cfz_loop_last_iterations(self._h))
+
+    def loop_record(self, K):
+        """`cfz_loop_record`: record the next K steps (state after the plant, applied (a, w), status, iterations); 0 stops."""
+        self._ck(self.lib.cfz_loop_record(self._h, int(K)), "cfz_loop_record")
+        self._rec_cap, self._rec_used = int(K), 0
+
+    def loop_history(self, t0=0, K=None):
+        """`cfz_loop_history`: recorded steps [t0, t0 + K) (K None: all recorded so far) ->
+        dict(traj [K,S,V,7] (x, y, psi, v, delta, a, w), status [K,S,V], iters [K,S,V])."""
+        K = self._rec_used - int(t0) if K is None else int(K)
+        S, V = self._S, self._V
+        out = dict(traj=np.empty((K, S, V, 7)), status=np.empty((K, S, V), np.int32), iters=np.empty((K, S, V), np.int32))
+        self._ck(self.lib.cfz_loop_history(self._h, int(t0), K, _ptr(out["traj"]), _ptr(out["status"]), _ptr(out["iters"])),
+                 "cfz_loop_history")
+        return out
+
+    @staticmethod
+    def _audit_out(S, V):
+        return dict(clear=np.empty((S, 2)), where=np.empty((S, 6), np.int32), first_contact=np.empty(S, np.int32),
+                    arrive=np.empty((S, V), np.int32))
+
+    def loop_audit(self, t0=0, K=None, pos_tol=ARRIVE_TOL["pos_tol"], psi_tol=ARRIVE_TOL["psi_tol"], v_tol=ARRIVE_TOL["v_tol"]):
+        """`cfz_loop_audit` over recorded steps [t0, t0 + K) (K None: all recorded so far) -> dict(clear [S,2] (smallest
+        vehicle-vehicle, vehicle-obstacle signed distance), where [S,6] ((step, u, w), (step, v, j) of those), first_contact [S],
+        arrive [S,V]); steps count from t0, -1 = never."""
+        K = self._rec_used - int(t0) if K is None else int(K)
+        o = self._audit_out(self._S, self._V)
+        self._ck(self.lib.cfz_loop_audit(self._h, int(t0), K, float(pos_tol), float(psi_tol), float(v_tol), _ptr(o["clear"]),
+                                         _ptr(o["where"]), _ptr(o["first_contact"]), _ptr(o["arrive"])), "cfz_loop_audit")
+        return o
+
+    def audit(self, traj, goal, pos_tol=ARRIVE_TOL["pos_tol"], psi_tol=ARRIVE_TOL["psi_tol"], v_tol=ARRIVE_TOL["v_tol"]):
+        """`cfz_audit` of a host trajectory traj [K,S,V,7] (x, y, psi, v, ...) with goals [S,V,3], against this engine's body and
+        obstacles -> the dict of `loop_audit`."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        if traj.ndim != 4 or traj.shape[3] < 4:
+            raise ValueError(f"expected traj of shape [K, S, V, 7], got {traj.shape}")
+        K, S, V = traj.shape[:3]
+        if traj.shape[3] != 7:
+            t7 = np.zeros((K, S, V, 7)); t7[..., : traj.shape[3]] = traj; traj = t7
+        goal = _f64(goal, (S, V, 3))
+        o = self._audit_out(S, V)
+        self._ck(self.lib.cfz_audit(self._h, K, S, V, _ptr(traj), _ptr(goal), float(pos_tol), float(psi_tol), float(v_tol),
+                                    _ptr(o["clear"]), _ptr(o["where"]), _ptr(o["first_contact"]), _ptr(o["arrive"])), "cfz_audit")
+        return o
 
     def loop_last_converged(self):
         """Solves of the last `loop_run` that converged (status 0)."""

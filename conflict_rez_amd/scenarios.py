@@ -218,3 +218,131 @@ def mpc_batch_from_table(spec: ProblemSpec, table, k0, noise):
             for o, u in enumerate(others):
                 nbr[b, o] = preds[u][adv][:, :3].T
     return x0, ref, nbr, zu
+
+
+def plan_scenarios(strategies, init_offsets=None, final_headings=None, dt=0.1, pad=30, device=0):
+    """The reference tables of P strategies in one planning chain: `VehicleFollower.plan_single_path(strict=True)`
+    (vehicle_follower.py:73, reference :91-138) for all P x V plans with ONE `cfz_state_ws` launch and ONE `cfz_colloc` launch
+    (heterogeneous strategy lengths are one batch), each plan sampled every `dt` as `planned_reference_table` samples it and
+    padded to a common length by holding the goal at rest.  `dual_ws` is skipped: `cfz_colloc` does not read the duals
+    (`Vehicle.setup_single_final_problem`).
+    strategies: P dicts agent -> list of {"front", "back"} (`strategy.generate_strategy`), the same V agents in each;
+    init_offsets [P][V][3] (x, y, psi added to each start, as `VehicleFollower(init_offset=...)`); final_headings [P][V] or
+    None (default: the heading of the last cell pair, as `planned_reference_table`).
+    Returns dict(tables [P,V,T,7], lengths [P,V] (samples before the padding, 0 for a plan that failed), ws_status, ws_iters,
+    colloc_status, colloc_iters [P,V] (-1: stage not run because the one before it failed), ok [P] (every plan of the strategy
+    converged)).  A plan that does not converge is reported, not replaced: its rows of the table stay zero."""
+    import tempfile
+
+    from . import engine as eng
+    from . import strategy as strat
+    from .control.compute_sets import interp_along_sets
+    from .control.vehicle import radau_points
+    from .control.vehicle_follower import VehicleFollower
+    from .pytypes import VehiclePrediction, VehicleState
+
+    N_ws, K, N_per_set, shrink = 30, 5, 5, 0.5  # plan_single_path's defaults
+    P = len(strategies)
+    agents = sorted(strategies[0])
+    V = len(agents)
+    if any(sorted(h) != agents for h in strategies):
+        raise ValueError("every strategy must have the same agents")
+    plans = []  # (follower, init_pose, tube, guess, final_heading), [p][v] flattened
+    with tempfile.TemporaryDirectory() as d:
+        for p, hist in enumerate(strategies):
+            fn = os.path.join(d, f"strategy_{p}")
+            strat.write_strategy(fn, hist)
+            paths = interp_along_sets(fn, VehicleBody(), N_ws)
+            for i, a in enumerate(agents):
+                off = VehicleState()
+                if init_offsets is not None:
+                    off.x.x, off.x.y, off.e.psi = (float(c) for c in np.asarray(init_offsets, float)[p, i, :3])
+                fh = float(paths[a][-1, 2]) if final_headings is None else final_headings[p][i]
+                v = VehicleFollower(rl_file_name=fn, agent=a, color={"front": (1, 0, 0), "back": (0, 1, 0)}, init_offset=off,
+                                    final_heading=fh, printer=lambda *_: None)
+                s0 = v.init_state
+                init_pose = [s0.x.x + off.x.x, s0.x.y + off.x.y, s0.e.psi + off.e.psi]
+                tube = [((st["back"].A, st["back"].b), (st["front"].A, st["front"].b)) for st in v.rl_tube[1:]]
+                plans.append((v, off, init_pose, tube, paths[a], fh))
+    v0 = plans[0][0]
+    vc, r = v0.vehicle_config, v0.region
+    bounds = [r.x_min, r.x_max, r.y_min, r.y_max, vc.v_min, vc.v_max, vc.delta_min, vc.delta_max, vc.a_min, vc.a_max, vc.w_delta_min, vc.w_delta_max]
+    n = P * V
+    ws_status, ws_iters = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    co_status, co_iters = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    # stage 1: every warm start in one launch (Vehicle.state_ws, vehicle.py:99-231)
+    ws = eng.state_ws([q[2] for q in plans], [q[3] for q in plans], [q[4] for q in plans], [q[5] for q in plans], device=device,
+                      N=N_ws, dt=dt, wb=v0.vehicle_body.wb, shrink_tube=shrink, bounded_input=0, bounds=bounds)
+    fps, idx = [], []
+    for b, (res, q) in enumerate(zip(ws, plans)):
+        ws_status[b], ws_iters[b] = res["status"], res["iters"]
+        if res["status"] != 0:
+            continue
+        v = q[0]
+        T = N_ws * (v.num_sets - 1)
+        tr = res["traj"]
+        zu0 = VehiclePrediction()
+        zu0.t = np.linspace(0, T * dt, T + 1, endpoint=True)
+        zu0.x, zu0.y, zu0.psi, zu0.v, zu0.u_steer = (tr[:, c].copy() for c in range(5))
+        zu0.u_a, zu0.u_steer_dot = tr[:, 5].copy(), tr[:, 6].copy()
+        zuc = v.interp_ws_for_collocation(zu0=zu0, K=K, N_per_set=N_per_set)
+        fps.append(v.setup_single_final_problem(zu0=zuc, init_offset=q[1], final_heading=q[5], K=K, N_per_set=N_per_set, shrink_tube=shrink))
+        idx.append(b)
+    # stage 2: every collocation plan in one launch (vehicle.py:360-661)
+    sols = {}
+    if fps:
+        res = eng.colloc(fps[0]["spec"], [f["init_pose"] for f in fps], [f["tube"] for f in fps], [f["guess"] for f in fps],
+                         [f["dt0"] for f in fps], [f["final_heading"] for f in fps], device=device, N_per_set=N_per_set, shrink_tube=shrink)
+        for b, rr in zip(idx, res):
+            co_status[b], co_iters[b] = rr["status"], rr["iters"]
+            if rr["status"] == 0:
+                sols[b] = rr
+    # sampling: the collocation interpolant every dt (get_solution / get_interpolator, vehicle.py:663-829)
+    tau_root = np.append(0.0, radau_points(K))
+    trajs = {}
+    for b, rr in sols.items():
+        v = plans[b][0]
+        tr, dtp = rr["traj"], float(rr["dt"])
+        Nc = tr.shape[0]
+        result = VehiclePrediction()
+        result.t = (np.arange(Nc)[:, None] + tau_root[None, :]).ravel() * dtp
+        result.x, result.y, result.psi, result.v, result.u_steer, result.u_a, result.u_steer_dot = (tr[:, :, c].ravel() for c in range(7))
+        v.get_interpolator(K=K, N=Nc, dt=dtp, opt=result)
+        tt = np.arange(0.0, float(result.t[-1]) + 0.5 * dt, dt)
+        s_ = v.interpolate_states(tt)
+        trajs[b] = np.stack([s_.x, s_.y, s_.psi, s_.v, s_.u_steer, s_.u_a, s_.u_steer_dot], 1)
+    T = (max(len(t) for t in trajs.values()) if trajs else 1) + pad
+    tables = np.zeros((P, V, T, 7))
+    lengths = np.zeros((P, V), np.int64)
+    for b, tr in trajs.items():
+        p, i = divmod(b, V)
+        tables[p, i, : len(tr)] = tr
+        tables[p, i, len(tr):, :3] = tr[-1, :3]  # goal pose held, at rest
+        lengths[p, i] = len(tr)
+    sh = (P, V)
+    return dict(tables=tables, lengths=lengths, ws_status=ws_status.reshape(sh), ws_iters=ws_iters.reshape(sh),
+                colloc_status=co_status.reshape(sh), colloc_iters=co_iters.reshape(sh), ok=(co_status.reshape(sh) == 0).all(1))
+
+
+def distinct_strategies(n_vehicles=4, delays=(0, 1, 2)):
+    """The distinct strategies `strategy.generate_strategy` gives over every priority order x start delays in delays^n (infeasible
+    combinations skipped), in the order first met.  Returns (strategies, combos): combos[i] lists the (order, delays) that give
+    strategy i."""
+    from itertools import permutations, product
+
+    from . import strategy as strat
+
+    seen, out, combos = {}, [], []
+    for order in permutations(range(n_vehicles)):
+        for dl in product(delays, repeat=n_vehicles):
+            try:
+                h = strat.generate_strategy(n_vehicles, list(order), list(dl))
+            except RuntimeError:
+                continue
+            key = repr(sorted((a, [sorted(c.items()) for c in h[a]]) for a in h))
+            if key not in seen:
+                seen[key] = len(out)
+                out.append(h)
+                combos.append([])
+            combos[seen[key]].append((order, dl))
+    return out, combos

@@ -389,6 +389,40 @@ int cfz_loop_last_status_counts(const cfz_handle *h, long counts[6]);
 /* state[S][V][5], pred[S][V][7][N], status int32[S][V] of the last step; NULL to skip. */
 int cfz_loop_get(cfz_handle *h, double *state, double *pred, int32_t *status, int32_t *iters);
 
+/* ---- closed loop over per-scenario plans -------------------------------------------------------
+ * tables[P][V][T][7]: a pool of P plan sets (each what cfz_loop_init takes as ref_table); scenario s follows set table_of[s]
+ * (NULL: set s, which needs P == S).  Otherwise exactly cfz_loop_init, which is this call with P = 1 and every scenario on set 0.
+ * Refused: P < 1, table_of[s] outside [0, P), S * V > max_batch, NULL tables or k0. */
+int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *tables, const int32_t *table_of, const int32_t *k0,
+                         const double *noise);
+
+/* ---- record of the realised trajectory (the reference's `final_traj`, vehicle_follower.py:74-82, :526-563) ----------------
+ * cfz_loop_record(h, K): the next K steps (of cfz_loop_step and cfz_loop_run alike) each write, per scenario and vehicle, the
+ * state after the plant (x, y, psi, v, delta) and the applied input (a, w) (:556-563), and the status and iterations of that
+ * step's solve.  K = 0 stops recording and frees the record; cfz_loop_init / cfz_loop_init_tables do the same.  A step or run
+ * that would go past K recorded steps is refused before anything is launched (the loop's state stays as it was).
+ * cfz_loop_history: recorded steps [t0, t0 + K) as traj[K][S][V][7], status[K][S][V], iters[K][S][V]; any output may be NULL. */
+int cfz_loop_record(cfz_handle *h, int K);
+int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status, int32_t *iters);
+
+/* ---- audit of a realised trajectory --------------------------------------------------------------------------------------
+ * Signed distance of two convex polygons: their Euclidean distance if they are disjoint, else minus the penetration depth (the
+ * smallest overlap of their projections over the face normals of both, 0 when they only touch).  Bodies: the spec's rectangle g
+ * at (x, y, psi); obstacles: the spec's n_obs polygons.  Per scenario s over the steps [t0, t0 + K) (step numbers relative to t0):
+ *   clear[s][0] the smallest vehicle-vehicle signed distance, where[s][0:3] its (step, u, w) with u < w;
+ *   clear[s][1] the smallest vehicle-obstacle signed distance, where[s][3:6] its (step, v, j)   (+inf and -1: nothing to measure);
+ *   first_contact[s] the first step with a negative signed distance, -1 if none;
+ *   arrive[s][v] the first step at which vehicle v is within pos_tol of its goal in (x, y), within psi_tol of its heading
+ *   (wrapped) and |v| <= v_tol, -1 if never.
+ * Ties go to the lowest step, then the lowest index.  One wavefront per scenario, deterministic.  Any output may be NULL.
+ * cfz_loop_audit: the handle's record; goals = the last sample of the table each scenario follows.
+ * cfz_audit: a host trajectory traj[K][S][V][7] (x, y, psi, v, ...: what cfz_loop_history returns, or a `_follower_final.pkl`
+ * of the reference laid out so) with goal[S][V][3]; V in 1..CFZ_MAX_NBR+1 need not be the handle's. */
+int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
+                   int32_t *first_contact, int32_t *arrive);
+int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, double pos_tol, double psi_tol, double v_tol,
+              double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive);
+
 const char *cfz_last_error(void);
 /* First 16 hex digits of the SHA-256 over the kernel sources this library was built from (__graft_entry__.source_hash; "unknown" for
  * a build made by hand).  bench.py quotes profiler counters from profiles/ only if they were taken on a library with the same hash. */
