@@ -160,8 +160,10 @@ class VehicleFollower(Vehicle):
         raise ValueError("unexpected shape when advancing the array to one step ahead.")
 
     # ---- one MPC step, split so that several vehicles can share one kernel launch ----------------------
-    def prepare_step(self):
-        """Parameters and warm start of this step (:432-476): (x0[5], ref[3,N], nbr[n_nbr,3,N], zu[7,N])."""
+    def prepare_step(self, current=()):
+        """Parameters and warm start of this step (:432-476): (x0[5], ref[3,N], nbr[n_nbr,3,N], zu[7,N]).
+        current: agents whose predictions in `others_pred` were made in this same step (a sequential exchange); they already
+        start at this step's time and go into nbr as they are.  The others' are advanced one step, as in the reference."""
         s = self.state
         x0 = np.array([s.x.x, s.x.y, s.e.psi, s.v.v, s.u.u_steer], float)
         cur = self.get_current_ref()
@@ -169,7 +171,10 @@ class VehicleFollower(Vehicle):
         nbr = np.zeros((len(self.others), 3, self.N))
         for o, other in enumerate(self.others):
             p = self.others_pred[other]
-            nbr[o] = np.stack([self._adv_onestep(p.x), self._adv_onestep(p.y), self._adv_onestep(p.psi)])
+            if other in current:
+                nbr[o] = np.stack([p.x, p.y, p.psi])
+            else:
+                nbr[o] = np.stack([self._adv_onestep(p.x), self._adv_onestep(p.y), self._adv_onestep(p.psi)])
         zu = np.stack([self._adv_onestep(getattr(self.pred, n)) for n in _PRIMAL])
         return x0, ref, nbr, zu
 
@@ -205,9 +210,9 @@ class VehicleFollower(Vehicle):
                          (ft.u_steer, s.u.u_steer), (ft.u_a, s.u.u_a), (ft.u_steer_dot, s.u.u_steer_dot)):
             lst.append(val)
 
-    def step(self):
-        """step the controller (:428-563)"""
-        x0, ref, nbr, zu = self.prepare_step()
+    def step(self, current=()):
+        """step the controller (:428-563); current: as `prepare_step`"""
+        x0, ref, nbr, zu = self.prepare_step(current)
         # a batch of one in THIS vehicle's carry slot of the (possibly shared) engine: after a converged step the next
         # one starts from its own multipliers (the reference hands the previous duals to opti.set_initial, :458-464,
         # :475-476), never from another vehicle's
@@ -218,7 +223,9 @@ class VehicleFollower(Vehicle):
 
 class MultiDistributedFollower:
     """Several vehicles as distributed path followers (:566-670); the four `step()` solves of one
-    iteration are independent (Jacobi exchange, :636-641) and go to the GPU as one batch."""
+    iteration are independent (Jacobi exchange, :636-641) and go to the GPU as one batch, or, with
+    `solve(order=...)`, run one after another, each against the predictions its predecessors made in
+    the same iteration (sequential exchange)."""
 
     def __init__(self, rl_file_name, spline_ws_config, colors, init_offsets, final_headings, visualizer=None):
         self.rl_file_name = rl_file_name
@@ -255,18 +262,19 @@ class MultiDistributedFollower:
             v.get_current_ref()
             self.single_results[v.agent] = v.reference_traj
 
-    def solve(self, num_iter: int = 500, dump: bool = True):
+    def solve(self, num_iter: int = 500, dump: bool = True, order: List[str] = None):
+        """num_iter MPC iterations (:630-663).  order None: Jacobi, the reference's exchange.  order (agent names, each once):
+        in every iteration the agents step in that order; each plans against the predictions of the agents before it from
+        this iteration (not advanced) and the others' from the previous one (advanced), as a batch of one in its own slot."""
+        if order is not None:
+            order = list(order)
+            if sorted(order) != sorted(self.agents):
+                raise ValueError(f"order must name every agent of {self.agents} once, got {order}")
         for _ in range(num_iter):
-            for v in self.vehicles:
-                v.get_others_pred(self.vehicles)
-            batch = [v.prepare_step() for v in self.vehicles]
-            t0 = time.perf_counter()
-            # slot b is always vehicle b: a vehicle whose last step converged starts from its multipliers
-            carry = [int(getattr(v, "status", 1) == 0) for v in self.vehicles]
-            out = self.engine.solve(*(np.stack([b[i] for b in batch]) for i in range(4)), carry=carry)
-            wall = time.perf_counter() - t0
-            for b, v in enumerate(self.vehicles):
-                v.finish_step(out, b, solve_time=wall / len(self.vehicles))
+            if order is not None:
+                self._sequential_iteration(order)
+            else:
+                self._jacobi_iteration()
             if self.vis is not None:
                 self.vis.draw_background(), self.vis.draw_obstacles()
                 for v in self.vehicles:
@@ -283,3 +291,28 @@ class MultiDistributedFollower:
 
             dump_file(self.final_results, f"{self.rl_file_name}_follower_final.pkl")
             dump_file(self.iter_time, f"{self.rl_file_name}_follower_iter_time.pkl")
+
+    def _sequential_iteration(self, order):
+        by_agent = {v.agent: v for v in self.vehicles}
+        stepped = []
+        for a in order:
+            v = by_agent[a]
+            v.get_others_pred(self.vehicles)
+            x0, ref, nbr, zu = v.prepare_step(current=tuple(stepped))
+            t0 = time.perf_counter()
+            out = self.engine.solve(x0[None], ref[None], nbr[None], zu[None], carry=[int(getattr(v, "status", 1) == 0)],
+                                    slots=[v.slot])
+            v.finish_step(out, 0, solve_time=time.perf_counter() - t0)
+            stepped.append(a)
+
+    def _jacobi_iteration(self):
+        for v in self.vehicles:
+            v.get_others_pred(self.vehicles)
+        batch = [v.prepare_step() for v in self.vehicles]
+        t0 = time.perf_counter()
+        # slot b is always vehicle b: a vehicle whose last step converged starts from its multipliers
+        carry = [int(getattr(v, "status", 1) == 0) for v in self.vehicles]
+        out = self.engine.solve(*(np.stack([b[i] for b in batch]) for i in range(4)), carry=carry)
+        wall = time.perf_counter() - t0
+        for b, v in enumerate(self.vehicles):
+            v.finish_step(out, b, solve_time=wall / len(self.vehicles))

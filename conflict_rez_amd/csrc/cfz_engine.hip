@@ -7,6 +7,7 @@
 //                  (8*(5 + 3N + 3N n_nbr + 2*7N) B per instance) beside the carry record of the slot (8.8 KB)
 //   loop_kernel    the persistent closed loop (cfz_loop_run): the same solver body fed from per-iteration ticket queues of
 //                  (scenario, vehicle, iteration) work items, hand-offs between workgroups at agent scope
+//   loop_kernel_seq  the same with the sequential exchange of cfz_loop_set_order (one body: cfz_loop_body.inl)
 //   loop_prep      closed loop: parameters and shifted warm start of every vehicle from the
 //                  previous predictions (reference vehicle_follower.py:432-476, 636-637)
 //   loop_post      closed loop: read-back or shift fallback, plant integration, clock
@@ -86,14 +87,18 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
 // ---- closed loop ------------------------------------------------------------------------------
 // pred[S][V][7][N] last predictions, state[S][V][5], kidx[S] reference sample index.  ref_table[P][V][T][7] is a pool of plan
 // sets; scenario s follows set table_of[s].
-// One thread per (instance, stage).
+// xperm / xrank [S][V] (cfz_loop_set_order): the exchange order of every scenario and its inverse.  NULL: Jacobi, one thread per
+// (instance, stage) of all B instances.  Otherwise round r of a sequential step: one thread per (scenario, stage), for the vehicle
+// v = xperm[s][r]; the neighbours ranked before it have already posted this step's prediction to `pred`, which starts at this
+// step's time and is read as it stands; the others' (and v's own warm start) are the previous step's, advanced.
 __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, const int32_t *table_of, const int32_t *kidx,
                           const double *pred, const double *state, double *x0, double *ref, double *nbr,
-                          double *zu) {
+                          double *zu, int r, const int32_t *xperm, const int32_t *xrank) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= (long)S * V * N) return;
+  if (tid >= (long)(xperm ? S : S * V) * N) return;
   const int k = (int)(tid % N);
-  const int b = (int)(tid / N);
+  int b = (int)(tid / N);
+  if (xperm) b = b * V + xperm[b * V + r];
   const int s = b / V, v = b - s * V;
   const int ka = (k + 1 < N) ? k + 1 : N - 1;  // _adv_onestep (:413-426)
   if (k < 5) x0[b * 5 + k] = state[b * 5 + k];
@@ -105,7 +110,8 @@ __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, c
   for (int u = 0; u < V; ++u) {
     if (u == v) continue;
     const size_t bo = (size_t)s * V + u;
-    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + o) * 3 + c) * N + k] = pred[(bo * 7 + c) * N + ka];
+    const int ku = (xrank && xrank[bo] < r) ? k : ka;
+    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + o) * 3 + c) * N + k] = pred[(bo * 7 + c) * N + ku];
     ++o;
   }
 }
@@ -117,11 +123,14 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
 
 // One thread per instance: accept the solution or shift the old prediction, integrate the plant.  rec (NULL: no record) is
 // this step's slice [S][V][7] of the record: state after the plant and the applied (a, w); rec_si its [2][S][V] status, iters.
+// xperm NULL: all B instances.  Otherwise round r of a sequential step (loop_prep): one thread per scenario, for its vehicle of
+// rank r; the clock advances with the last round, after every vehicle has read its reference.
 __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
                           const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
-                          int32_t *rec_si) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= S * V) return;
+                          int32_t *rec_si, int r, const int32_t *xperm) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= (xperm ? S : S * V)) return;
+  if (xperm) b = b * V + xperm[b * V + r];
   double *pb = pred + (size_t)b * 7 * N;
   if (status[b] == 0) {
     for (int i = 0; i < 7 * N; ++i) pb[i] = zu[(size_t)b * 7 * N + i];
@@ -133,7 +142,7 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
   for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
   cfz::rk4_step<false>(z, pb[5 * N], pb[6 * N], dt, wb, plant_substeps, out, nullptr);
   for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
-  if (b % V == 0) kidx[b / V] += 1;
+  if (xperm ? r == V - 1 : b % V == 0) kidx[b / V] += 1;
   if (rec) {
     double *r = rec + (size_t)b * 7;
     for (int i = 0; i < 5; ++i) r[i] = out[i];
@@ -230,147 +239,37 @@ __global__ __launch_bounds__(1024) void order_by_iters(int B, const int32_t *ite
 #endif
 //   ref_table[P][V][T][7], table_of[S]: the pool of plan sets and the one each scenario follows (as loop_prep)
 //   rec[K][S][V][7], rec_si[K][2][S][V]: the record of this launch's iterations (NULL: none; as loop_post)
+// kSeq (loop_kernel_seq): the sequential exchange of cfz_loop_set_order.  xperm / xrank [S][V] are the order of every scenario and
+// its inverse (written by the host before the launch: plain loads, no acquire).  The V solves of a scenario's iteration t run one
+// after another: the item of rank r publishes the item of rank r + 1 into the same queue t, the last rank publishes rank 0 of
+// t + 1.  Every iteration still receives exactly B slots, so the ticket rules above hold unchanged.  A vehicle reads the neighbours
+// ranked before it from the output parity at stage k (iteration t's predictions start at time t), the others from the input
+// parity, advanced.  The new edge, rank r to rank r + 1, has the same release / acquire pair as the edge from t to t + 1, and the
+// chain of such pairs covers the ranks below r - 1 as well (release / acquire is transitive).
+// It cannot deadlock: a scenario has exactly one item in flight, every completion publishes exactly one item, and the workgroup
+// that completed is then free to take it; the grid (at most S workgroups) never exceeds the items in flight.
+// Two kernels, one body (cfz_loop_body.inl, included into both): loop_kernel keeps its symbol (profiles and bench.py name rows
+// by it), takes no argument for the exchange rule and compiles to the Jacobi loop's code alone (a __device__ template with the
+// `__restrict__` parameter moved the kernel's register allocation: 16 more VGPR spills).
 __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(const KArgs *__restrict__ ka, int S, int V, int K, int T,
                                                         const double *ref_table, const int32_t *table_of, const int32_t *kidx0, int t_base,
                                                         double *pred, double *state, double *scratch, int32_t *qbuf,
                                                         int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
                                                         double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
                                                         double *rec, int32_t *rec_si) {
-  extern __shared__ double smem[];
-  const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
-  const int N = sp.N, nn = sp.n_nbr, B = S * V, tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  double *my = scratch + (size_t)blockIdx.x * (5 + 3 * N + nn * 3 * N + 7 * N);
-  double *ref = my + 5;  // (the record keeps the layout x0 | ref | nbr | zu of the stepwise path; only ref is used here)
-  int32_t *head = qbuf, *tail = qbuf + K, *slots = qbuf + 2 * K;
-  // what wavefront 0 popped, for wavefront 1: {iteration t (-1: leave), instance b}.  Lives in the reduction exchange
-  // area of the workspace, which is idle between two solves.
-  volatile int32_t *cmd = reinterpret_cast<volatile int32_t *>(smem + L.xw);
-#define CFZ_LD(p) __builtin_amdgcn_readfirstlane(__hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-  int idle = 0;
-  while (true) {
-    if (wave == 0) {
-      // ---- pop (wavefront 0 only): lowest iteration first -----------------------------------------------
-      int t = -1, b = -1;
-      while (true) {
-        int t0 = CFZ_LD(&ctrl[0]);
-        const int hint = t0;
-        while (t0 < K && CFZ_LD(&head[t0]) >= B) ++t0;
-        if (t0 > hint && lane == 0) atomicMax(&ctrl[0], t0);
-        if (t0 >= K) break;  // every item of every iteration has been handed out
-        int idx = 0;
-        for (int tt = t0; tt < K; ++tt) {
-          const int hd = CFZ_LD(&head[tt]), tl = CFZ_LD(&tail[tt]);
-          if (tl == 0) break;  // no scenario has reached iteration tt yet, hence none is further either
-          if (hd >= tl) continue;
-          idx = __builtin_amdgcn_readfirstlane(atomicAdd(&head[tt], lane == 0 ? 1 : 0));
-          if (idx < B) { t = tt; break; }
-        }
-        if (t < 0) {  // nothing to hand out right now
-          __builtin_amdgcn_s_sleep(32);
-          if (++idle > (1 << 22) || CFZ_LD(&ctrl[2])) { if (lane == 0) atomicExch(&ctrl[2], 1); break; }
-          continue;
-        }
-        idle = 0;
-        for (int spins = 0; (b = CFZ_LD(&slots[(size_t)t * B + idx])) < 0; ++spins) {
-          __builtin_amdgcn_s_sleep(8);
-          if (spins > (1 << 23) || CFZ_LD(&ctrl[2])) break;
-        }
-        if (b < 0) { if (lane == 0) atomicExch(&ctrl[2], 1); t = -1; }
-        break;
-      }
-      CFZ_MARK(1);
-      // acquire: predictions / states written by other workgroups.  One agent-scope acquire by the polling wavefront
-      // (invalidates this CU's L1), completed before the barrier that releases the other wavefront's loads.
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) { cmd[0] = t; cmd[1] = b; }
-    }
-    __syncthreads();
-    const int t = cmd[0], b = cmd[1];
-    if (t < 0) break;
-    CFZ_MARK(2);
-    // The launch ends with its slowest scenario (a chain of K dependent iterations).  A workgroup serving the oldest open
-    // iteration is on that critical path: its two wavefronts take issue priority over the wavefronts they share their
-    // SIMDs with (VALU issue is arbitrated by priority, then age), the others give way.
-    if (prio_lag >= 0) {
-      if (t <= CFZ_LD(&ctrl[0]) + prio_lag) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-    }
-    const int s = b / V, v = b - s * V;
-    const double *pin = pred + (size_t)(t & 1) * B * 7 * N;   // predictions after iteration t-1
-    double *pout = pred + (size_t)((t + 1) & 1) * B * 7 * N;
-    const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
-    // ---- parameters and shifted warm start (vehicle_follower.py:432-476), straight into the solver's workspace: measured
-    // state, neighbours' poses with cos / sin, warm start (solve_instance's `preloaded` form); only the reference goes through
-    // a global record (the solver reads it from there in every iteration)
-    if (tid < 5) smem[L.x0 + tid] = state[b * 5 + tid];
-    for (int k = tid; k < N; k += cfz::kNL) {
-      const int ka = (k + 1 < N) ? k + 1 : N - 1;
-      int kr = kidx0[s] + t_base + t + k; if (kr > T - 1) kr = T - 1;
-      for (int c = 0; c < 3; ++c) ref[c * N + k] = tab[((size_t)v * T + kr) * 7 + c];
-      for (int c = 0; c < 7; ++c) smem[L.p + k * cfz::kNP + c] = pin[((size_t)b * 7 + c) * N + ka];
-      int o = 0;
-      for (int u = 0; u < V; ++u) {
-        if (u == v) continue;
-        const size_t bo = (size_t)s * V + u;
-        double *q = smem + L.nb4 + (k * nn + o) * 4;
-        const double po = pin[(bo * 7 + 2) * N + ka];
-        q[0] = pin[(bo * 7 + 0) * N + ka]; q[1] = pin[(bo * 7 + 1) * N + ka]; q[2] = cos(po); q[3] = sin(po);
-        ++o;
-      }
-    }
-    __syncthreads();
-    CFZ_MARK(3);
-    int oi[2]; double od[3];
-    cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    cfz::solve_instance(sp, dv, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
-    __syncthreads();
-    CFZ_MARK(4);
-    // ---- read-back (the solution is still in the workspace) or shift fallback (:484-524), plant (:528-543) ------------
-    for (int i = tid; i < 7 * N; i += cfz::kNL) {
-      const int c = i / N, k = i - c * N;
-      const int ka = (k + 1 < N) ? k + 1 : N - 1;
-      pout[(size_t)b * 7 * N + i] = (oi[1] == 0) ? smem[L.p + k * cfz::kNP + c] : pin[((size_t)b * 7 + c) * N + ka];
-    }
-    CFZ_MARK(5);
-    if (tid == 0) {
-      const double a0 = (oi[1] == 0) ? smem[L.p + 5] : pin[((size_t)b * 7 + 5) * N + 1];
-      const double w0 = (oi[1] == 0) ? smem[L.p + 6] : pin[((size_t)b * 7 + 6) * N + 1];
-      double z[5], out[5];
-      for (int i = 0; i < 5; ++i) z[i] = smem[L.x0 + i];
-      cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
-      for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
-      status[b] = oi[1]; iters[b] = oi[0];
-      if (rec) {
-        double *r = rec + ((size_t)t * B + b) * 7;
-        for (int i = 0; i < 5; ++i) r[i] = out[i];
-        r[5] = a0; r[6] = w0;
-        rec_si[(size_t)t * 2 * B + b] = oi[1]; rec_si[(size_t)(t * 2 + 1) * B + b] = oi[0];
-      }
-      stats[b * 3] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
-      atomicAdd(iter_sum, oi[0]);
-      if (oi[1] == 0) atomicAdd(iter_sum + 1, 1);  // converged solves of this launch
-      atomicAdd(iter_sum + 2 + (oi[1] < 0 ? 0 : (oi[1] > 5 ? 5 : oi[1])), 1);  // ... and how every solve of it ended (status 0..5)
-    }
-    // release: prediction and state of (s, v, t).  Every storing wavefront drains its stores, the workgroup meets, one
-    // lane writes the XCD's L2 back and only then signals (the asm wait keeps the compiler from dropping the drain).
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    CFZ_MARK(6);
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int c = atomicAdd(&done[s], 1);
-      if ((c % V) == V - 1 && t + 1 < K) {  // last vehicle of the scenario: publish iteration t+1
-        const int pos = atomicAdd(&tail[t + 1], V);
-        for (int u = 0; u < V; ++u)
-          __hip_atomic_store(&slots[(size_t)(t + 1) * B + pos + u], s * V + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      atomicAdd(&ctrl[1], 1);
-    }
-    CFZ_MARK(8);
-  }
-  CFZ_MARK(9);
+  constexpr bool kSeq = false;
+  const int32_t *const xperm = nullptr, *const xrank = nullptr;
+#include "cfz_loop_body.inl"
+}
+
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(const KArgs *__restrict__ ka, int S, int V, int K, int T,
+                                                            const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
+                                                            int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
+                                                            int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
+                                                            double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
+                                                            double *rec, int32_t *rec_si, const int32_t *xperm, const int32_t *xrank) {
+  constexpr bool kSeq = true;
+#include "cfz_loop_body.inl"
 }
 
 // ---- dual warm starts: exact separation of two convex quadrilaterals and the duals that certify it ------------------
@@ -607,6 +506,10 @@ struct cfz_handle {
   int S = 0, T = 0, P = 0;
   double *ref_table = nullptr, *pred = nullptr, *state = nullptr;
   int32_t *kidx = nullptr, *order = nullptr, *table_of = nullptr;
+  // exchange order (cfz_loop_set_order; NULL: Jacobi): xperm[S][V] the order of every scenario, xrank[S][V] its inverse,
+  // xlist[V][S] the instance ids s * V + xperm[s][r] of round r (the dispatch list of a stepwise round)
+  int32_t *xperm = nullptr, *xrank = nullptr, *xlist = nullptr;
+  std::vector<int32_t> xperm_host;
   // record of the realised trajectory (cfz_loop_record): rec[rec_cap][S][V][7], rec_si[rec_cap][2][S][V]; rec_used steps written
   double *rec = nullptr;
   int32_t *rec_si = nullptr;
@@ -623,14 +526,15 @@ struct cfz_handle {
 namespace {
 
 
+// grid (0: B) workgroups solve the instances order[0 .. grid) of the B (order NULL: 0 .. B)
 int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, const double *nbr, double *zu,
                  int32_t *status, int32_t *iters, double *stats, bool duals, hipStream_t st,
-                 const int32_t *order = nullptr, int carry_all = 0) {
+                 const int32_t *order = nullptr, int carry_all = 0, int grid = 0) {
   DualPtrs du = {nullptr, nullptr, nullptr, nullptr, nullptr};
   if (duals) du = {h->l, h->m, h->lam_ij, h->lam_ji, h->s};
   if ((h->carry_set || h->slots_set) && st != h->stream) HIP_OK(hipStreamWaitEvent(st, h->ev_stage, 0));  // staged on the handle's stream
   HIP_OK(hipEventRecord(h->ev0, st));
-  hipLaunchKernelGGL(solve_kernel, dim3(B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
+  hipLaunchKernelGGL(solve_kernel, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
                      iters, stats, du, order, h->carry_duals ? h->wst : nullptr, h->wst_stride,
                      h->carry_ext ? h->carry_ext : (h->carry_set ? h->carry : nullptr), carry_all, h->slots_set ? h->slots : nullptr);
   h->carry_set = false; h->slots_set = false; h->carry_ext = nullptr;  // the flags of cfz_mpc_set_carry / cfz_mpc_set_slots hold for one solve
@@ -738,6 +642,8 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
     if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
     e = hipFuncSetAttribute((const void *)loop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
+    e = hipFuncSetAttribute((const void *)loop_kernel_seq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+    if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
   }
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->blocks_per_cu, (const void *)solve_kernel, cfz::kNL, h->lds_bytes);
   {
@@ -789,7 +695,8 @@ int cfz_destroy(cfz_handle *h) {
   hipSetDevice(h->device);
   void *bufs[] = {h->x0, h->ref, h->nbr, h->zu, h->stats, h->status, h->iters, h->l, h->m, h->lam_ij, h->lam_ji, h->s,
                   h->ref_table, h->pred, h->state, h->kidx, h->order, h->pred2, h->scratch, h->queue, h->ctrl, h->done,
-                  h->iter_sum, h->obs_tab, h->wst, h->carry, h->slots, h->kargs, h->table_of, h->rec, h->rec_si};
+                  h->iter_sum, h->obs_tab, h->wst, h->carry, h->slots, h->kargs, h->table_of, h->rec, h->rec_si,
+                  h->xperm, h->xrank, h->xlist};
   for (void *p : bufs) if (p) hipFree(p);
   arena_destroy(h->arena);
   if (h->stage_host) hipHostFree(h->stage_host);
@@ -1004,6 +911,12 @@ void record_free(cfz_handle *h) {
 }
 
 // room for `steps` more steps in the record (or no record at all)
+void exchange_free(cfz_handle *h) {
+  for (void *p : {(void *)h->xperm, (void *)h->xrank, (void *)h->xlist}) if (p) (void)hipFree(p);
+  h->xperm = h->xrank = h->xlist = nullptr;
+  h->xperm_host.clear();
+}
+
 int record_room(cfz_handle *h, int steps) {
   if (h->rec_cap && h->rec_used + steps > h->rec_cap) return fail("the step(s) would overflow the record (cfz_loop_record)");
   return 0;
@@ -1064,6 +977,7 @@ int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *table
   for (void *p : {(void *)h->ref_table, (void *)h->pred, (void *)h->state, (void *)h->kidx, (void *)h->order, (void *)h->table_of}) if (p) hipFree(p);
   h->ref_table = h->pred = h->state = nullptr; h->kidx = nullptr; h->order = nullptr; h->table_of = nullptr; h->have_order = false;
   record_free(h);  // a record belongs to one initialisation (its shape is that of S)
+  exchange_free(h);  // back to Jacobi
   h->S = S; h->T = T; h->P = P;
   const size_t B = (size_t)S * V;
   HIP_OK(hipMalloc(&h->ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->pred, B * 7 * N * 8));
@@ -1153,24 +1067,81 @@ int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const doub
   return audit_launch(h, K, S, V, dt_, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
 }
 
+int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
+  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (!order) { exchange_free(h); return 0; }
+  const int S = h->S, V = h->ks.n_nbr + 1;
+  std::vector<int32_t> rank((size_t)S * V), list((size_t)V * S);
+  for (int s = 0; s < S; ++s) {
+    std::vector<char> seen((size_t)V, 0);
+    for (int r = 0; r < V; ++r) {
+      const int32_t v = order[(size_t)s * V + r];
+      if (v < 0 || v >= V || seen[v]) return fail("order[s] is not a permutation of 0..V-1");
+      seen[v] = 1;
+      rank[(size_t)s * V + v] = r; list[(size_t)r * S + s] = s * V + v;
+    }
+  }
+  if (!h->xperm) {
+    HIP_OK(hipMalloc(&h->xperm, (size_t)S * V * 4)); HIP_OK(hipMalloc(&h->xrank, (size_t)S * V * 4));
+    HIP_OK(hipMalloc(&h->xlist, (size_t)S * V * 4));
+  }
+  HIP_OK(hipMemcpy(h->xperm, order, (size_t)S * V * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->xrank, rank.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->xlist, list.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
+  h->xperm_host.assign(order, order + (size_t)S * V);
+  return 0;
+}
+
 int cfz_loop_step(cfz_handle *h) {
   if (!h || !h->pred) return fail("cfz_loop_init has not been called");
   if (record_room(h, 1)) return -1;
   HIP_OK(hipSetDevice(h->device));
   const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->S, B = S * V;
+  double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
+  int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
+  if (h->xperm) {
+    // sequential exchange: V rounds; round r prepares, solves (S instances, dispatch list xlist[r], carry slot b as in Jacobi)
+    // and posts the vehicle of rank r of every scenario.  The solve time is the sum of the V launches; each round's events
+    // are read once the next round's preparation is queued behind them.
+    const long nt = (long)S * N;
+    float total_ms = 0.f;
+    for (int r = 0; r < V; ++r) {
+      if (r > 0) {
+        HIP_OK(hipEventSynchronize(h->ev1));
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1)); total_ms += ms;
+      }
+      hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
+                         h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, r, h->xperm, h->xrank);
+      HIP_OK(hipGetLastError());
+      if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, h->xlist + (size_t)r * S,
+                       1, S)) return -1;
+      hipLaunchKernelGGL(loop_post, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb,
+                         kPlantSubsteps, h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, r, h->xperm);
+      HIP_OK(hipGetLastError());
+    }
+    if (h->rec) h->rec_used += 1;
+    h->have_order = false;  // the LPT list is the Jacobi steps' own
+    HIP_OK(hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    h->last_ms = total_ms + ms;
+    h->ms_pending = false;
+    return 0;
+  }
   const long nt = (long)B * N;
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
-                     h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu);
+                     h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, 0, nullptr, nullptr);
   HIP_OK(hipGetLastError());
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream,
                    h->have_order ? h->order : nullptr, 1)) return -1;
   hipLaunchKernelGGL(order_by_iters, dim3(1), dim3(1024), 0, h->stream, B, h->iters, h->order);
   HIP_OK(hipGetLastError());
   h->have_order = true;
-  double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
-  int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
-                     h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si);
+                     h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, 0, nullptr);
   HIP_OK(hipGetLastError());
   if (h->rec) h->rec_used += 1;
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -1190,13 +1161,17 @@ int cfz_loop_run(cfz_handle *h, int K) {
   int ncu = 0;
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)loop_kernel, cfz::kNL, h->lds_bytes));
+  const bool seq = h->xperm != nullptr;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, seq ? (const void *)loop_kernel_seq : (const void *)loop_kernel, cfz::kNL,
+                                                      h->lds_bytes));
   per_cu = std::min(per_cu, h->blocks_per_cu);  // the 2 KiB LDS granules (cfz_create): what the hardware really keeps resident
   if (per_cu < 1) return fail("loop kernel does not fit on a CU");
   // one workgroup per resident slot: more would only queue behind them (any workgroup can serve any item, so a surplus
   // is harmless, just useless)
   if (const char *cap = std::getenv("CFZ_LOOP_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(cap)));  // experiments
-  const int grid = std::min(B, per_cu * ncu);
+  // the sequential exchange has at most S items in flight (one per scenario): workgroups beyond S would never win one and
+  // would end the launch through the idle give-up
+  const int grid = std::min(seq ? S : B, per_cu * ncu);
   const size_t per_block = 5 + 3 * (size_t)N + (size_t)h->ks.n_nbr * 3 * N + 7 * (size_t)N;
   if (!h->pred2) {
     HIP_OK(hipMalloc(&h->pred2, (size_t)2 * B * 7 * N * 8)); HIP_OK(hipMalloc(&h->ctrl, (4 + 1024) * 4));
@@ -1216,10 +1191,12 @@ int cfz_loop_run(cfz_handle *h, int K) {
   HIP_OK(hipMemsetAsync(h->queue, 0, 2 * (size_t)K * 4, h->stream));
   HIP_OK(hipMemsetAsync(h->queue + 2 * K, 0xff, total * 4, h->stream));
   {
-    std::vector<int32_t> first(B);
-    for (int b = 0; b < B; ++b) first[b] = b;
-    HIP_OK(hipMemcpyAsync(h->queue + 2 * K, first.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_OK(hipMemcpyAsync(h->queue + K, &B, 4, hipMemcpyHostToDevice, h->stream));  // tail[0] = B
+    // Jacobi: all B items; sequential: the S items (s, xperm[s][0])
+    const int n0 = seq ? S : B;
+    std::vector<int32_t> first(n0);
+    for (int i = 0; i < n0; ++i) first[i] = seq ? i * V + h->xperm_host[(size_t)i * V] : i;
+    HIP_OK(hipMemcpyAsync(h->queue + 2 * K, first.data(), (size_t)n0 * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(h->queue + K, &n0, 4, hipMemcpyHostToDevice, h->stream));  // tail[0]
     const int32_t ctrl0[4] = {0, 0, 0, 0};
     HIP_OK(hipMemcpyAsync(h->ctrl, ctrl0, sizeof ctrl0, hipMemcpyHostToDevice, h->stream));
     HIP_OK(hipMemsetAsync(h->done, 0, (size_t)S * 4, h->stream));
@@ -1229,10 +1206,16 @@ int cfz_loop_run(cfz_handle *h, int K) {
   HIP_OK(hipEventRecord(h->ev0, h->stream));
   double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
   int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
-  hipLaunchKernelGGL(loop_kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
-                     h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
-                     h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride,
-                     std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0, rec, rec_si);
+  const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
+  if (seq)
+    hipLaunchKernelGGL(loop_kernel_seq, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
+                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
+                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si,
+                       h->xperm, h->xrank);
+  else
+    hipLaunchKernelGGL(loop_kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
+                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
+                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si);
   HIP_OK(hipGetLastError());
   if (h->rec) h->rec_used += K;
   HIP_OK(hipEventRecord(h->ev1, h->stream));

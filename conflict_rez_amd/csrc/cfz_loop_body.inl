@@ -1,0 +1,151 @@
+// cfz_loop_body.inl -- the body of the persistent closed-loop kernels loop_kernel and loop_kernel_seq (cfz_engine.hip), included
+// inside both.  The including kernel defines `constexpr bool kSeq` and the exchange order arrays `xperm`, `xrank` (nullptr for
+// the Jacobi kernel); everything else is the kernel's arguments.
+  extern __shared__ double smem[];
+  const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
+  const int N = sp.N, nn = sp.n_nbr, B = S * V, tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double *my = scratch + (size_t)blockIdx.x * (5 + 3 * N + nn * 3 * N + 7 * N);
+  double *ref = my + 5;  // (the record keeps the layout x0 | ref | nbr | zu of the stepwise path; only ref is used here)
+  int32_t *head = qbuf, *tail = qbuf + K, *slots = qbuf + 2 * K;
+  // what wavefront 0 popped, for wavefront 1: {iteration t (-1: leave), instance b}.  Lives in the reduction exchange
+  // area of the workspace, which is idle between two solves.
+  volatile int32_t *cmd = reinterpret_cast<volatile int32_t *>(smem + L.xw);
+#define CFZ_LD(p) __builtin_amdgcn_readfirstlane(__hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+  int idle = 0;
+  while (true) {
+    if (wave == 0) {
+      // ---- pop (wavefront 0 only): lowest iteration first -----------------------------------------------
+      int t = -1, b = -1;
+      while (true) {
+        int t0 = CFZ_LD(&ctrl[0]);
+        const int hint = t0;
+        while (t0 < K && CFZ_LD(&head[t0]) >= B) ++t0;
+        if (t0 > hint && lane == 0) atomicMax(&ctrl[0], t0);
+        if (t0 >= K) break;  // every item of every iteration has been handed out
+        int idx = 0;
+        for (int tt = t0; tt < K; ++tt) {
+          const int hd = CFZ_LD(&head[tt]), tl = CFZ_LD(&tail[tt]);
+          if (tl == 0) break;  // no scenario has reached iteration tt yet, hence none is further either
+          if (hd >= tl) continue;
+          idx = __builtin_amdgcn_readfirstlane(atomicAdd(&head[tt], lane == 0 ? 1 : 0));
+          if (idx < B) { t = tt; break; }
+        }
+        if (t < 0) {  // nothing to hand out right now
+          __builtin_amdgcn_s_sleep(32);
+          if (++idle > (1 << 22) || CFZ_LD(&ctrl[2])) { if (lane == 0) atomicExch(&ctrl[2], 1); break; }
+          continue;
+        }
+        idle = 0;
+        for (int spins = 0; (b = CFZ_LD(&slots[(size_t)t * B + idx])) < 0; ++spins) {
+          __builtin_amdgcn_s_sleep(8);
+          if (spins > (1 << 23) || CFZ_LD(&ctrl[2])) break;
+        }
+        if (b < 0) { if (lane == 0) atomicExch(&ctrl[2], 1); t = -1; }
+        break;
+      }
+      CFZ_MARK(1);
+      // acquire: predictions / states written by other workgroups.  One agent-scope acquire by the polling wavefront
+      // (invalidates this CU's L1), completed before the barrier that releases the other wavefront's loads.
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) { cmd[0] = t; cmd[1] = b; }
+    }
+    __syncthreads();
+    const int t = cmd[0], b = cmd[1];
+    if (t < 0) break;
+    CFZ_MARK(2);
+    // The launch ends with its slowest scenario (a chain of K dependent iterations).  A workgroup serving the oldest open
+    // iteration is on that critical path: its two wavefronts take issue priority over the wavefronts they share their
+    // SIMDs with (VALU issue is arbitrated by priority, then age), the others give way.
+    if (prio_lag >= 0) {
+      if (t <= CFZ_LD(&ctrl[0]) + prio_lag) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
+    }
+    const int s = b / V, v = b - s * V;
+    const double *pin = pred + (size_t)(t & 1) * B * 7 * N;   // predictions after iteration t-1
+    double *pout = pred + (size_t)((t + 1) & 1) * B * 7 * N;
+    const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
+    const int rv = kSeq ? xrank[b] : 0;  // v's rank in its scenario's exchange order
+    // ---- parameters and shifted warm start (vehicle_follower.py:432-476), straight into the solver's workspace: measured
+    // state, neighbours' poses with cos / sin, warm start (solve_instance's `preloaded` form); only the reference goes through
+    // a global record (the solver reads it from there in every iteration)
+    if (tid < 5) smem[L.x0 + tid] = state[b * 5 + tid];
+    for (int k = tid; k < N; k += cfz::kNL) {
+      const int ka = (k + 1 < N) ? k + 1 : N - 1;
+      int kr = kidx0[s] + t_base + t + k; if (kr > T - 1) kr = T - 1;
+      for (int c = 0; c < 3; ++c) ref[c * N + k] = tab[((size_t)v * T + kr) * 7 + c];
+      for (int c = 0; c < 7; ++c) smem[L.p + k * cfz::kNP + c] = pin[((size_t)b * 7 + c) * N + ka];
+      int o = 0;
+      for (int u = 0; u < V; ++u) {
+        if (u == v) continue;
+        const size_t bo = (size_t)s * V + u;
+        double *q = smem + L.nb4 + (k * nn + o) * 4;
+        const bool cur = kSeq && xrank[bo] < rv;  // ranked before v: its prediction of this iteration, not advanced
+        const double *pu = cur ? pout : pin;
+        const int ku = cur ? k : ka;
+        const double po = pu[(bo * 7 + 2) * N + ku];
+        q[0] = pu[(bo * 7 + 0) * N + ku]; q[1] = pu[(bo * 7 + 1) * N + ku]; q[2] = cos(po); q[3] = sin(po);
+        ++o;
+      }
+    }
+    __syncthreads();
+    CFZ_MARK(3);
+    int oi[2]; double od[3];
+    cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    cfz::solve_instance(sp, dv, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
+    __syncthreads();
+    CFZ_MARK(4);
+    // ---- read-back (the solution is still in the workspace) or shift fallback (:484-524), plant (:528-543) ------------
+    for (int i = tid; i < 7 * N; i += cfz::kNL) {
+      const int c = i / N, k = i - c * N;
+      const int ka = (k + 1 < N) ? k + 1 : N - 1;
+      pout[(size_t)b * 7 * N + i] = (oi[1] == 0) ? smem[L.p + k * cfz::kNP + c] : pin[((size_t)b * 7 + c) * N + ka];
+    }
+    CFZ_MARK(5);
+    if (tid == 0) {
+      const double a0 = (oi[1] == 0) ? smem[L.p + 5] : pin[((size_t)b * 7 + 5) * N + 1];
+      const double w0 = (oi[1] == 0) ? smem[L.p + 6] : pin[((size_t)b * 7 + 6) * N + 1];
+      double z[5], out[5];
+      for (int i = 0; i < 5; ++i) z[i] = smem[L.x0 + i];
+      cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
+      for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
+      status[b] = oi[1]; iters[b] = oi[0];
+      if (rec) {
+        double *r = rec + ((size_t)t * B + b) * 7;
+        for (int i = 0; i < 5; ++i) r[i] = out[i];
+        r[5] = a0; r[6] = w0;
+        rec_si[(size_t)t * 2 * B + b] = oi[1]; rec_si[(size_t)(t * 2 + 1) * B + b] = oi[0];
+      }
+      stats[b * 3] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
+      atomicAdd(iter_sum, oi[0]);
+      if (oi[1] == 0) atomicAdd(iter_sum + 1, 1);  // converged solves of this launch
+      atomicAdd(iter_sum + 2 + (oi[1] < 0 ? 0 : (oi[1] > 5 ? 5 : oi[1])), 1);  // ... and how every solve of it ended (status 0..5)
+    }
+    // release: prediction and state of (s, v, t).  Every storing wavefront drains its stores, the workgroup meets, one
+    // lane writes the XCD's L2 back and only then signals (the asm wait keeps the compiler from dropping the drain).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    CFZ_MARK(6);
+    if (tid == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const int c = atomicAdd(&done[s], 1);
+      if (kSeq) {  // completions of a scenario are serialised: c % V is this item's rank; publish exactly one item
+        const int r = c % V;
+        const int tn = r < V - 1 ? t : t + 1;
+        if (tn < K) {
+          const int pos = atomicAdd(&tail[tn], 1);
+          __hip_atomic_store(&slots[(size_t)tn * B + pos], s * V + xperm[s * V + (r < V - 1 ? r + 1 : 0)], __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+        }
+      } else if ((c % V) == V - 1 && t + 1 < K) {  // last vehicle of the scenario: publish iteration t+1
+        const int pos = atomicAdd(&tail[t + 1], V);
+        for (int u = 0; u < V; ++u)
+          __hip_atomic_store(&slots[(size_t)(t + 1) * B + pos + u], s * V + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      atomicAdd(&ctrl[1], 1);
+    }
+    CFZ_MARK(8);
+  }
+  CFZ_MARK(9);
+#undef CFZ_LD

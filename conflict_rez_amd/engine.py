@@ -160,6 +160,7 @@ def load_library(path=None):
     lib.cfz_loop_last_converged.restype = C.c_long
     lib.cfz_loop_last_status_counts.argtypes = [vp, vp]
     lib.cfz_loop_get.argtypes = [vp, vp, vp, vp, vp]
+    lib.cfz_loop_set_order.argtypes = [vp, vp]
     lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.cfz_loop_record.argtypes = [vp, C.c_int]
     lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -172,7 +173,7 @@ def load_library(path=None):
 EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
-    "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit"
+    "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -569,13 +570,36 @@ class Engine:
         self._S, self._V = S, V
         self._rec_cap, self._rec_used = 0, 0
 
+    def loop_set_order(self, order):
+        """`cfz_loop_set_order`: the exchange rule of the closed loop's later steps and runs.  None: Jacobi (every vehicle plans
+        against the others' predictions of the previous iteration, advanced; the default, and what `loop_init` restores).  [V]
+        (one order for every scenario) or [S, V] integers (one per scenario): the vehicles of a scenario solve one after another
+        in that order, each against the predictions of those before it from the same iteration (not advanced) and the previous
+        iteration's predictions of the others, advanced."""
+        if order is None or not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+            self._ck(self.lib.cfz_loop_set_order(self._h, None), "cfz_loop_set_order")
+            return
+        S, V = self._S, self._V
+        o = np.asarray(order)
+        if o.dtype.kind not in "iu":
+            raise ValueError(f"order must hold integers, got dtype {o.dtype}")
+        if o.shape == (V,):
+            o = np.broadcast_to(o, (S, V))
+        if o.shape != (S, V):
+            raise ValueError(f"order must have shape ({V},) or ({S}, {V}), got {np.shape(order)}")
+        bad = np.flatnonzero((np.sort(o, axis=1) != np.arange(V)).any(axis=1))
+        if bad.size:
+            raise ValueError(f"order[{bad[0]}] = {o[bad[0]].tolist()} is not a permutation of 0..{V - 1}")
+        o = np.ascontiguousarray(o, dtype=np.int32)
+        self._ck(self.lib.cfz_loop_set_order(self._h, _ptr(o)), "cfz_loop_set_order")
+
     def loop_step(self):
         self._ck(self.lib.cfz_loop_step(self._h), "cfz_loop_step")
         if self._rec_cap:
             self._rec_used += 1
 
     def loop_run(self, K):
-        """K closed-loop iterations in one persistent launch (same results as K x loop_step)."""
+        """K closed-loop iterations in one persistent launch (same results as K x loop_step, under either exchange rule)."""
         self._ck(self.lib.cfz_loop_run(self._h, int(K)), "cfz_loop_run")
         if self._rec_cap:
             self._rec_used += int(K)

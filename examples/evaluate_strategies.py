@@ -5,10 +5,12 @@
 2. All their single-vehicle plans in one planning chain (`scenarios.plan_scenarios`: one state_ws launch, one collocation launch).
 3. M sampled starts per plan set (`scenarios.sample_scenarios` on that set's table).
 4. One persistent closed-loop launch over all plan sets x starts (`Engine.loop_init` with a pool of tables), recorded, then audited.
+   --exchange sequential: each scenario's vehicles solve one after another in its strategy's planning priority (the order of the
+   first (order, delays) combination that gives the strategy; `Engine.loop_set_order`) instead of the reference's Jacobi exchange.
 5. One row per strategy: plans converged, share of converged MPC solves, smallest vehicle / obstacle clearance, scenarios with
    contact, arrival step p50 / max.
 
-usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED]
+usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
 """
 import argparse
 import os
@@ -26,6 +28,8 @@ def main():
     ap.add_argument("--steps", type=int, default=150, help="closed-loop MPC iterations (dt = 0.1 s)")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--exchange", choices=("jacobi", "sequential"), default="jacobi",
+                    help="exchange rule of the closed loop: jacobi (the reference's) or sequential in each strategy's planning priority")
     a = ap.parse_args()
 
     import torch
@@ -58,6 +62,8 @@ def main():
     S = len(k0)
     eng = engine.Engine(spec, max_batch=S * V, device=a.device)
     eng.loop_init(plan["tables"], k0, noise, table_of=tof)
+    if a.exchange == "sequential":
+        eng.loop_set_order(np.array([combos[p][0][0] for p in tof], np.int32))
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -66,7 +72,8 @@ def main():
     aud = eng.loop_audit()
     sync(); t_audit = time.perf_counter() - t0
     hist = eng.loop_history()
-    print(f"closed loop: {S} scenarios x {V} vehicles x {K} steps in one launch, {t_loop:.2f} s; audit {t_audit * 1e3:.1f} ms")
+    print(f"closed loop: {S} scenarios x {V} vehicles x {K} steps in one launch, {t_loop:.2f} s; audit {t_audit * 1e3:.1f} ms"
+          + ("; sequential exchange in each strategy's planning priority" if a.exchange == "sequential" else ""))
 
     print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}")
     no_contact = []

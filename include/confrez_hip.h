@@ -157,7 +157,7 @@ int cfz_mpc_stats(cfz_handle *h, int B, int32_t *status, int32_t *iters, double 
                   double *min_sep);
 
 /* Milliseconds the last cfz_mpc_solve / cfz_loop_step spent in its solver kernel (HIP events
- * on the handle's stream). */
+ * on the handle's stream); after a sequential cfz_loop_step (cfz_loop_set_order) the sum of its V solve launches. */
 double cfz_last_solve_ms(const cfz_handle *h);
 
 /* ---- device-resident path ------------------------------------------------------------- */
@@ -371,14 +371,24 @@ int cfz_abi_version(void);
  * cfz_loop_init sets state = ref_table[v][k0][0:5] + noise[s][v][5] and the first prediction =
  * the plan at the horizon times (:397-400).
  * cfz_loop_step does one iteration for all scenarios, entirely on the device:
- *   neighbours' predictions copied first (get_others_pred :636-637, Jacobi), every vehicle's
+ *   neighbours' predictions copied first (get_others_pred :636-637), every vehicle's
  *   step(): parameters + shifted warm start (:432-476), solve (:479), read-back or shift
- *   fallback (:484-524), clock += dt (:526), plant integration over dt with (a0,w0) (:528-543). */
+ *   fallback (:484-524), clock += dt (:526), plant integration over dt with (a0,w0) (:528-543).
+ * Exchange rule (cfz_loop_set_order): with no order set (the default), Jacobi: every vehicle plans against the others'
+ * predictions of the previous iteration, advanced one step.  With an order, the V solves of scenario s run one after
+ * another in the order order[s]: the vehicle of rank r plans against the predictions of the vehicles ranked before it
+ * from this same iteration (after their solve or their shift fallback; they already start at this iteration's time, so
+ * they are not advanced) and the previous iteration's predictions of the others, advanced.  Measured state, reference,
+ * warm start (its own previous prediction, advanced), carried multipliers, read-back, fallback, plant and record are the
+ * same in both rules.  A converged solve then keeps dmin - constr_viol_tol from the prediction of every vehicle ranked
+ * before it at stages 1..N-1; the realised states after the plant are not bounded so (the stage-0 dynamics defect and the
+ * plant's finer integration separate them from the predictions): cfz_loop_audit measures them. */
 int cfz_loop_init(cfz_handle *h, int S, int T, const double *ref_table, const int32_t *k0, const double *noise);
 int cfz_loop_step(cfz_handle *h);
-/* K iterations for all scenarios in one persistent launch: the V solves of a scenario still exchange predictions
- * after every iteration (Jacobi), but scenarios no longer wait for each other between iterations.  Same results
- * as K calls of cfz_loop_step.  cfz_loop_last_iterations: IPM iterations summed over all solves of that call. */
+/* K iterations for all scenarios in one persistent launch: the V solves of a scenario exchange predictions by the rule
+ * above (Jacobi, or in the order of cfz_loop_set_order), but scenarios no longer wait for each other between iterations.
+ * Same results, bit for bit, as K calls of cfz_loop_step under the same rule.  cfz_loop_last_iterations: IPM iterations
+ * summed over all solves of that call. */
 int cfz_loop_run(cfz_handle *h, int K);
 long cfz_loop_last_iterations(const cfz_handle *h);
 /* solves of that call that converged (status 0); the others took the reference's shift fallback (:501-524) */
@@ -388,6 +398,14 @@ long cfz_loop_last_converged(const cfz_handle *h);
 int cfz_loop_last_status_counts(const cfz_handle *h, long counts[6]);
 /* state[S][V][5], pred[S][V][7][N], status int32[S][V] of the last step; NULL to skip. */
 int cfz_loop_get(cfz_handle *h, double *state, double *pred, int32_t *status, int32_t *iters);
+/* Exchange order of the closed loop (cfz_loop_step, cfz_loop_run).  order[S][V]: row s is the order in which the V vehicles
+ * of scenario s solve within one MPC iteration; a vehicle sees the predictions of those before it from the same iteration and
+ * those of the others from the previous one, advanced one step.  NULL: Jacobi, every vehicle sees the previous iteration's
+ * predictions (the reference, vehicle_follower.py:636-641).  cfz_loop_init / cfz_loop_init_tables reset it to NULL.
+ * The order holds for every later step and run until it is changed; it may change between calls (at a step boundary all
+ * predictions start at the same time).  Refused: a call before cfz_loop_init, a row that is not a permutation of 0..V-1
+ * (the order in force stays). */
+int cfz_loop_set_order(cfz_handle *h, const int32_t *order);
 
 /* ---- closed loop over per-scenario plans -------------------------------------------------------
  * tables[P][V][T][7]: a pool of P plan sets (each what cfz_loop_init takes as ref_table); scenario s follows set table_of[s]
