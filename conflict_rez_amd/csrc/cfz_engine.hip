@@ -8,6 +8,7 @@
 //   loop_kernel    the persistent closed loop (cfz_loop_run): the same solver body fed from per-iteration ticket queues of
 //                  (scenario, vehicle, iteration) work items, hand-offs between workgroups at agent scope
 //   loop_kernel_seq  the same with the sequential exchange of cfz_loop_set_order (one body: cfz_loop_body.inl)
+//   loop_kernel_dist, loop_kernel_seq_dist  the same two with the disturbances of cfz_loop_set_disturbance (cfz_disturb.inl)
 //   loop_prep      closed loop: parameters and shifted warm start of every vehicle from the
 //                  previous predictions (reference vehicle_follower.py:432-476, 636-637)
 //   loop_post      closed loop: read-back or shift fallback, plant integration, clock
@@ -33,6 +34,7 @@
 #include "../../include/confrez_hip.h"
 #include "cfz_solver.inl"
 #include "cfz_audit.inl"
+#include "cfz_disturb.inl"
 #include "cfz_common.h"
 
 thread_local std::string cfz_g_err;  // cfz_last_error(); shared with cfz_planning.hip (cfz_common.h)
@@ -91,9 +93,10 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
 // (instance, stage) of all B instances.  Otherwise round r of a sequential step: one thread per (scenario, stage), for the vehicle
 // v = xperm[s][r]; the neighbours ranked before it have already posted this step's prediction to `pred`, which starts at this
 // step's time and is read as it stands; the others' (and v's own warm start) are the previous step's, advanced.
+// dz (cfz_loop_set_disturbance; dz.sigma NULL: none): the solver's x0 is the measurement, state + d[0:5] of this `step`.
 __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, const int32_t *table_of, const int32_t *kidx,
                           const double *pred, const double *state, double *x0, double *ref, double *nbr,
-                          double *zu, int r, const int32_t *xperm, const int32_t *xrank) {
+                          double *zu, int r, const int32_t *xperm, const int32_t *xrank, cfz::DisturbArgs dz, int step) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= (long)(xperm ? S : S * V) * N) return;
   const int k = (int)(tid % N);
@@ -101,7 +104,7 @@ __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, c
   if (xperm) b = b * V + xperm[b * V + r];
   const int s = b / V, v = b - s * V;
   const int ka = (k + 1 < N) ? k + 1 : N - 1;  // _adv_onestep (:413-426)
-  if (k < 5) x0[b * 5 + k] = state[b * 5 + k];
+  if (k < 5) x0[b * 5 + k] = dz.sigma ? cfz::disturb_add(state[b * 5 + k], cfz::disturb_value(dz, s, v, step, k)) : state[b * 5 + k];
   int kr = kidx[s] + k; if (kr > T - 1) kr = T - 1;
   const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
   for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = tab[((size_t)v * T + kr) * 7 + c];
@@ -125,9 +128,12 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
 // this step's slice [S][V][7] of the record: state after the plant and the applied (a, w); rec_si its [2][S][V] status, iters.
 // xperm NULL: all B instances.  Otherwise round r of a sequential step (loop_prep): one thread per scenario, for its vehicle of
 // rank r; the clock advances with the last round, after every vehicle has read its reference.
+// dz (dz.sigma NULL: none): the applied input is the prediction's first plus d[5:7], clipped to the input box [a_lo, a_hi] x
+// [w_lo, w_hi]; the plant starts from the true state and d[7:12] is added to what it returns; the record keeps both.
 __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
                           const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
-                          int32_t *rec_si, int r, const int32_t *xperm) {
+                          int32_t *rec_si, int r, const int32_t *xperm, cfz::DisturbArgs dz, int step, double a_lo, double a_hi,
+                          double w_lo, double w_hi) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (xperm ? S : S * V)) return;
   if (xperm) b = b * V + xperm[b * V + r];
@@ -140,13 +146,21 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
   }
   double z[5], out[5];
   for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
-  cfz::rk4_step<false>(z, pb[5 * N], pb[6 * N], dt, wb, plant_substeps, out, nullptr);
+  double a0 = pb[5 * N], w0 = pb[6 * N];
+  const int s = b / V, v = b - s * V;
+  if (dz.sigma) {
+    a0 = cfz::disturb_clip(cfz::disturb_add(a0, cfz::disturb_value(dz, s, v, step, 5)), a_lo, a_hi);
+    w0 = cfz::disturb_clip(cfz::disturb_add(w0, cfz::disturb_value(dz, s, v, step, 6)), w_lo, w_hi);
+  }
+  cfz::rk4_step<false>(z, a0, w0, dt, wb, plant_substeps, out, nullptr);
+  if (dz.sigma)
+    for (int i = 0; i < 5; ++i) out[i] = cfz::disturb_add(out[i], cfz::disturb_value(dz, s, v, step, 7 + i));
   for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
   if (xperm ? r == V - 1 : b % V == 0) kidx[b / V] += 1;
   if (rec) {
     double *r = rec + (size_t)b * 7;
     for (int i = 0; i < 5; ++i) r[i] = out[i];
-    r[5] = pb[5 * N]; r[6] = pb[6 * N];
+    r[5] = a0; r[6] = w0;
     rec_si[b] = status[b]; rec_si[S * V + b] = iters[b];
   }
 }
@@ -257,8 +271,10 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(cons
                                                         int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
                                                         double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
                                                         double *rec, int32_t *rec_si) {
-  constexpr bool kSeq = false;
+  constexpr bool kSeq = false, kDist = false;
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
+  const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
+  const int step0 = 0;
 #include "cfz_loop_body.inl"
 }
 
@@ -268,8 +284,45 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(
                                                             int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
                                                             double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
                                                             double *rec, int32_t *rec_si, const int32_t *xperm, const int32_t *xrank) {
-  constexpr bool kSeq = true;
+  constexpr bool kSeq = true, kDist = false;
+  const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
+  const int step0 = 0;
 #include "cfz_loop_body.inl"
+}
+
+// The two kernels above with the disturbances of cfz_loop_set_disturbance (kDist): dz is the setting, step0 the MPC iterations done
+// since cfz_loop_init* (iteration t of this launch is step step0 + t of the streams).  Kernels of their own, made as loop_kernel_seq
+// was, so that the two undisturbed kernels keep the code they had before disturbances existed.
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_dist(const KArgs *__restrict__ ka, int S, int V, int K, int T,
+                                                             const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
+                                                             int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
+                                                             int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
+                                                             double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
+                                                             double *rec, int32_t *rec_si, cfz::DisturbArgs dz, int step0) {
+  constexpr bool kSeq = false, kDist = true;
+  const int32_t *const xperm = nullptr, *const xrank = nullptr;
+#include "cfz_loop_body.inl"
+}
+
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_dist(const KArgs *__restrict__ ka, int S, int V, int K, int T,
+                                                                 const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
+                                                                 int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
+                                                                 int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
+                                                                 double *stats, int32_t *iter_sum, double *wst, int wst_stride,
+                                                                 int prio_lag, double *rec, int32_t *rec_si, const int32_t *xperm,
+                                                                 const int32_t *xrank, cfz::DisturbArgs dz, int step0) {
+  constexpr bool kSeq = true, kDist = true;
+#include "cfz_loop_body.inl"
+}
+
+// d[K][S][V][12]: the disturbances of steps [t0, t0 + K) (cfz_loop_disturbance), one thread each, through the function the loop uses
+__global__ void disturb_fill(cfz::DisturbArgs dz, int S, int V, int t0, long n, double *d) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int c = (int)(i % cfz::kDisturbN);
+  const long b = i / cfz::kDisturbN;
+  const int v = (int)(b % V), s = (int)((b / V) % S), k = (int)(b / ((long)V * S));
+  d[i] = cfz::disturb_value(dz, s, v, t0 + k, c);
 }
 
 // ---- dual warm starts: exact separation of two convex quadrilaterals and the duals that certify it ------------------
@@ -515,6 +568,11 @@ struct cfz_handle {
   int32_t *rec_si = nullptr;
   int rec_cap = 0, rec_used = 0;
   bool have_order = false;
+  // disturbances (cfz_loop_set_disturbance; dz_on false: none): one device buffer dz_buf = sigma[12] | level[S] | stream[S] (uint32);
+  // steps_done below is the step count of the streams
+  void *dz_buf = nullptr;
+  uint64_t dz_seed = 0;
+  bool dz_on = false;
   // persistent loop
   double *pred2 = nullptr, *scratch = nullptr;
   int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
@@ -643,6 +701,8 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
     e = hipFuncSetAttribute((const void *)loop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
     e = hipFuncSetAttribute((const void *)loop_kernel_seq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)loop_kernel_dist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)loop_kernel_seq_dist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
     if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
   }
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->blocks_per_cu, (const void *)solve_kernel, cfz::kNL, h->lds_bytes);
@@ -696,7 +756,7 @@ int cfz_destroy(cfz_handle *h) {
   void *bufs[] = {h->x0, h->ref, h->nbr, h->zu, h->stats, h->status, h->iters, h->l, h->m, h->lam_ij, h->lam_ji, h->s,
                   h->ref_table, h->pred, h->state, h->kidx, h->order, h->pred2, h->scratch, h->queue, h->ctrl, h->done,
                   h->iter_sum, h->obs_tab, h->wst, h->carry, h->slots, h->kargs, h->table_of, h->rec, h->rec_si,
-                  h->xperm, h->xrank, h->xlist};
+                  h->xperm, h->xrank, h->xlist, h->dz_buf};
   for (void *p : bufs) if (p) hipFree(p);
   arena_destroy(h->arena);
   if (h->stage_host) hipHostFree(h->stage_host);
@@ -917,6 +977,18 @@ void exchange_free(cfz_handle *h) {
   h->xperm_host.clear();
 }
 
+void disturb_free(cfz_handle *h) {
+  if (h->dz_buf) (void)hipFree(h->dz_buf);
+  h->dz_buf = nullptr; h->dz_on = false; h->dz_seed = 0;
+}
+
+// the setting in force as the kernels take it (sigma NULL: none)
+cfz::DisturbArgs disturb_args(const cfz_handle *h) {
+  if (!h->dz_on) return {0, nullptr, nullptr, nullptr};
+  const double *f = static_cast<const double *>(h->dz_buf);
+  return {h->dz_seed, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->S)};
+}
+
 int record_room(cfz_handle *h, int steps) {
   if (h->rec_cap && h->rec_used + steps > h->rec_cap) return fail("the step(s) would overflow the record (cfz_loop_record)");
   return 0;
@@ -978,6 +1050,7 @@ int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *table
   h->ref_table = h->pred = h->state = nullptr; h->kidx = nullptr; h->order = nullptr; h->table_of = nullptr; h->have_order = false;
   record_free(h);  // a record belongs to one initialisation (its shape is that of S)
   exchange_free(h);  // back to Jacobi
+  disturb_free(h);   // back to the undisturbed loop; the step count restarts below
   h->S = S; h->T = T; h->P = P;
   const size_t B = (size_t)S * V;
   HIP_OK(hipMalloc(&h->ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->pred, B * 7 * N * 8));
@@ -1094,6 +1167,49 @@ int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
   return 0;
 }
 
+int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_meas[5], const double sigma_act[2],
+                             const double sigma_proc[5], const double *level, const uint32_t *stream) {
+  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (!sigma_meas && !sigma_act && !sigma_proc) { h->dz_on = false; return 0; }  // off: the plain kernels
+  const int S = h->S;
+  std::vector<double> f((size_t)cfz::kDisturbN + S, 0.0);
+  for (int i = 0; i < 5; ++i) { if (sigma_meas) f[i] = sigma_meas[i]; if (sigma_proc) f[7 + i] = sigma_proc[i]; }
+  for (int i = 0; i < 2; ++i) if (sigma_act) f[5 + i] = sigma_act[i];
+  for (int i = 0; i < cfz::kDisturbN; ++i)
+    if (!(f[i] >= 0.0) || !std::isfinite(f[i])) return fail("a sigma is negative or not finite");
+  for (int s = 0; s < S; ++s) {
+    f[cfz::kDisturbN + s] = level ? level[s] : 1.0;
+    if (!(f[cfz::kDisturbN + s] >= 0.0) || !std::isfinite(f[cfz::kDisturbN + s])) return fail("a level is negative or not finite");
+  }
+  std::vector<uint32_t> id((size_t)S);
+  for (int s = 0; s < S; ++s) id[s] = stream ? stream[s] : (uint32_t)s;
+  if (!h->dz_buf) HIP_OK(hipMalloc(&h->dz_buf, f.size() * 8 + id.size() * 4));
+  HIP_OK(hipMemcpy(h->dz_buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(static_cast<char *>(h->dz_buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  h->dz_seed = seed; h->dz_on = true;
+  return 0;
+}
+
+int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d) {
+  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h->dz_on) return fail("no disturbance is set (cfz_loop_set_disturbance)");
+  if (t0 < 0 || K < 1 || !d) return fail("t0 must not be negative, K must be positive and d not NULL");
+  HIP_OK(hipSetDevice(h->device));
+  const int S = h->S, V = h->ks.n_nbr + 1;
+  const size_t n = (size_t)K * S * V * cfz::kDisturbN;
+  if (n > ((size_t)1 << 31)) return fail("window too large");
+  if (arena_reset(h->arena)) return -1;
+  double *dd = nullptr;
+  ARENA_ALLOC(h->arena, dd, n * 8);
+  hipLaunchKernelGGL(disturb_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, disturb_args(h), S, V, t0, (long)n, dd);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(d, dd, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int cfz_loop_step(cfz_handle *h) {
   if (!h || !h->pred) return fail("cfz_loop_init has not been called");
   if (record_room(h, 1)) return -1;
@@ -1101,6 +1217,8 @@ int cfz_loop_step(cfz_handle *h) {
   const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->S, B = S * V;
   double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
   int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
+  const cfz::DisturbArgs dz = disturb_args(h);
+  const double *bd = h->ks.bounds;  // (the input box: a in [bd[8], bd[9]], w in [bd[10], bd[11]])
   if (h->xperm) {
     // sequential exchange: V rounds; round r prepares, solves (S instances, dispatch list xlist[r], carry slot b as in Jacobi)
     // and posts the vehicle of rank r of every scenario.  The solve time is the sum of the V launches; each round's events
@@ -1114,15 +1232,17 @@ int cfz_loop_step(cfz_handle *h) {
         HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1)); total_ms += ms;
       }
       hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
-                         h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, r, h->xperm, h->xrank);
+                         h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, r, h->xperm, h->xrank, dz, h->steps_done);
       HIP_OK(hipGetLastError());
       if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, h->xlist + (size_t)r * S,
                        1, S)) return -1;
       hipLaunchKernelGGL(loop_post, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb,
-                         kPlantSubsteps, h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, r, h->xperm);
+                         kPlantSubsteps, h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, r, h->xperm, dz, h->steps_done,
+                         bd[8], bd[9], bd[10], bd[11]);
       HIP_OK(hipGetLastError());
     }
     if (h->rec) h->rec_used += 1;
+    h->steps_done += 1;
     h->have_order = false;  // the LPT list is the Jacobi steps' own
     HIP_OK(hipStreamSynchronize(h->stream));
     float ms = 0.f;
@@ -1133,7 +1253,7 @@ int cfz_loop_step(cfz_handle *h) {
   }
   const long nt = (long)B * N;
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
-                     h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, 0, nullptr, nullptr);
+                     h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, 0, nullptr, nullptr, dz, h->steps_done);
   HIP_OK(hipGetLastError());
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream,
                    h->have_order ? h->order : nullptr, 1)) return -1;
@@ -1141,9 +1261,11 @@ int cfz_loop_step(cfz_handle *h) {
   HIP_OK(hipGetLastError());
   h->have_order = true;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
-                     h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, 0, nullptr);
+                     h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, 0, nullptr, dz, h->steps_done, bd[8], bd[9], bd[10],
+                     bd[11]);
   HIP_OK(hipGetLastError());
   if (h->rec) h->rec_used += 1;
+  h->steps_done += 1;
   HIP_OK(hipStreamSynchronize(h->stream));
   HIP_OK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
   h->ms_pending = false;
@@ -1161,9 +1283,10 @@ int cfz_loop_run(cfz_handle *h, int K) {
   int ncu = 0;
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
-  const bool seq = h->xperm != nullptr;
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, seq ? (const void *)loop_kernel_seq : (const void *)loop_kernel, cfz::kNL,
-                                                      h->lds_bytes));
+  const bool seq = h->xperm != nullptr, dist = h->dz_on;
+  const void *kern = dist ? (seq ? (const void *)loop_kernel_seq_dist : (const void *)loop_kernel_dist)
+                          : (seq ? (const void *)loop_kernel_seq : (const void *)loop_kernel);
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, cfz::kNL, h->lds_bytes));
   per_cu = std::min(per_cu, h->blocks_per_cu);  // the 2 KiB LDS granules (cfz_create): what the hardware really keeps resident
   if (per_cu < 1) return fail("loop kernel does not fit on a CU");
   // one workgroup per resident slot: more would only queue behind them (any workgroup can serve any item, so a surplus
@@ -1207,7 +1330,18 @@ int cfz_loop_run(cfz_handle *h, int K) {
   double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
   int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
   const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
-  if (seq)
+  const cfz::DisturbArgs dz = disturb_args(h);
+  if (dist && seq)
+    hipLaunchKernelGGL(loop_kernel_seq_dist, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
+                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
+                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si,
+                       h->xperm, h->xrank, dz, h->steps_done);
+  else if (dist)
+    hipLaunchKernelGGL(loop_kernel_dist, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
+                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
+                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, dz,
+                       h->steps_done);
+  else if (seq)
     hipLaunchKernelGGL(loop_kernel_seq, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
                        h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
                        h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si,
@@ -1218,6 +1352,7 @@ int cfz_loop_run(cfz_handle *h, int K) {
                        h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si);
   HIP_OK(hipGetLastError());
   if (h->rec) h->rec_used += K;
+  h->steps_done += K;
   HIP_OK(hipEventRecord(h->ev1, h->stream));
   // predictions after K iterations live in parity K%2; advance the scenario clocks by K
   HIP_OK(hipMemcpyAsync(h->pred, h->pred2 + (size_t)(K & 1) * B * 7 * N, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));

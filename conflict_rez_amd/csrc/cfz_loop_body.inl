@@ -1,12 +1,14 @@
-// cfz_loop_body.inl -- the body of the persistent closed-loop kernels loop_kernel and loop_kernel_seq (cfz_engine.hip), included
-// inside both.  The including kernel defines `constexpr bool kSeq` and the exchange order arrays `xperm`, `xrank` (nullptr for
-// the Jacobi kernel); everything else is the kernel's arguments.
+// cfz_loop_body.inl -- the body of the persistent closed-loop kernels loop_kernel, loop_kernel_seq and their disturbed variants
+// loop_kernel_dist, loop_kernel_seq_dist (cfz_engine.hip), included inside all four.  The including kernel defines `constexpr bool
+// kSeq` and the exchange order arrays `xperm`, `xrank` (nullptr for the Jacobi kernels), `constexpr bool kDist` and the disturbance
+// setting `dz` with the step count `step0` (unused constants in the undisturbed kernels); everything else is the kernel's arguments.
   extern __shared__ double smem[];
   const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
   const int N = sp.N, nn = sp.n_nbr, B = S * V, tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   double *my = scratch + (size_t)blockIdx.x * (5 + 3 * N + nn * 3 * N + 7 * N);
   double *ref = my + 5;  // (the record keeps the layout x0 | ref | nbr | zu of the stepwise path; only ref is used here)
+  double *dn = ref + 3 * N;  // kDist: d[5:12] of the item in hand, kept from the parameter phase to the plant in the idle nbr | zu slots
   int32_t *head = qbuf, *tail = qbuf + K, *slots = qbuf + 2 * K;
   // what wavefront 0 popped, for wavefront 1: {iteration t (-1: leave), instance b}.  Lives in the reduction exchange
   // area of the workspace, which is idle between two solves.
@@ -69,7 +71,14 @@
     // ---- parameters and shifted warm start (vehicle_follower.py:432-476), straight into the solver's workspace: measured
     // state, neighbours' poses with cos / sin, warm start (solve_instance's `preloaded` form); only the reference goes through
     // a global record (the solver reads it from there in every iteration)
-    if (tid < 5) smem[L.x0 + tid] = state[b * 5 + tid];
+    if (!kDist) {
+      if (tid < 5) smem[L.x0 + tid] = state[b * 5 + tid];
+    } else if (tid < cfz::kDisturbN) {
+      // twelve lanes, one Philox call each: the measurement state + d[0:5] is what the solver is pinned to; d[5:12] wait for the plant
+      const double d = cfz::disturb_value(dz, s, v, step0 + t, tid);
+      if (tid < 5) smem[L.x0 + tid] = cfz::disturb_add(state[b * 5 + tid], d);
+      else dn[tid - 5] = d;
+    }
     for (int k = tid; k < N; k += cfz::kNL) {
       const int ka = (k + 1 < N) ? k + 1 : N - 1;
       int kr = kidx0[s] + t_base + t + k; if (kr > T - 1) kr = T - 1;
@@ -103,11 +112,19 @@
     }
     CFZ_MARK(5);
     if (tid == 0) {
-      const double a0 = (oi[1] == 0) ? smem[L.p + 5] : pin[((size_t)b * 7 + 5) * N + 1];
-      const double w0 = (oi[1] == 0) ? smem[L.p + 6] : pin[((size_t)b * 7 + 6) * N + 1];
+      double a0 = (oi[1] == 0) ? smem[L.p + 5] : pin[((size_t)b * 7 + 5) * N + 1];
+      double w0 = (oi[1] == 0) ? smem[L.p + 6] : pin[((size_t)b * 7 + 6) * N + 1];
       double z[5], out[5];
-      for (int i = 0; i < 5; ++i) z[i] = smem[L.x0 + i];
+      if (!kDist) {
+        for (int i = 0; i < 5; ++i) z[i] = smem[L.x0 + i];
+      } else {  // the plant starts from the true state (x0 holds the measurement) with the disturbed, clipped input
+        for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
+        a0 = cfz::disturb_clip(cfz::disturb_add(a0, dn[0]), sp.bounds[8], sp.bounds[9]);
+        w0 = cfz::disturb_clip(cfz::disturb_add(w0, dn[1]), sp.bounds[10], sp.bounds[11]);
+      }
       cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
+      if (kDist)
+        for (int i = 0; i < 5; ++i) out[i] = cfz::disturb_add(out[i], dn[2 + i]);
       for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
       status[b] = oi[1]; iters[b] = oi[0];
       if (rec) {

@@ -161,6 +161,9 @@ def load_library(path=None):
     lib.cfz_loop_last_status_counts.argtypes = [vp, vp]
     lib.cfz_loop_get.argtypes = [vp, vp, vp, vp, vp]
     lib.cfz_loop_set_order.argtypes = [vp, vp]
+    if hasattr(lib, "cfz_loop_set_disturbance"):  # (tools/gpu_lib_compare.py loads the build before this export through `path`)
+        lib.cfz_loop_set_disturbance.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
+        lib.cfz_loop_disturbance.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.cfz_loop_record.argtypes = [vp, C.c_int]
     lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -173,7 +176,8 @@ def load_library(path=None):
 EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
-    "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order"
+    "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
+    "cfz_loop_set_disturbance cfz_loop_disturbance"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -592,6 +596,42 @@ class Engine:
             raise ValueError(f"order[{bad[0]}] = {o[bad[0]].tolist()} is not a permutation of 0..{V - 1}")
         o = np.ascontiguousarray(o, dtype=np.int32)
         self._ck(self.lib.cfz_loop_set_order(self._h, _ptr(o)), "cfz_loop_set_order")
+
+    def loop_set_disturbance(self, seed, meas=None, act=None, proc=None, level=None, stream=None):
+        """`cfz_loop_set_disturbance`: noise on the later steps and runs of the closed loop, drawn on the device from counter-based
+        streams (Philox4x32-10 keyed by `seed`; include/confrez_hip.h).  Standard deviations meas [5] of the measurement (x, y, psi, v,
+        delta) the solver is pinned to, act [2] of the applied input (a, w; clipped to the input box afterwards), proc [5] of the state
+        after the plant; None: zeros, all three None: off (what `loop_init` restores).  level [S] scales the three groups per scenario
+        (None: 1), stream [S] is each scenario's stream id (None: s): scenarios with equal ids draw the same noise."""
+        S = getattr(self, "_S", 0)
+
+        def group(a, n, name):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (n,):
+                raise ValueError(f"{name} must have shape ({n},), got {a.shape}")
+            return a
+
+        meas, act, proc = group(meas, 5, "meas"), group(act, 2, "act"), group(proc, 5, "proc")
+        if not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+            level = stream = None
+        level = group(level, S, "level")
+        if stream is not None:
+            st = np.asarray(stream)
+            if st.dtype.kind not in "iu" or st.shape != (S,) or (st < 0).any() or (st > 0xFFFFFFFF).any():
+                raise ValueError(f"stream must hold {S} integers in [0, 2^32)")
+            stream = np.ascontiguousarray(st, dtype=np.uint32)
+        self._ck(self.lib.cfz_loop_set_disturbance(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(meas), _ptr(act), _ptr(proc),
+                                                   _ptr(level), _ptr(stream)), "cfz_loop_set_disturbance")
+
+    def loop_disturbance(self, t0=0, K=1):
+        """`cfz_loop_disturbance`: d [K,S,V,12] that the loop adds at steps [t0, t0 + K) under the setting in force (0:5 measurement,
+        5:7 input, 7:12 process); steps count from `loop_init`."""
+        S, V = getattr(self, "_S", 1), getattr(self, "_V", self.spec.n_nbr + 1)
+        d = np.empty((max(int(K), 0), S, V, 12))
+        self._ck(self.lib.cfz_loop_disturbance(self._h, int(t0), int(K), _ptr(d)), "cfz_loop_disturbance")
+        return d
 
     def loop_step(self):
         self._ck(self.lib.cfz_loop_step(self._h), "cfz_loop_step")

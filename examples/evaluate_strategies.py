@@ -9,8 +9,12 @@
    first (order, delays) combination that gives the strategy; `Engine.loop_set_order`) instead of the reference's Jacobi exchange.
 5. One row per strategy: plans converged, share of converged MPC solves, smallest vehicle / obstacle clearance, scenarios with
    contact, arrival step p50 / max.
+   --noise-levels 0,0.5,1,2: every (strategy, start) runs once per level in the same launch, disturbed by level x NOISE_SIGMA
+   (`Engine.loop_set_disturbance`: measurement, actuator and process noise drawn on the device); the replicas of a start share one
+   stream id, so the levels are compared on common random numbers.  The table gains the share of scenarios with contact per level.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
+                                              [--noise-levels L0,L1,...] [--noise-seed SEED]
 """
 import argparse
 import os
@@ -21,6 +25,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np  # noqa: E402
 
+# standard deviations at noise level 1: measurement and process noise on (x, y, psi, v, delta), actuator noise on (a, w)
+NOISE_SIGMA = dict(meas=(0.02, 0.02, 0.005, 0.02, 0.0), act=(0.05, 0.02), proc=(0.005, 0.005, 0.002, 0.01, 0.0))
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
@@ -30,6 +37,9 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--exchange", choices=("jacobi", "sequential"), default="jacobi",
                     help="exchange rule of the closed loop: jacobi (the reference's) or sequential in each strategy's planning priority")
+    ap.add_argument("--noise-levels", type=lambda t: [float(x) for x in t.split(",")], default=None,
+                    help="comma-separated scales of NOISE_SIGMA, e.g. 0,0.5,1,2: one replica of every start per level, in one launch")
+    ap.add_argument("--noise-seed", type=int, default=2024, help="seed of the disturbance streams")
     a = ap.parse_args()
 
     import torch
@@ -59,9 +69,20 @@ def main():
         k0, nz = scenarios.sample_scenarios(M, plan["tables"][p], seed=a.seed + int(p), spec=spec)
         k0s.append(k0); noises.append(nz); tof.append(np.full(M, p, np.int32))
     k0, noise, tof = np.concatenate(k0s), np.concatenate(noises), np.concatenate(tof)
+    levels = a.noise_levels
+    lvl = None
+    if levels:
+        # replicas: block l of the batch is every (strategy, start) at level l, on the stream of its start
+        S0, L = len(k0), len(levels)
+        k0, noise, tof = np.tile(k0, L), np.tile(noise, (L, 1, 1)), np.tile(tof, L)
+        lvl, streams = np.repeat(np.asarray(levels, float), S0), np.tile(np.arange(S0, dtype=np.uint32), L)
+        print(f"noise levels {levels} x sigma: meas {NOISE_SIGMA['meas']}, act {NOISE_SIGMA['act']}, proc {NOISE_SIGMA['proc']}; "
+              f"noise seed {a.noise_seed}, one stream per start shared by its {L} replicas")
     S = len(k0)
     eng = engine.Engine(spec, max_batch=S * V, device=a.device)
     eng.loop_init(plan["tables"], k0, noise, table_of=tof)
+    if levels:
+        eng.loop_set_disturbance(a.noise_seed, level=lvl, stream=streams, **NOISE_SIGMA)
     if a.exchange == "sequential":
         eng.loop_set_order(np.array([combos[p][0][0] for p in tof], np.int32))
     eng.loop_record(K)
@@ -75,7 +96,8 @@ def main():
     print(f"closed loop: {S} scenarios x {V} vehicles x {K} steps in one launch, {t_loop:.2f} s; audit {t_audit * 1e3:.1f} ms"
           + ("; sequential exchange in each strategy's planning priority" if a.exchange == "sequential" else ""))
 
-    print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}")
+    print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}"
+          + "".join(f" {'c@%g' % l:>6}" for l in levels or []))
     no_contact = []
     for p in range(P):
         row = f"{p:5d} {len(combos[p]):6d} {int((plan['colloc_status'][p] == 0).sum()):3d}/{V}"
@@ -88,11 +110,13 @@ def main():
         done = arr.min(1) >= 0  # every vehicle of the scenario arrived
         last = arr.max(1)[done]
         n_contact = int((aud["first_contact"][sel] >= 0).sum())
-        print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{M:<2d} "
-              f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{M:<2d}")
+        n_sel = int(sel.sum())  # M starts x noise levels
+        print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{n_sel:<2d} "
+              f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
+              + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or []))
         if n_contact == 0:
             no_contact.append(p)
-    print(f"strategies whose {M} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
+    print(f"strategies whose {M * len(levels or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms")
     eng.close()
 

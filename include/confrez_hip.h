@@ -407,6 +407,33 @@ int cfz_loop_get(cfz_handle *h, double *state, double *pred, int32_t *status, in
  * (the order in force stays). */
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order);
 
+/* ---- disturbances of the closed loop ------------------------------------------------------------------------------------------
+ * The reference's follower measures its state exactly (opti.set_value of the current state, to which stage 0 is pinned,
+ * vehicle_follower.py:194-199) and its plant applies the solver's input exactly (:528-543).  With a disturbance set, step t of
+ * scenario s, vehicle v (cfz_loop_step and cfz_loop_run alike, under either exchange rule) becomes:
+ *   1. the solver's x0 is the measurement, state + d[0:5] (:194-199); the true state is kept;
+ *   2. parameters, warm start, solve, read-back or shift fallback as without (a measurement inside a clearance or outside the boxes
+ *      ends in status 4 and takes the fallback);
+ *   3. the applied input is (a0 + d[5], w0 + d[6]) clipped to the spec's input box, (a0, w0) being what the step would apply;
+ *   4. the new state is the plant (:528-543) from the TRUE state with the applied input, plus d[7:12];
+ *   5. the record (cfz_loop_record) keeps that true state and the applied input.  Predictions are the solver's own.
+ * d[i] = level[s] * sigma[i] * z[i], sigma = sigma_meas (x, y, psi, v, delta) | sigma_act (a, w) | sigma_proc (x, y, psi, v, delta) and
+ * z the twelve standard normals of (seed, stream[s], v, t): Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter
+ * (stream[s], v, t, j), j = 0..5, each call's four words giving z[2j], z[2j+1] by Box-Muller (csrc/cfz_disturb.inl states the
+ * bits).  t counts the MPC iterations done since cfz_loop_init / cfz_loop_init_tables.  A stream depends on (seed, stream id,
+ * vehicle, step) alone: not on S, on the workgroup that serves the item, on the exchange rule or on stepping against running.
+ * cfz_loop_set_disturbance: a NULL sigma group is zeros; all three NULL switch the disturbance off (the undisturbed kernels run
+ * again).  level[S] NULL: 1; stream[S] NULL: s.  The setting holds until it is changed and may change between calls, the step count
+ * keeps running; cfz_loop_init / cfz_loop_init_tables switch it off and reset the count.  Refused, the setting in force staying: a
+ * call before cfz_loop_init, a negative or non-finite sigma or level.
+ * cfz_loop_disturbance: d[K][S][V][12] that the loop adds at steps [t0, t0 + K) under the setting in force, past or future (a pure
+ * function of the setting); each d is a rounded double that the loop adds in one rounded addition, so a host replay that
+ * downloads d has the loop's exact inputs.  Refused when no disturbance is set, t0 < 0, K < 1. */
+int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_meas[5], const double sigma_act[2],
+                             const double sigma_proc[5], const double *level /* [S] or NULL: 1 */,
+                             const uint32_t *stream /* [S] or NULL: s */);
+int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d /* [K][S][V][12] */);
+
 /* ---- closed loop over per-scenario plans -------------------------------------------------------
  * tables[P][V][T][7]: a pool of P plan sets (each what cfz_loop_init takes as ref_table); scenario s follows set table_of[s]
  * (NULL: set s, which needs P == S).  Otherwise exactly cfz_loop_init, which is this call with P = 1 and every scenario on set 0.
