@@ -9,15 +9,19 @@
 //                  (scenario, vehicle, iteration) work items, hand-offs between workgroups at agent scope
 //   loop_kernel_seq  the same with the sequential exchange of cfz_loop_set_order (one body: cfz_loop_body.inl)
 //   loop_kernel_dist, loop_kernel_seq_dist  the same two with the disturbances of cfz_loop_set_disturbance (cfz_disturb.inl)
-//   loop_prep      closed loop: parameters and shifted warm start of every vehicle from the
-//                  previous predictions (reference vehicle_follower.py:432-476, 636-637)
-//   loop_post      closed loop: read-back or shift fallback, plant integration, clock
+//   loop_prep      stepwise closed loop (cfz_loop_step): parameters and shifted warm start of every vehicle from the
+//                  previous predictions (reference vehicle_follower.py:432-476, 636-637), the measurement under a disturbance
+//   loop_post      stepwise closed loop: read-back or shift fallback, plant integration, clock
 //                  (reference :484-563), and the record of the realised trajectory when one is kept (:556-563)
+//   vs_prep        loop_prep for the vehicle-sharded loop (cfz_vsl_step, which ends with loop_post): table, clock and neighbours
+//                  from the caller; the two share the __device__ function prep_stage
 //   audit_kernel   signed distances, first contact and arrivals along a recorded trajectory (cfz_audit.inl), one
 //                  wavefront per scenario
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
-// Host side: a handle owns all device buffers, one stream and two events.
+// Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
+// (loop_release).  cfz_loop_step is loop_round (prep, solve, post) once for Jacobi or V times for the sequential exchange;
+// cfz_loop_run picks its kernel from kLoopKernel[disturbed][sequential].
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -89,6 +93,28 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
 // ---- closed loop ------------------------------------------------------------------------------
 // pred[S][V][7][N] last predictions, state[S][V][5], kidx[S] reference sample index.  ref_table[P][V][T][7] is a pool of plan
 // sets; scenario s follows set table_of[s].
+// The rule of one step is stated once: cfz_loop_step (loop_prep) and cfz_vsl_step (vs_prep) differ in where the table, the clock and
+// the neighbours' predictions come from and share prep_stage; both end with loop_post.
+
+// stage k of instance b's parameters and warm start (vehicle_follower.py:432-476): the reference window from the vehicle's
+// plan[T][7] at clock k0, clamped at the last sample; its own prediction own[7][N] and the neighbours' advanced one step
+// (_adv_onestep, :413-426).  others[V][rows][N] holds x, y, psi of the scenario's V vehicles in the first three of `rows` rows; v is
+// the instance's vehicle.  rank[V] (NULL: none) with r: the vehicles ranked before r are read as they stand.
+__device__ inline void prep_stage(int b, int k, int N, int T, int V, int v, const double *plan, int k0, const double *own,
+                                  const double *others, int rows, const int32_t *rank, int r, double *ref, double *nbr, double *zu) {
+  const int ka = (k + 1 < N) ? k + 1 : N - 1;
+  int kr = k0 + k; if (kr > T - 1) kr = T - 1;
+  for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = plan[(size_t)kr * 7 + c];
+  for (int c = 0; c < 7; ++c) zu[((size_t)b * 7 + c) * N + k] = own[c * N + ka];
+  int o = 0;
+  for (int u = 0; u < V; ++u) {
+    if (u == v) continue;
+    const int ku = (rank && rank[u] < r) ? k : ka;
+    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + o) * 3 + c) * N + k] = others[((size_t)u * rows + c) * N + ku];
+    ++o;
+  }
+}
+
 // xperm / xrank [S][V] (cfz_loop_set_order): the exchange order of every scenario and its inverse.  NULL: Jacobi, one thread per
 // (instance, stage) of all B instances.  Otherwise round r of a sequential step: one thread per (scenario, stage), for the vehicle
 // v = xperm[s][r]; the neighbours ranked before it have already posted this step's prediction to `pred`, which starts at this
@@ -103,20 +129,9 @@ __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, c
   int b = (int)(tid / N);
   if (xperm) b = b * V + xperm[b * V + r];
   const int s = b / V, v = b - s * V;
-  const int ka = (k + 1 < N) ? k + 1 : N - 1;  // _adv_onestep (:413-426)
   if (k < 5) x0[b * 5 + k] = dz.sigma ? cfz::disturb_add(state[b * 5 + k], cfz::disturb_value(dz, s, v, step, k)) : state[b * 5 + k];
-  int kr = kidx[s] + k; if (kr > T - 1) kr = T - 1;
-  const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
-  for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = tab[((size_t)v * T + kr) * 7 + c];
-  for (int c = 0; c < 7; ++c) zu[((size_t)b * 7 + c) * N + k] = pred[((size_t)b * 7 + c) * N + ka];
-  int o = 0;
-  for (int u = 0; u < V; ++u) {
-    if (u == v) continue;
-    const size_t bo = (size_t)s * V + u;
-    const int ku = (xrank && xrank[bo] < r) ? k : ka;
-    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + o) * 3 + c) * N + k] = pred[(bo * 7 + c) * N + ku];
-    ++o;
-  }
+  prep_stage(b, k, N, T, V, v, ref_table + ((size_t)table_of[s] * V + v) * T * 7, kidx[s], pred + (size_t)b * 7 * N,
+             pred + (size_t)s * V * 7 * N, 7, xrank ? xrank + (size_t)s * V : nullptr, r, ref, nbr, zu);
 }
 
 __global__ void advance_clock(int S, int K, int32_t *kidx) {
@@ -127,13 +142,15 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
 // One thread per instance: accept the solution or shift the old prediction, integrate the plant.  rec (NULL: no record) is
 // this step's slice [S][V][7] of the record: state after the plant and the applied (a, w); rec_si its [2][S][V] status, iters.
 // xperm NULL: all B instances.  Otherwise round r of a sequential step (loop_prep): one thread per scenario, for its vehicle of
-// rank r; the clock advances with the last round, after every vehicle has read its reference.
+// rank r; the clock kidx (NULL: the caller keeps it) advances with the last round, after every vehicle has read its reference.
 // dz (dz.sigma NULL: none): the applied input is the prediction's first plus d[5:7], clipped to the input box [a_lo, a_hi] x
 // [w_lo, w_hi]; the plant starts from the true state and d[7:12] is added to what it returns; the record keeps both.
+// carry (NULL: none; cfz_vsl_step): the carry flag of the next iteration, a vehicle whose solve converged starts its next one from
+// these multipliers.
 __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
                           const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
                           int32_t *rec_si, int r, const int32_t *xperm, cfz::DisturbArgs dz, int step, double a_lo, double a_hi,
-                          double w_lo, double w_hi) {
+                          double w_lo, double w_hi, int32_t *carry) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (xperm ? S : S * V)) return;
   if (xperm) b = b * V + xperm[b * V + r];
@@ -156,7 +173,8 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
   if (dz.sigma)
     for (int i = 0; i < 5; ++i) out[i] = cfz::disturb_add(out[i], cfz::disturb_value(dz, s, v, step, 7 + i));
   for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
-  if (xperm ? r == V - 1 : b % V == 0) kidx[b / V] += 1;
+  if (kidx && (xperm ? r == V - 1 : b % V == 0)) kidx[b / V] += 1;
+  if (carry) carry[b] = status[b] == 0;
   if (rec) {
     double *r = rec + (size_t)b * 7;
     for (int i = 0; i < 5; ++i) r[i] = out[i];
@@ -169,7 +187,8 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
 // The glue of one MPC iteration around the solve, on the caller's stream: instances are ordered [s][o] (o = index into the
 // owned vehicles).  allpred[S][V][3][N] holds x, y, psi of EVERY vehicle's last prediction (gathered over RCCL by the
 // caller), pred[S][n_own][7][N] this rank's own predictions, table[n_own][T][7] the owned vehicles' plans.
-// vs_prep: parameters and shifted warm start (vehicle_follower.py:432-476).  One thread per (instance, stage).
+// vs_prep: parameters and shifted warm start (prep_stage), one thread per (instance, stage); the step ends with loop_post, which
+// writes the carry flag.
 __global__ void vs_prep(int S, int V, int n_own, int N, int T, const int32_t *own, const double *table, const int32_t *k0, int t,
                         const double *allpred, const double *pred, const double *state, double *x0, double *ref, double *nbr,
                         double *zu) {
@@ -177,38 +196,10 @@ __global__ void vs_prep(int S, int V, int n_own, int N, int T, const int32_t *ow
   if (tid >= (long)S * n_own * N) return;
   const int k = (int)(tid % N);
   const int b = (int)(tid / N);
-  const int s = b / n_own, o = b - s * n_own, v = own[o];
-  const int ka = (k + 1 < N) ? k + 1 : N - 1;  // _adv_onestep (:413-426)
+  const int s = b / n_own, o = b - s * n_own;
   if (k < 5) x0[b * 5 + k] = state[b * 5 + k];
-  int kr = k0[s] + t + k; if (kr > T - 1) kr = T - 1;
-  for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = table[((size_t)o * T + kr) * 7 + c];
-  for (int c = 0; c < 7; ++c) zu[((size_t)b * 7 + c) * N + k] = pred[((size_t)b * 7 + c) * N + ka];
-  int q = 0;
-  for (int u = 0; u < V; ++u) {
-    if (u == v) continue;
-    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + q) * 3 + c) * N + k] = allpred[(((size_t)s * V + u) * 3 + c) * N + ka];
-    ++q;
-  }
-}
-
-// vs_post: read-back or shift fallback (:484-524), plant (:528-543), and the carry flag of the next iteration (a vehicle
-// whose solve converged starts its next one from these multipliers).  One thread per instance.
-__global__ void vs_post(int B, int N, double dt, double wb, int plant_substeps, const int32_t *status, const double *zu,
-                        double *pred, double *state, int32_t *carry) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  double *pb = pred + (size_t)b * 7 * N;
-  if (status[b] == 0) {
-    for (int i = 0; i < 7 * N; ++i) pb[i] = zu[(size_t)b * 7 * N + i];
-  } else {
-    for (int c = 0; c < 7; ++c)
-      for (int k = 0; k + 1 < N; ++k) pb[c * N + k] = pb[c * N + k + 1];
-  }
-  double z[5], out[5];
-  for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
-  cfz::rk4_step<false>(z, pb[5 * N], pb[6 * N], dt, wb, plant_substeps, out, nullptr);
-  for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
-  carry[b] = status[b] == 0;
+  prep_stage(b, k, N, T, V, own[o], table + (size_t)o * T * 7, k0[s] + t, pred + (size_t)b * 7 * N, allpred + (size_t)s * V * 3 * N, 3,
+             nullptr, 0, ref, nbr, zu);
 }
 
 // Longest-processing-time-first dispatch order for the next step: instances sorted by the iteration count of
@@ -314,6 +305,10 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
   constexpr bool kSeq = true, kDist = true;
 #include "cfz_loop_body.inl"
 }
+
+// the persistent kernel of a setting, [disturbed][sequential]
+const void *const kLoopKernel[2][2] = {{(const void *)loop_kernel, (const void *)loop_kernel_seq},
+                                       {(const void *)loop_kernel_dist, (const void *)loop_kernel_seq_dist}};
 
 // d[K][S][V][12]: the disturbances of steps [t0, t0 + K) (cfz_loop_disturbance), one thread each, through the function the loop uses
 __global__ void disturb_fill(cfz::DisturbArgs dz, int S, int V, int t0, long n, double *d) {
@@ -555,34 +550,36 @@ struct cfz_handle {
   double *x0 = nullptr, *ref = nullptr, *nbr = nullptr, *zu = nullptr, *stats = nullptr;
   int32_t *status = nullptr, *iters = nullptr;
   double *l = nullptr, *m = nullptr, *lam_ij = nullptr, *lam_ji = nullptr, *s = nullptr;
-  // closed loop: ref_table[P][V][T][7] the pool of plan sets, table_of[S] the set of each scenario
-  int S = 0, T = 0, P = 0;
-  double *ref_table = nullptr, *pred = nullptr, *state = nullptr;
-  int32_t *kidx = nullptr, *order = nullptr, *table_of = nullptr;
-  // exchange order (cfz_loop_set_order; NULL: Jacobi): xperm[S][V] the order of every scenario, xrank[S][V] its inverse,
-  // xlist[V][S] the instance ids s * V + xperm[s][r] of round r (the dispatch list of a stepwise round)
-  int32_t *xperm = nullptr, *xrank = nullptr, *xlist = nullptr;
-  std::vector<int32_t> xperm_host;
-  // record of the realised trajectory (cfz_loop_record): rec[rec_cap][S][V][7], rec_si[rec_cap][2][S][V]; rec_used steps written
-  double *rec = nullptr;
-  int32_t *rec_si = nullptr;
-  int rec_cap = 0, rec_used = 0;
-  bool have_order = false;
-  // disturbances (cfz_loop_set_disturbance; dz_on false: none): one device buffer dz_buf = sigma[12] | level[S] | stream[S] (uint32);
-  // steps_done below is the step count of the streams
-  void *dz_buf = nullptr;
-  uint64_t dz_seed = 0;
-  bool dz_on = false;
-  // persistent loop
-  double *pred2 = nullptr, *scratch = nullptr;
-  int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
-  int queue_cap = 0, grid_blocks = 0, steps_done = 0;
+  // closed loop: everything cfz_loop_init_tables sets up; loop_release frees it and returns it to these defaults
+  struct Loop {
+    // ref_table[P][V][T][7] the pool of plan sets, table_of[S] the set of each scenario
+    int S = 0, T = 0, P = 0;
+    double *ref_table = nullptr, *pred = nullptr, *state = nullptr;
+    int32_t *kidx = nullptr, *order = nullptr, *table_of = nullptr;
+    bool have_order = false;
+    // exchange order (cfz_loop_set_order; NULL: Jacobi): xperm[S][V] the order of every scenario, xrank[S][V] its inverse,
+    // xlist[V][S] the instance ids s * V + xperm[s][r] of round r (the dispatch list of a stepwise round)
+    int32_t *xperm = nullptr, *xrank = nullptr, *xlist = nullptr;
+    std::vector<int32_t> xperm_host;
+    // record of the realised trajectory (cfz_loop_record): rec[rec_cap][S][V][7], rec_si[rec_cap][2][S][V]; rec_used steps written
+    double *rec = nullptr;
+    int32_t *rec_si = nullptr;
+    int rec_cap = 0, rec_used = 0;
+    // disturbances (cfz_loop_set_disturbance; dz_on false: none): one device buffer dz_buf = sigma[12] | level[S] | stream[S] (uint32);
+    // steps_done below is the step count of the streams
+    void *dz_buf = nullptr;
+    uint64_t dz_seed = 0;
+    bool dz_on = false;
+    // persistent loop
+    double *pred2 = nullptr, *scratch = nullptr;
+    int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
+    int queue_cap = 0, grid_blocks = 0, steps_done = 0;
+  } lp;
   long last_iter_sum = 0, last_converged = 0, last_status[6] = {0, 0, 0, 0, 0, 0};
   CfzArena arena;  // device buffers of cfz_dual_ws / cfz_joint_dual_ws, kept between calls
 };
 
 namespace {
-
 
 // grid (0: B) workgroups solve the instances order[0 .. grid) of the B (order NULL: 0 .. B)
 int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, const double *nbr, double *zu,
@@ -603,6 +600,7 @@ int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, cons
 }
 
 int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt);
+void loop_release(cfz_handle *h);
 
 int check(cfz_handle *h, int B) {
   if (!h) return fail("null handle");
@@ -696,14 +694,10 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
   if (const char *pad = std::getenv("CFZ_LDS_PAD")) h->lds_bytes += (size_t)std::atoi(pad);  // occupancy experiments only
   if (h->lds_bytes > 160 * 1024) return fail("problem does not fit the 160 KiB LDS of one CU");
   if (h->lds_bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void *)solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
-    if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
-    e = hipFuncSetAttribute((const void *)loop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
-    if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
-    e = hipFuncSetAttribute((const void *)loop_kernel_seq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)loop_kernel_dist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)loop_kernel_seq_dist, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
-    if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
+    for (const void *kern : {(const void *)solve_kernel, kLoopKernel[0][0], kLoopKernel[0][1], kLoopKernel[1][0], kLoopKernel[1][1]}) {
+      const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
+      if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
+    }
   }
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&h->blocks_per_cu, (const void *)solve_kernel, cfz::kNL, h->lds_bytes);
   {
@@ -753,10 +747,9 @@ extern "C" {
 int cfz_destroy(cfz_handle *h) {
   if (!h) return 0;
   hipSetDevice(h->device);
+  loop_release(h);
   void *bufs[] = {h->x0, h->ref, h->nbr, h->zu, h->stats, h->status, h->iters, h->l, h->m, h->lam_ij, h->lam_ji, h->s,
-                  h->ref_table, h->pred, h->state, h->kidx, h->order, h->pred2, h->scratch, h->queue, h->ctrl, h->done,
-                  h->iter_sum, h->obs_tab, h->wst, h->carry, h->slots, h->kargs, h->table_of, h->rec, h->rec_si,
-                  h->xperm, h->xrank, h->xlist, h->dz_buf};
+                  h->obs_tab, h->wst, h->carry, h->slots, h->kargs};
   for (void *p : bufs) if (p) hipFree(p);
   arena_destroy(h->arena);
   if (h->stage_host) hipHostFree(h->stage_host);
@@ -914,8 +907,9 @@ int cfz_vsl_step(cfz_handle *h, int S, int V, int n_own, const int32_t *d_own, i
   HIP_OK(hipGetLastError());
   h->carry_ext = t > 0 ? d_carry : nullptr;  // iteration 0 has nothing to carry
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, d_status, d_iters, d_stats, false, st)) return -1;
-  hipLaunchKernelGGL(vs_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, B, N, h->ks.dt, h->ks.wb, kPlantSubsteps, d_status, h->zu,
-                     d_pred, d_state, d_carry);
+  hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, S, n_own, N, h->ks.dt, h->ks.wb, kPlantSubsteps, d_status,
+                     nullptr, h->zu, d_pred, d_state, nullptr, nullptr, nullptr, 0, nullptr, cfz::DisturbArgs{0, nullptr, nullptr, nullptr}, 0,
+                     0.0, 0.0, 0.0, 0.0, d_carry);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -964,33 +958,73 @@ int cfz_joint_dual_ws(cfz_handle *h, int n, const double *poses_this, const doub
 }  // extern "C"
 
 namespace {
-void record_free(cfz_handle *h) {
-  if (h->rec) (void)hipFree(h->rec);
-  if (h->rec_si) (void)hipFree(h->rec_si);
-  h->rec = nullptr; h->rec_si = nullptr; h->rec_cap = h->rec_used = 0;
+template <class T> void dev_free(T *&p) {
+  if (p) (void)hipFree(p);
+  p = nullptr;
 }
 
-// room for `steps` more steps in the record (or no record at all)
+void record_free(cfz_handle *h) {
+  dev_free(h->lp.rec); dev_free(h->lp.rec_si);
+  h->lp.rec_cap = h->lp.rec_used = 0;
+}
+
 void exchange_free(cfz_handle *h) {
-  for (void *p : {(void *)h->xperm, (void *)h->xrank, (void *)h->xlist}) if (p) (void)hipFree(p);
-  h->xperm = h->xrank = h->xlist = nullptr;
-  h->xperm_host.clear();
+  dev_free(h->lp.xperm); dev_free(h->lp.xrank); dev_free(h->lp.xlist);
+  h->lp.xperm_host.clear();
 }
 
 void disturb_free(cfz_handle *h) {
-  if (h->dz_buf) (void)hipFree(h->dz_buf);
-  h->dz_buf = nullptr; h->dz_on = false; h->dz_seed = 0;
+  dev_free(h->lp.dz_buf);
+  h->lp.dz_on = false; h->lp.dz_seed = 0;
+}
+
+// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance setting and the
+// persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
+void loop_release(cfz_handle *h) {
+  record_free(h); exchange_free(h); disturb_free(h);
+  dev_free(h->lp.ref_table); dev_free(h->lp.table_of); dev_free(h->lp.pred); dev_free(h->lp.state); dev_free(h->lp.kidx); dev_free(h->lp.order);
+  dev_free(h->lp.pred2); dev_free(h->lp.scratch); dev_free(h->lp.queue); dev_free(h->lp.ctrl); dev_free(h->lp.done); dev_free(h->lp.iter_sum);
+  h->lp = cfz_handle::Loop();
 }
 
 // the setting in force as the kernels take it (sigma NULL: none)
 cfz::DisturbArgs disturb_args(const cfz_handle *h) {
-  if (!h->dz_on) return {0, nullptr, nullptr, nullptr};
-  const double *f = static_cast<const double *>(h->dz_buf);
-  return {h->dz_seed, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->S)};
+  if (!h->lp.dz_on) return {0, nullptr, nullptr, nullptr};
+  const double *f = static_cast<const double *>(h->lp.dz_buf);
+  return {h->lp.dz_seed, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
 }
 
+// room for `steps` more steps in the record (or no record at all)
 int record_room(cfz_handle *h, int steps) {
-  if (h->rec_cap && h->rec_used + steps > h->rec_cap) return fail("the step(s) would overflow the record (cfz_loop_record)");
+  if (h->lp.rec_cap && h->lp.rec_used + steps > h->lp.rec_cap) return fail("the step(s) would overflow the record (cfz_loop_record)");
+  return 0;
+}
+
+// the slice of the step about to be written in rec and rec_si (NULL: no record is kept)
+void record_slice(const cfz_handle *h, double *&rec, int32_t *&rec_si) {
+  const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
+  rec = h->lp.rec ? h->lp.rec + (size_t)h->lp.rec_used * B * 7 : nullptr;
+  rec_si = h->lp.rec ? h->lp.rec_si + (size_t)h->lp.rec_used * 2 * B : nullptr;
+}
+
+// One round of a stepwise iteration (cfz_loop_step): loop_prep, solve_kernel, loop_post for n_inst instances.  Jacobi: all B of them,
+// xperm and xrank NULL; round r of the sequential exchange: the S vehicles of rank r.  dispatch (NULL: index order) lists the instance
+// ids in the order the solve's workgroups take them; the carry slot of instance b is b either way.
+int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const int32_t *xperm, const int32_t *xrank) {
+  const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->lp.S;
+  double *rec; int32_t *rec_si;
+  record_slice(h, rec, rec_si);
+  const cfz::DisturbArgs dz = disturb_args(h);
+  const double *bd = h->ks.bounds;  // (the input box: a in [bd[8], bd[9]], w in [bd[10], bd[11]])
+  const long nt = (long)n_inst * N;
+  hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->lp.T, h->lp.ref_table,
+                     h->lp.table_of, h->lp.kidx, h->lp.pred, h->lp.state, h->x0, h->ref, h->nbr, h->zu, r, xperm, xrank, dz, h->lp.steps_done);
+  HIP_OK(hipGetLastError());
+  if (launch_solve(h, S * V, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, dispatch, 1, n_inst)) return -1;
+  hipLaunchKernelGGL(loop_post, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
+                     h->status, h->iters, h->zu, h->lp.pred, h->lp.state, h->lp.kidx, rec, rec_si, r, xperm, dz, h->lp.steps_done, bd[8], bd[9], bd[10],
+                     bd[11], nullptr);
+  HIP_OK(hipGetLastError());
   return 0;
 }
 
@@ -1046,27 +1080,21 @@ int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *table
     if (tof[s] < 0 || tof[s] >= P) return fail("table_of[s] outside [0, P)");
   }
   HIP_OK(hipSetDevice(h->device));
-  for (void *p : {(void *)h->ref_table, (void *)h->pred, (void *)h->state, (void *)h->kidx, (void *)h->order, (void *)h->table_of}) if (p) hipFree(p);
-  h->ref_table = h->pred = h->state = nullptr; h->kidx = nullptr; h->order = nullptr; h->table_of = nullptr; h->have_order = false;
-  record_free(h);  // a record belongs to one initialisation (its shape is that of S)
-  exchange_free(h);  // back to Jacobi
-  disturb_free(h);   // back to the undisturbed loop; the step count restarts below
-  h->S = S; h->T = T; h->P = P;
+  loop_release(h);  // record, exchange order and disturbance included: back to the undisturbed Jacobi loop at step 0
+  h->lp.S = S; h->lp.T = T; h->lp.P = P;
   const size_t B = (size_t)S * V;
-  HIP_OK(hipMalloc(&h->ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->pred, B * 7 * N * 8));
-  HIP_OK(hipMalloc(&h->state, B * 5 * 8)); HIP_OK(hipMalloc(&h->kidx, (size_t)S * 4));
-  HIP_OK(hipMalloc(&h->order, B * 4)); HIP_OK(hipMalloc(&h->table_of, (size_t)S * 4));
+  HIP_OK(hipMalloc(&h->lp.ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->lp.pred, B * 7 * N * 8));
+  HIP_OK(hipMalloc(&h->lp.state, B * 5 * 8)); HIP_OK(hipMalloc(&h->lp.kidx, (size_t)S * 4));
+  HIP_OK(hipMalloc(&h->lp.order, B * 4)); HIP_OK(hipMalloc(&h->lp.table_of, (size_t)S * 4));
   HIP_OK(hipMemset(h->wst, 0, (size_t)h->max_batch * h->wst_stride * 8));  // first iteration: cold multipliers
-  for (void *p : {(void *)h->pred2, (void *)h->scratch, (void *)h->queue, (void *)h->ctrl, (void *)h->done, (void *)h->iter_sum}) if (p) (void)hipFree(p);
-  h->pred2 = h->scratch = nullptr; h->queue = h->ctrl = h->done = h->iter_sum = nullptr; h->queue_cap = 0; h->grid_blocks = 0; h->steps_done = 0;
-  HIP_OK(hipMemcpy(h->ref_table, tables, (size_t)P * V * T * 7 * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->table_of, tof.data(), (size_t)S * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->kidx, k0, (size_t)S * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->lp.ref_table, tables, (size_t)P * V * T * 7 * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->lp.table_of, tof.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->lp.kidx, k0, (size_t)S * 4, hipMemcpyHostToDevice));
   double *dn = nullptr;
   if (noise) { if (arena_reset(h->arena)) return -1; ARENA_ALLOC(h->arena, dn, B * 5 * 8); HIP_OK(hipMemcpy(dn, noise, B * 5 * 8, hipMemcpyHostToDevice)); }
   const long nt = (long)B * N;
-  hipLaunchKernelGGL(loop_seed, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, T, h->ref_table,
-                     h->table_of, h->kidx, dn, h->pred, h->state);
+  hipLaunchKernelGGL(loop_seed, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, T, h->lp.ref_table,
+                     h->lp.table_of, h->lp.kidx, dn, h->lp.pred, h->lp.state);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(h->stream));
   return 0;
@@ -1080,28 +1108,28 @@ int cfz_loop_init(cfz_handle *h, int S, int T, const double *ref_table, const in
 }
 
 int cfz_loop_record(cfz_handle *h, int K) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   if (K < 0) return fail("K must not be negative");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
   record_free(h);
   if (K == 0) return 0;
-  const size_t B = (size_t)h->S * (h->ks.n_nbr + 1);
+  const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
   if ((size_t)K * B * 7 > ((size_t)1 << 31)) return fail("record too large");
-  HIP_OK(hipMalloc(&h->rec, (size_t)K * B * 7 * 8)); HIP_OK(hipMalloc(&h->rec_si, (size_t)K * 2 * B * 4));
-  h->rec_cap = K;
+  HIP_OK(hipMalloc(&h->lp.rec, (size_t)K * B * 7 * 8)); HIP_OK(hipMalloc(&h->lp.rec_si, (size_t)K * 2 * B * 4));
+  h->lp.rec_cap = K;
   return 0;
 }
 
 int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status, int32_t *iters) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
-  if (t0 < 0 || K < 1 || t0 + K > h->rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
   HIP_OK(hipSetDevice(h->device));
-  const size_t B = (size_t)h->S * (h->ks.n_nbr + 1);
-  if (traj) HIP_OK(hipMemcpy(traj, h->rec + (size_t)t0 * B * 7, (size_t)K * B * 7 * 8, hipMemcpyDeviceToHost));
+  const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
+  if (traj) HIP_OK(hipMemcpy(traj, h->lp.rec + (size_t)t0 * B * 7, (size_t)K * B * 7 * 8, hipMemcpyDeviceToHost));
   if (status || iters) {
     std::vector<int32_t> si((size_t)K * 2 * B);
-    HIP_OK(hipMemcpy(si.data(), h->rec_si + (size_t)t0 * 2 * B, si.size() * 4, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(si.data(), h->lp.rec_si + (size_t)t0 * 2 * B, si.size() * 4, hipMemcpyDeviceToHost));
     for (int k = 0; k < K; ++k) {
       if (status) memcpy(status + (size_t)k * B, si.data() + (size_t)k * 2 * B, B * 4);
       if (iters) memcpy(iters + (size_t)k * B, si.data() + ((size_t)k * 2 + 1) * B, B * 4);
@@ -1112,17 +1140,17 @@ int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status
 
 int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
                    int32_t *first_contact, int32_t *arrive) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
-  if (t0 < 0 || K < 1 || t0 + K > h->rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
   HIP_OK(hipSetDevice(h->device));
-  const int S = h->S, V = h->ks.n_nbr + 1;
+  const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t B = (size_t)S * V;
   if (arena_reset(h->arena)) return -1;
   double *dg = nullptr;
   ARENA_ALLOC(h->arena, dg, B * 3 * 8);
-  hipLaunchKernelGGL(loop_goals, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, h->T, h->ref_table, h->table_of, dg);
+  hipLaunchKernelGGL(loop_goals, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, h->lp.T, h->lp.ref_table, h->lp.table_of, dg);
   HIP_OK(hipGetLastError());
-  return audit_launch(h, K, S, V, h->rec + (size_t)t0 * B * 7, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
+  return audit_launch(h, K, S, V, h->lp.rec + (size_t)t0 * B * 7, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
 }
 
 int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, double pos_tol, double psi_tol, double v_tol,
@@ -1141,11 +1169,11 @@ int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const doub
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
   if (!order) { exchange_free(h); return 0; }
-  const int S = h->S, V = h->ks.n_nbr + 1;
+  const int S = h->lp.S, V = h->ks.n_nbr + 1;
   std::vector<int32_t> rank((size_t)S * V), list((size_t)V * S);
   for (int s = 0; s < S; ++s) {
     std::vector<char> seen((size_t)V, 0);
@@ -1156,24 +1184,24 @@ int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
       rank[(size_t)s * V + v] = r; list[(size_t)r * S + s] = s * V + v;
     }
   }
-  if (!h->xperm) {
-    HIP_OK(hipMalloc(&h->xperm, (size_t)S * V * 4)); HIP_OK(hipMalloc(&h->xrank, (size_t)S * V * 4));
-    HIP_OK(hipMalloc(&h->xlist, (size_t)S * V * 4));
+  if (!h->lp.xperm) {
+    HIP_OK(hipMalloc(&h->lp.xperm, (size_t)S * V * 4)); HIP_OK(hipMalloc(&h->lp.xrank, (size_t)S * V * 4));
+    HIP_OK(hipMalloc(&h->lp.xlist, (size_t)S * V * 4));
   }
-  HIP_OK(hipMemcpy(h->xperm, order, (size_t)S * V * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->xrank, rank.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->xlist, list.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
-  h->xperm_host.assign(order, order + (size_t)S * V);
+  HIP_OK(hipMemcpy(h->lp.xperm, order, (size_t)S * V * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->lp.xrank, rank.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(h->lp.xlist, list.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
+  h->lp.xperm_host.assign(order, order + (size_t)S * V);
   return 0;
 }
 
 int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_meas[5], const double sigma_act[2],
                              const double sigma_proc[5], const double *level, const uint32_t *stream) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   HIP_OK(hipSetDevice(h->device));
   HIP_OK(hipStreamSynchronize(h->stream));
-  if (!sigma_meas && !sigma_act && !sigma_proc) { h->dz_on = false; return 0; }  // off: the plain kernels
-  const int S = h->S;
+  if (!sigma_meas && !sigma_act && !sigma_proc) { h->lp.dz_on = false; return 0; }  // off: the plain kernels
+  const int S = h->lp.S;
   std::vector<double> f((size_t)cfz::kDisturbN + S, 0.0);
   for (int i = 0; i < 5; ++i) { if (sigma_meas) f[i] = sigma_meas[i]; if (sigma_proc) f[7 + i] = sigma_proc[i]; }
   for (int i = 0; i < 2; ++i) if (sigma_act) f[5 + i] = sigma_act[i];
@@ -1185,19 +1213,19 @@ int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_me
   }
   std::vector<uint32_t> id((size_t)S);
   for (int s = 0; s < S; ++s) id[s] = stream ? stream[s] : (uint32_t)s;
-  if (!h->dz_buf) HIP_OK(hipMalloc(&h->dz_buf, f.size() * 8 + id.size() * 4));
-  HIP_OK(hipMemcpy(h->dz_buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(static_cast<char *>(h->dz_buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
-  h->dz_seed = seed; h->dz_on = true;
+  if (!h->lp.dz_buf) HIP_OK(hipMalloc(&h->lp.dz_buf, f.size() * 8 + id.size() * 4));
+  HIP_OK(hipMemcpy(h->lp.dz_buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(static_cast<char *>(h->lp.dz_buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  h->lp.dz_seed = seed; h->lp.dz_on = true;
   return 0;
 }
 
 int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
-  if (!h->dz_on) return fail("no disturbance is set (cfz_loop_set_disturbance)");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (!h->lp.dz_on) return fail("no disturbance is set (cfz_loop_set_disturbance)");
   if (t0 < 0 || K < 1 || !d) return fail("t0 must not be negative, K must be positive and d not NULL");
   HIP_OK(hipSetDevice(h->device));
-  const int S = h->S, V = h->ks.n_nbr + 1;
+  const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t n = (size_t)K * S * V * cfz::kDisturbN;
   if (n > ((size_t)1 << 31)) return fail("window too large");
   if (arena_reset(h->arena)) return -1;
@@ -1211,82 +1239,53 @@ int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d) {
 }
 
 int cfz_loop_step(cfz_handle *h) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   if (record_room(h, 1)) return -1;
   HIP_OK(hipSetDevice(h->device));
-  const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->S, B = S * V;
-  double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
-  int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
-  const cfz::DisturbArgs dz = disturb_args(h);
-  const double *bd = h->ks.bounds;  // (the input box: a in [bd[8], bd[9]], w in [bd[10], bd[11]])
-  if (h->xperm) {
-    // sequential exchange: V rounds; round r prepares, solves (S instances, dispatch list xlist[r], carry slot b as in Jacobi)
-    // and posts the vehicle of rank r of every scenario.  The solve time is the sum of the V launches; each round's events
-    // are read once the next round's preparation is queued behind them.
-    const long nt = (long)S * N;
-    float total_ms = 0.f;
+  const int V = h->ks.n_nbr + 1, S = h->lp.S, B = S * V;
+  float total_ms = 0.f;
+  if (h->lp.xperm) {
+    // sequential exchange: V rounds; round r prepares, solves (S instances, dispatch list xlist[r]) and posts the vehicle of rank r
+    // of every scenario.  The solve time is the sum of the V launches: launch_solve records ev0 / ev1 anew, so each round's pair is
+    // read before the next round is queued.
     for (int r = 0; r < V; ++r) {
       if (r > 0) {
         HIP_OK(hipEventSynchronize(h->ev1));
         float ms = 0.f;
         HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1)); total_ms += ms;
       }
-      hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
-                         h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, r, h->xperm, h->xrank, dz, h->steps_done);
-      HIP_OK(hipGetLastError());
-      if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, h->xlist + (size_t)r * S,
-                       1, S)) return -1;
-      hipLaunchKernelGGL(loop_post, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb,
-                         kPlantSubsteps, h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, r, h->xperm, dz, h->steps_done,
-                         bd[8], bd[9], bd[10], bd[11]);
-      HIP_OK(hipGetLastError());
+      if (loop_round(h, r, S, h->lp.xlist + (size_t)r * S, h->lp.xperm, h->lp.xrank)) return -1;
     }
-    if (h->rec) h->rec_used += 1;
-    h->steps_done += 1;
-    h->have_order = false;  // the LPT list is the Jacobi steps' own
-    HIP_OK(hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->last_ms = total_ms + ms;
-    h->ms_pending = false;
-    return 0;
+    h->lp.have_order = false;  // the LPT list is the Jacobi steps' own
+  } else {
+    if (loop_round(h, 0, B, h->lp.have_order ? h->lp.order : nullptr, nullptr, nullptr)) return -1;
+    hipLaunchKernelGGL(order_by_iters, dim3(1), dim3(1024), 0, h->stream, B, h->iters, h->lp.order);
+    HIP_OK(hipGetLastError());
+    h->lp.have_order = true;
   }
-  const long nt = (long)B * N;
-  hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->T, h->ref_table,
-                     h->table_of, h->kidx, h->pred, h->state, h->x0, h->ref, h->nbr, h->zu, 0, nullptr, nullptr, dz, h->steps_done);
-  HIP_OK(hipGetLastError());
-  if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream,
-                   h->have_order ? h->order : nullptr, 1)) return -1;
-  hipLaunchKernelGGL(order_by_iters, dim3(1), dim3(1024), 0, h->stream, B, h->iters, h->order);
-  HIP_OK(hipGetLastError());
-  h->have_order = true;
-  hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
-                     h->status, h->iters, h->zu, h->pred, h->state, h->kidx, rec, rec_si, 0, nullptr, dz, h->steps_done, bd[8], bd[9], bd[10],
-                     bd[11]);
-  HIP_OK(hipGetLastError());
-  if (h->rec) h->rec_used += 1;
-  h->steps_done += 1;
+  if (h->lp.rec) h->lp.rec_used += 1;
+  h->lp.steps_done += 1;
   HIP_OK(hipStreamSynchronize(h->stream));
-  HIP_OK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
+  float ms = 0.f;
+  HIP_OK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = total_ms + ms;
   h->ms_pending = false;
   return 0;
 }
 
 int cfz_loop_run(cfz_handle *h, int K) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   if (K < 1) return fail("K must be positive");
   if (record_room(h, K)) return -1;
   HIP_OK(hipSetDevice(h->device));
-  const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->S, B = S * V;
+  const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->lp.S, B = S * V;
   const size_t total = (size_t)B * K;
   if (total > (size_t)1 << 30) return fail("too many work items");
   int ncu = 0;
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
-  const bool seq = h->xperm != nullptr, dist = h->dz_on;
-  const void *kern = dist ? (seq ? (const void *)loop_kernel_seq_dist : (const void *)loop_kernel_dist)
-                          : (seq ? (const void *)loop_kernel_seq : (const void *)loop_kernel);
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, cfz::kNL, h->lds_bytes));
+  const bool seq = h->lp.xperm != nullptr, dist = h->lp.dz_on;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kLoopKernel[dist][seq], cfz::kNL, h->lds_bytes));
   per_cu = std::min(per_cu, h->blocks_per_cu);  // the 2 KiB LDS granules (cfz_create): what the hardware really keeps resident
   if (per_cu < 1) return fail("loop kernel does not fit on a CU");
   // one workgroup per resident slot: more would only queue behind them (any workgroup can serve any item, so a surplus
@@ -1296,67 +1295,58 @@ int cfz_loop_run(cfz_handle *h, int K) {
   // would end the launch through the idle give-up
   const int grid = std::min(seq ? S : B, per_cu * ncu);
   const size_t per_block = 5 + 3 * (size_t)N + (size_t)h->ks.n_nbr * 3 * N + 7 * (size_t)N;
-  if (!h->pred2) {
-    HIP_OK(hipMalloc(&h->pred2, (size_t)2 * B * 7 * N * 8)); HIP_OK(hipMalloc(&h->ctrl, (4 + 1024) * 4));
-    HIP_OK(hipMalloc(&h->done, (size_t)S * 4)); HIP_OK(hipMalloc(&h->iter_sum, 32));
+  if (!h->lp.pred2) {
+    HIP_OK(hipMalloc(&h->lp.pred2, (size_t)2 * B * 7 * N * 8)); HIP_OK(hipMalloc(&h->lp.ctrl, (4 + 1024) * 4));
+    HIP_OK(hipMalloc(&h->lp.done, (size_t)S * 4)); HIP_OK(hipMalloc(&h->lp.iter_sum, 32));
   }
-  if (h->grid_blocks < grid) {
-    if (h->scratch) (void)hipFree(h->scratch);
-    HIP_OK(hipMalloc(&h->scratch, (size_t)grid * per_block * 8)); h->grid_blocks = grid;
+  if (h->lp.grid_blocks < grid) {
+    if (h->lp.scratch) (void)hipFree(h->lp.scratch);
+    HIP_OK(hipMalloc(&h->lp.scratch, (size_t)grid * per_block * 8)); h->lp.grid_blocks = grid;
   }
   const size_t qwords = 2 * (size_t)K + total;  // [head K][tail K][slots K x B]
-  if ((size_t)h->queue_cap < qwords) {
-    if (h->queue) (void)hipFree(h->queue);
-    HIP_OK(hipMalloc(&h->queue, qwords * 4)); h->queue_cap = (int)qwords;
+  if ((size_t)h->lp.queue_cap < qwords) {
+    if (h->lp.queue) (void)hipFree(h->lp.queue);
+    HIP_OK(hipMalloc(&h->lp.queue, qwords * 4)); h->lp.queue_cap = (int)qwords;
   }
   // parity 0 of the double buffer <- current predictions; queue <- all items of iteration 0
-  HIP_OK(hipMemcpyAsync(h->pred2, h->pred, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
-  HIP_OK(hipMemsetAsync(h->queue, 0, 2 * (size_t)K * 4, h->stream));
-  HIP_OK(hipMemsetAsync(h->queue + 2 * K, 0xff, total * 4, h->stream));
+  HIP_OK(hipMemcpyAsync(h->lp.pred2, h->lp.pred, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
+  HIP_OK(hipMemsetAsync(h->lp.queue, 0, 2 * (size_t)K * 4, h->stream));
+  HIP_OK(hipMemsetAsync(h->lp.queue + 2 * K, 0xff, total * 4, h->stream));
   {
     // Jacobi: all B items; sequential: the S items (s, xperm[s][0])
     const int n0 = seq ? S : B;
     std::vector<int32_t> first(n0);
-    for (int i = 0; i < n0; ++i) first[i] = seq ? i * V + h->xperm_host[(size_t)i * V] : i;
-    HIP_OK(hipMemcpyAsync(h->queue + 2 * K, first.data(), (size_t)n0 * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_OK(hipMemcpyAsync(h->queue + K, &n0, 4, hipMemcpyHostToDevice, h->stream));  // tail[0]
+    for (int i = 0; i < n0; ++i) first[i] = seq ? i * V + h->lp.xperm_host[(size_t)i * V] : i;
+    HIP_OK(hipMemcpyAsync(h->lp.queue + 2 * K, first.data(), (size_t)n0 * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(h->lp.queue + K, &n0, 4, hipMemcpyHostToDevice, h->stream));  // tail[0]
     const int32_t ctrl0[4] = {0, 0, 0, 0};
-    HIP_OK(hipMemcpyAsync(h->ctrl, ctrl0, sizeof ctrl0, hipMemcpyHostToDevice, h->stream));
-    HIP_OK(hipMemsetAsync(h->done, 0, (size_t)S * 4, h->stream));
-    HIP_OK(hipMemsetAsync(h->iter_sum, 0, 32, h->stream));
+    HIP_OK(hipMemcpyAsync(h->lp.ctrl, ctrl0, sizeof ctrl0, hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemsetAsync(h->lp.done, 0, (size_t)S * 4, h->stream));
+    HIP_OK(hipMemsetAsync(h->lp.iter_sum, 0, 32, h->stream));
     HIP_OK(hipStreamSynchronize(h->stream));  // `first` and `ctrl0` are host temporaries
   }
   HIP_OK(hipEventRecord(h->ev0, h->stream));
-  double *rec = h->rec ? h->rec + (size_t)h->rec_used * B * 7 : nullptr;
-  int32_t *rec_si = h->rec ? h->rec_si + (size_t)h->rec_used * 2 * B : nullptr;
+  double *rec; int32_t *rec_si;
+  record_slice(h, rec, rec_si);
   const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
   const cfz::DisturbArgs dz = disturb_args(h);
-  if (dist && seq)
-    hipLaunchKernelGGL(loop_kernel_seq_dist, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
-                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
-                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si,
-                       h->xperm, h->xrank, dz, h->steps_done);
-  else if (dist)
-    hipLaunchKernelGGL(loop_kernel_dist, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
-                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
-                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, dz,
-                       h->steps_done);
-  else if (seq)
-    hipLaunchKernelGGL(loop_kernel_seq, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
-                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
-                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si,
-                       h->xperm, h->xrank);
-  else
-    hipLaunchKernelGGL(loop_kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->T,
-                       h->ref_table, h->table_of, h->kidx, 0, h->pred2, h->state, h->scratch, h->queue, h->ctrl, h->done, h->status,
-                       h->iters, h->stats, h->iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si);
+  // the four kernels share their arguments up to the record; `tail` is the exchange order and / or the disturbance setting
+  auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->lp.T, h->lp.ref_table, h->lp.table_of,
+                       h->lp.kidx, 0, h->lp.pred2, h->lp.state, h->lp.scratch, h->lp.queue, h->lp.ctrl, h->lp.done, h->status, h->iters, h->stats, h->lp.iter_sum,
+                       h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, tail...);
+  };
+  if (dist && seq) launch(loop_kernel_seq_dist, h->lp.xperm, h->lp.xrank, dz, h->lp.steps_done);
+  else if (dist) launch(loop_kernel_dist, dz, h->lp.steps_done);
+  else if (seq) launch(loop_kernel_seq, h->lp.xperm, h->lp.xrank);
+  else launch(loop_kernel);
   HIP_OK(hipGetLastError());
-  if (h->rec) h->rec_used += K;
-  h->steps_done += K;
+  if (h->lp.rec) h->lp.rec_used += K;
+  h->lp.steps_done += K;
   HIP_OK(hipEventRecord(h->ev1, h->stream));
   // predictions after K iterations live in parity K%2; advance the scenario clocks by K
-  HIP_OK(hipMemcpyAsync(h->pred, h->pred2 + (size_t)(K & 1) * B * 7 * N, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
-  hipLaunchKernelGGL(advance_clock, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, K, h->kidx);
+  HIP_OK(hipMemcpyAsync(h->lp.pred, h->lp.pred2 + (size_t)(K & 1) * B * 7 * N, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
+  hipLaunchKernelGGL(advance_clock, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, K, h->lp.kidx);
   HIP_OK(hipGetLastError());
   if (const char *dbg = std::getenv("CFZ_LOOP_WATCHDOG")) {
     // diagnostic: watch the queue counters from a second stream while the kernel runs; stop it if it stalls
@@ -1366,18 +1356,18 @@ int cfz_loop_run(cfz_handle *h, int K) {
     while (hipEventQuery(h->ev1) == hipErrorNotReady) {
       usleep(100000);
       int32_t c[4] = {0, 0, 0, 0};
-      HIP_OK(hipMemcpyAsync(c, h->ctrl, sizeof c, hipMemcpyDeviceToHost, s2)); HIP_OK(hipStreamSynchronize(s2));
+      HIP_OK(hipMemcpyAsync(c, h->lp.ctrl, sizeof c, hipMemcpyDeviceToHost, s2)); HIP_OK(hipStreamSynchronize(s2));
       std::fprintf(stderr, "[cfz watchdog] lowest open iteration %d, completed %d of %zu, err %d (grid %d)", c[0], c[1], total, c[2], grid);
 #ifdef CFZ_LOOP_TRACE
       int32_t mk[8];
-      HIP_OK(hipMemcpyAsync(mk, h->ctrl + 4, sizeof mk, hipMemcpyDeviceToHost, s2)); HIP_OK(hipStreamSynchronize(s2));
+      HIP_OK(hipMemcpyAsync(mk, h->lp.ctrl + 4, sizeof mk, hipMemcpyDeviceToHost, s2)); HIP_OK(hipStreamSynchronize(s2));
       for (int i = 0; i < 8 && i < grid; ++i) std::fprintf(stderr, " m%d=%d", i, mk[i]);
 #endif
       std::fprintf(stderr, "\n");
       stalled = (c[1] == last_head) ? stalled + 0.1 : 0.0; last_head = c[1];
       if (stalled > limit_s) {
         const int32_t one = 1;
-        HIP_OK(hipMemcpyAsync(h->ctrl + 2, &one, 4, hipMemcpyHostToDevice, s2)); HIP_OK(hipStreamSynchronize(s2));
+        HIP_OK(hipMemcpyAsync(h->lp.ctrl + 2, &one, 4, hipMemcpyHostToDevice, s2)); HIP_OK(hipStreamSynchronize(s2));
         stalled = -1e9;
       }
     }
@@ -1387,11 +1377,11 @@ int cfz_loop_run(cfz_handle *h, int K) {
   HIP_OK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
   h->ms_pending = false;
   int32_t ctrl[4] = {0, 0, 0, 0}, isum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HIP_OK(hipMemcpy(ctrl, h->ctrl, sizeof ctrl, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(isum, h->iter_sum, 32, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(ctrl, h->lp.ctrl, sizeof ctrl, hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(isum, h->lp.iter_sum, 32, hipMemcpyDeviceToHost));
   h->last_iter_sum = isum[0]; h->last_converged = isum[1];
   for (int i = 0; i < 6; ++i) h->last_status[i] = isum[2 + i];
-  h->have_order = false;
+  h->lp.have_order = false;
   if (ctrl[2]) return fail("persistent loop kernel timed out waiting for a work item");
   return 0;
 }
@@ -1405,11 +1395,11 @@ int cfz_loop_last_status_counts(const cfz_handle *h, long counts[6]) {
 }
 
 int cfz_loop_get(cfz_handle *h, double *state, double *pred, int32_t *status, int32_t *iters) {
-  if (!h || !h->pred) return fail("cfz_loop_init has not been called");
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   HIP_OK(hipSetDevice(h->device));
-  const size_t B = (size_t)h->S * (h->ks.n_nbr + 1), N = h->ks.N;
-  if (state) HIP_OK(hipMemcpy(state, h->state, B * 5 * 8, hipMemcpyDeviceToHost));
-  if (pred) HIP_OK(hipMemcpy(pred, h->pred, B * 7 * N * 8, hipMemcpyDeviceToHost));
+  const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1), N = h->ks.N;
+  if (state) HIP_OK(hipMemcpy(state, h->lp.state, B * 5 * 8, hipMemcpyDeviceToHost));
+  if (pred) HIP_OK(hipMemcpy(pred, h->lp.pred, B * 7 * N * 8, hipMemcpyDeviceToHost));
   if (status) HIP_OK(hipMemcpy(status, h->status, B * 4, hipMemcpyDeviceToHost));
   if (iters) HIP_OK(hipMemcpy(iters, h->iters, B * 4, hipMemcpyDeviceToHost));
   return 0;

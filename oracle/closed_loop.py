@@ -6,8 +6,11 @@ vehicle steps (:642-647): `_adv_onestep` shift of its own and its neighbours' pr
 (:479) started from the multipliers its previous solve left (`cfz_port_solve_carry`; the reference hands the old duals
 to `opti.set_initial`, :458-464), read-back (:484-500) or shift fallback (:501-524), plant over dt (:528-543).
 
-Used by tests/test_gpu_parity.py (the device loop must reproduce it solve by solve) and by bench.py's `cpu_baseline`
-leg (the same workload timed on the host cores).  Never imported by the product package.
+`step_inputs` is the one host statement of what a solve is fed; `replay` is the loop around it, with the sequential exchange
+(`order`) and the disturbances (`d`) of the device loop as options.
+
+Used by the GPU tests (the device loop must reproduce it solve by solve) and by bench.py's `cpu_baseline` leg (the same workload
+timed on the host cores).  Never imported by the product package.
 """
 import numpy as np
 
@@ -16,35 +19,59 @@ from .dynamics import plant_step
 from .mpc_nlp import MpcSpec
 
 
-def seed(table, k0, noise, N):
-    """State and first prediction of every (scenario, vehicle) as `get_current_ref` seeds them (:397-400)."""
-    S, V, T = len(k0), table.shape[0], table.shape[1]
+def seed(table, k0, noise, N, table_of=None):
+    """State and first prediction of every (scenario, vehicle) as `get_current_ref` seeds them (:397-400).  table [V,T,7], or a pool
+    [P,V,T,7] with table_of [S]."""
+    S = len(k0)
+    V, T = table.shape[-3], table.shape[-2]
     state = np.zeros((S, V, 5)); pred = np.zeros((S, V, 7, N))
     for s in range(S):
+        tab = table if table_of is None else table[table_of[s]]
         for v in range(V):
-            pred[s, v] = table[v, np.minimum(k0[s] + np.arange(N), T - 1), :].T
-            state[s, v] = table[v, k0[s], :5] + noise[s, v]
+            pred[s, v] = tab[v, np.minimum(k0[s] + np.arange(N), T - 1), :].T
+            state[s, v] = tab[v, k0[s], :5] + noise[s, v]
     return state, pred
 
 
-def replay(ospec: MpcSpec, table, k0, noise, steps, dt=0.1, wb=2.5, carry_duals=True, opt=None):
-    """Generator: after every iteration yields (state [S,V,5], pred [S,V,7,N], status [S,V], iters [S,V])."""
-    S, V, T, N = len(k0), table.shape[0], table.shape[1], ospec.N
-    state, pred = seed(table, k0, noise, N)
-    carry = [[None] * V for _ in range(S)]
+def step_inputs(table, k, state, pred, v, new_pred=None, before=()):
+    """Inputs of vehicle v's solve in one iteration of one scenario: (measured state [5], reference window [3,N], neighbours [V-1,3,N],
+    shifted warm start [7,N]).  table [V,T,7]: the scenario's plans, k its clock (k0 + t); state [V,5], pred [V,7,N]: before the step.
+    Sequential exchange: the vehicles in `before` (ranked before v) are read from new_pred [V,7,N], this step's predictions, unshifted."""
+    V, T, N = table.shape[0], table.shape[1], pred.shape[-1]
     adv = np.minimum(np.arange(N) + 1, N - 1)
+    kr = np.minimum(k + np.arange(N), T - 1)
+    nb = [new_pred[u][:3] if u in before else pred[u][:3][:, adv] for u in range(V) if u != v]
+    return state[v], table[v, kr, :3].T, np.stack(nb) if nb else np.zeros((0, 3, N)), pred[v][:, adv]
+
+
+def replay(ospec: MpcSpec, table, k0, noise, steps, dt=0.1, wb=2.5, carry_duals=True, opt=None, *, order=None, d=None, box=None,
+           table_of=None):
+    """Generator: after every iteration yields (state [S,V,5], pred [S,V,7,N], status [S,V], iters [S,V]).
+    order [S,V]: the sequential exchange, scenario s steps its vehicles in the order order[s] (None: Jacobi).  d [K,S,V,12]: the device's
+    disturbances (`Engine.loop_disturbance`) with box [2,2], the bounds of (a, w): the solver sees state + d[0:5], the plant takes
+    clip(input + d[5:7]) from the true state, d[7:12] is added to what it returns.  table_of [S]: `table` is a pool [P,V,T,7]."""
+    S, V, N = len(k0), table.shape[-3], ospec.N
+    state, pred = seed(table, k0, noise, N, table_of)
+    carry = [[None] * V for _ in range(S)]
+    kw = {} if opt is None else {"opt": opt}
     for t in range(steps):
         newp = pred.copy()
         status = np.zeros((S, V), int); iters = np.zeros((S, V), int)
         for s in range(S):
-            kr = np.minimum(k0[s] + t + np.arange(N), T - 1)
-            for v in range(V):
-                nb = np.stack([pred[s, u][:3][:, adv] for u in range(V) if u != v]) if V > 1 else np.zeros((0, 3, N))
-                w = pred[s, v][:, adv]
-                r = port.solve(ospec, state[s, v], table[v, kr, :3].T, nb, w.T.copy(), **({} if opt is None else {"opt": opt}), carry=carry[s][v] if carry_duals else None)
+            tab = table if table_of is None else table[table_of[s]]
+            done = []  # (stays empty under Jacobi)
+            for v in (range(V) if order is None else order[s]):
+                x0, ref, nb, w = step_inputs(tab, k0[s] + t, state[s], pred[s], v, newp[s], done)
+                dd = None if d is None else d[t, s, v]
+                r = port.solve(ospec, x0 if dd is None else x0 + dd[:5], ref, nb, w.T.copy(), **kw, carry=carry[s][v] if carry_duals else None)
                 carry[s][v] = r["carry"]
                 newp[s, v] = r["p"].T if r["status"] == 0 else w
-                state[s, v] = plant_step(state[s, v], newp[s, v][5:7, 0], dt, wb)
+                u = newp[s, v][5:7, 0] if dd is None else np.clip(newp[s, v][5:7, 0] + dd[5:7], box[:, 0], box[:, 1])
+                state[s, v] = plant_step(state[s, v], u, dt, wb)
+                if dd is not None:
+                    state[s, v] += dd[7:12]
                 status[s, v], iters[s, v] = r["status"], r["iters"]
+                if order is not None:
+                    done.append(v)
         pred = newp
         yield state.copy(), pred.copy(), status, iters

@@ -53,6 +53,7 @@ def _worker(rank, world, port, S, steps, q, V=4):
     from conflict_rez_amd import scenarios
     from conflict_rez_amd.distributed import VehicleShardedExchange
     from oracle import port as cport
+    from oracle.closed_loop import seed, step_inputs
     from oracle.dynamics import plant_step
     from oracle.mpc_nlp import MpcSpec
 
@@ -63,20 +64,18 @@ def _worker(rank, world, port, S, steps, q, V=4):
     k0, noise = scenarios.sample_scenarios(S, table, seed=9)
     ex = VehicleShardedExchange(V)
     mine = list(range(S)[ex.scenarios(S)])  # this rank's shard of the scenarios (all of them when world <= V)
-    N, T = spec.N, table.shape[1]
-    idx = lambda s, t: np.minimum(k0[s] + t + np.arange(N), T - 1)
-    state = {(s, v): table[v, k0[s], :5] + noise[s, v] for s in mine for v in ex.owned}
-    pred = {(s, v): table[v, idx(s, 0)].T.copy() for s in mine for v in ex.owned}
+    N = spec.N
+    state, pred = seed(table, k0, noise, N)  # (this rank steps and reads the rows of its scenarios and owned vehicles only)
     for t in range(steps):
-        local = torch.tensor(np.stack([[pred[(s, v)][:3] for v in ex.owned] for s in mine]))
+        local = torch.tensor(np.stack([[pred[s, v][:3] for v in ex.owned] for s in mine]))
         nbr = ex.neighbour_params(ex.gather(local)).numpy().reshape(len(mine), len(ex.owned), V - 1, 3, N)
         for si, s in enumerate(mine):
             for i, v in enumerate(ex.owned):
-                warm = advance_one_step(pred[(s, v)])
-                r = cport.solve(ospec, state[(s, v)], table[v, idx(s, t), :3].T.copy(), nbr[si, i], warm.T)
-                pred[(s, v)] = r["p"].T.copy() if r["status"] == 0 else warm
-                state[(s, v)] = plant_step(state[(s, v)], pred[(s, v)][5:7, 0], spec.dt, spec.wb)
-    q.put((rank, {k: v.copy() for k, v in state.items()}))
+                x0, ref, _, warm = step_inputs(table, k0[s] + t, state[s], pred[s], v)  # the neighbours come over the exchange
+                r = cport.solve(ospec, x0, ref, nbr[si, i], warm.T)
+                pred[s, v] = r["p"].T if r["status"] == 0 else warm
+                state[s, v] = plant_step(state[s, v], pred[s, v][5:7, 0], spec.dt, spec.wb)
+    q.put((rank, {(s, v): state[s, v].copy() for s in mine for v in ex.owned}))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -102,10 +101,9 @@ def test_vehicle_sharded_exchange_gloo(world, V):
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
-    # single-process replay of the same Jacobi iteration
+    # single-process replay of the same Jacobi iteration (cold multipliers in every solve, as the workers')
     from conflict_rez_amd import scenarios
-    from oracle import port as cport
-    from oracle.dynamics import plant_step
+    from oracle.closed_loop import replay
     from oracle.mpc_nlp import MpcSpec
 
     assert len(got) == S * V  # every (scenario, vehicle) stepped by exactly one rank
@@ -114,18 +112,7 @@ def test_vehicle_sharded_exchange_gloo(world, V):
     table, _ = scenarios.load_reference_table()
     table = table[:V]
     k0, noise = scenarios.sample_scenarios(S, table, seed=9)
-    N, T = spec.N, table.shape[1]
+    state = list(replay(ospec, table, k0, noise, steps, dt=spec.dt, wb=spec.wb, carry_duals=False))[-1][0]
     for s in range(S):
-        idx = lambda t: np.minimum(k0[s] + t + np.arange(N), T - 1)
-        state = [table[v, k0[s], :5] + noise[s, v] for v in range(V)]
-        pred = [table[v, idx(0)].T.copy() for v in range(V)]
-        for t in range(steps):
-            old = [p.copy() for p in pred]
-            for v in range(V):
-                nbr = np.stack([advance_one_step(old[u])[:3] for u in range(V) if u != v])
-                warm = advance_one_step(old[v])
-                r = cport.solve(ospec, state[v], table[v, idx(t), :3].T.copy(), nbr, warm.T)
-                pred[v] = r["p"].T.copy() if r["status"] == 0 else warm
-                state[v] = plant_step(state[v], pred[v][5:7, 0], spec.dt, spec.wb)
         for v in range(V):
-            assert np.array_equal(got[(s, v)], state[v]), (s, v)
+            assert np.array_equal(got[(s, v)], state[s, v]), (s, v)

@@ -252,49 +252,18 @@ def test_each_group_does_what_it_says(eng):
     assert np.abs(df[2:] - d2[2:, ..., 7:12]).max() < 1e-12 and np.abs(df[1] - d2[1, ..., 7:12]).max() > 1e-4
 
 
-def _replay(ospec, spec, table, k0, noise, d, order=None):
-    """oracle/closed_loop.replay's loop with the three injections and the device's d [K,S,V,12]; order [S,V]: the sequential exchange
-    (the ranks before v are read from this step's predictions, unshifted).  Yields (state, status, iters) after every step."""
-    from oracle import port
-    from oracle.closed_loop import seed
-    from oracle.dynamics import plant_step
-
-    S, V, T, N = len(k0), table.shape[0], table.shape[1], ospec.N
-    box = np.asarray(spec.bounds, float).reshape(6, 2)[4:6]
-    state, pred = seed(table, k0, noise, N)
-    carry = [[None] * V for _ in range(S)]
-    adv = np.minimum(np.arange(N) + 1, N - 1)
-    for t in range(len(d)):
-        newp = pred.copy()
-        status = np.zeros((S, V), int); iters = np.zeros((S, V), int)
-        for s in range(S):
-            kr = np.minimum(k0[s] + t + np.arange(N), T - 1)
-            seq = range(V) if order is None else order[s]
-            done = []
-            for v in seq:
-                nb = np.stack([newp[s, u][:3] if (order is not None and u in done) else pred[s, u][:3][:, adv] for u in range(V) if u != v])
-                w = pred[s, v][:, adv]
-                r = port.solve(ospec, state[s, v] + d[t, s, v, :5], table[v, kr, :3].T, nb, w.T.copy(), carry=carry[s][v])
-                carry[s][v] = r["carry"]
-                newp[s, v] = r["p"].T if r["status"] == 0 else w
-                u_app = np.clip(newp[s, v][5:7, 0] + d[t, s, v, 5:7], box[:, 0], box[:, 1])
-                state[s, v] = plant_step(state[s, v], u_app, spec.dt, spec.wb) + d[t, s, v, 7:12]
-                status[s, v], iters[s, v] = r["status"], r["iters"]
-                done.append(v)
-        pred = newp
-        yield state.copy(), status, iters
-
-
 @pytest.mark.parametrize("S,exchange", [(8, "jacobi"), (4, "sequential")])
 def test_against_the_host_replay(eng, ospec, S, exchange):
     """(10) S scenarios of the planned table (sample_scenarios(S, table, seed=3, spec)), 10 steps, base sigmas, noise seed 2024, against
-    the host replay with d downloaded from the device: status and iterations equal solve for solve, states within 1e-6 (the tolerances
+    the host replay (oracle/closed_loop.replay) with d downloaded from the device: status and iterations equal solve for solve, states within 1e-6 (the tolerances
     of test_pool_matches_oracle_replay); at least 85 % of the replay's solves converge."""
     from conflict_rez_amd import scenarios
+    from oracle.closed_loop import replay
 
     table, _ = scenarios.load_reference_table(kind="planned")
     k0, noise = scenarios.sample_scenarios(S, table, seed=3, spec=eng.spec)
     steps, V = 10, table.shape[0]
+    box = np.asarray(eng.spec.bounds, float).reshape(6, 2)[4:6]  # a, w
     order = _orders(S, V, 5) if exchange == "sequential" else None
     eng.loop_init(table, k0, noise)
     if order is not None:
@@ -307,7 +276,7 @@ def test_against_the_host_replay(eng, ospec, S, exchange):
         got.append(eng.loop_get())
     plain = _run(eng, ((table, k0, noise), {}), steps, "step", order, record=False)
     n_conv, worst = 0, 0.0
-    for t, (state, status, iters) in enumerate(_replay(ospec, eng.spec, table, k0, noise, d, order)):
+    for t, (state, _, status, iters) in enumerate(replay(ospec, table, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, order=order, d=d, box=box)):
         assert np.array_equal(got[t]["status"], status) and np.array_equal(got[t]["iters"], iters), t
         worst = max(worst, float(np.abs(got[t]["state"] - state).max()))
         n_conv += int((status == 0).sum())

@@ -254,16 +254,16 @@ def test_every_solve_of_the_bench_workload_against_the_port(ospec):
     (starts half a metre inside a neighbour's prediction), status 4 / 5 exits and the carried shift hint as they occur."""
     from conflict_rez_amd import engine, scenarios
     from oracle import port
+    from oracle.closed_loop import step_inputs
 
     spec = scenarios.parking_lot_spec()
     table, _ = scenarios.load_reference_table(kind="planned")
     S, steps = 256, 8
     k0, noise = scenarios.sample_scenarios(1024, table, seed=2024, spec=spec)
     k0, noise = k0[:S], noise[:S]
-    V, T, N = table.shape[0], table.shape[1], spec.N
+    V, N = table.shape[0], spec.N
     e = engine.Engine(spec, max_batch=S * V)
     e.loop_init(table, k0, noise)
-    adv = np.minimum(np.arange(N) + 1, N - 1)
     carry = [[None] * V for _ in range(S)]
     n = n_resto = 0
     seen = set()
@@ -274,11 +274,9 @@ def test_every_solve_of_the_bench_workload_against_the_port(ospec):
         g1 = e.loop_get()
         st, it, p1 = g1["status"].reshape(S, V), g1["iters"].reshape(S, V), g1["pred"].reshape(S, V, 7, N)
         for s in range(S):
-            kr = np.minimum(k0[s] + t + np.arange(N), T - 1)
             for v in range(V):
-                nb = np.stack([pred[s, u][:3][:, adv] for u in range(V) if u != v])
-                w = pred[s, v][:, adv]
-                r = port.solve(ospec, state[s, v], table[v, kr, :3].T, nb, w.T.copy(), carry=carry[s][v])
+                x0, ref, nb, w = step_inputs(table, k0[s] + t, state[s], pred[s], v)
+                r = port.solve(ospec, x0, ref, nb, w.T.copy(), carry=carry[s][v])
                 carry[s][v] = r["carry"]
                 assert (r["status"], r["iters"]) == (int(st[s, v]), int(it[s, v])), (t, s, v, r["status"], r["iters"], st[s, v], it[s, v])
                 if r["status"] == 0:  # (measured worst case over the 8,192 solves: 1.9e-6, at an input w where v ~ 0 -- TOL_U above; 1e-6 held until the

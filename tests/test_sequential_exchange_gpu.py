@@ -65,16 +65,16 @@ def test_every_sequential_solve_of_the_bench_workload_against_the_port(ospec):
     per (s, v).  Equal status and iteration count of every solve, converged predictions to 1e-5 (the Jacobi test's tolerance)."""
     from conflict_rez_amd import engine
     from oracle import port
+    from oracle.closed_loop import step_inputs
 
     spec, table, k0, noise = _bench_workload(128)
     S, steps = len(k0), 8
-    V, T, N = table.shape[0], table.shape[1], spec.N
+    V = table.shape[0]
     order = _orders(S, V, seed=5)
     rank = np.argsort(order, axis=1)
     e = engine.Engine(spec, max_batch=S * V)
     e.loop_init(table, k0, noise)
     e.loop_set_order(order)
-    adv = np.minimum(np.arange(N) + 1, N - 1)
     carry = [[None] * V for _ in range(S)]
     n, worst, seen = 0, 0.0, set()
     for t in range(steps):
@@ -83,10 +83,9 @@ def test_every_sequential_solve_of_the_bench_workload_against_the_port(ospec):
         g1 = e.loop_get()
         state, pred, p1 = g0["state"], g0["pred"], g1["pred"]
         for s in range(S):
-            kr = np.minimum(k0[s] + t + np.arange(N), T - 1)
             for v in order[s]:
-                nb = np.stack([p1[s, u][:3] if rank[s, u] < rank[s, v] else pred[s, u][:3][:, adv] for u in range(V) if u != v])
-                r = port.solve(ospec, state[s, v], table[v, kr, :3].T, nb, pred[s, v][:, adv].T.copy(), carry=carry[s][v])
+                x0, ref, nb, w = step_inputs(table, k0[s] + t, state[s], pred[s], v, p1[s], order[s][: rank[s, v]])
+                r = port.solve(ospec, x0, ref, nb, w.T.copy(), carry=carry[s][v])
                 carry[s][v] = r["carry"]
                 got = (int(g1["status"][s, v]), int(g1["iters"][s, v]))
                 assert (r["status"], r["iters"]) == got, (t, s, int(v), r["status"], r["iters"], got)

@@ -1,24 +1,45 @@
 #!/usr/bin/env python3
-"""Two builds of the library on the same seeded MPC batch (cold solves and a short closed loop): are the results equal bit for bit?
+"""Two builds of the library on the same seeded MPC batch: are the results equal bit for bit?  Cold solves; a Jacobi persistent run of 6
+steps; 3 `loop_step`s, Jacobi and under seeded orders; a sequential persistent run of 4; a disturbed persistent run of 4 (the sigmas of
+tests/disturbance_binding.SIGMA).  Every loop is compared at its end point and over its record.
 usage: python tools/gpu_lib_compare.py <libA.so> <libB.so> [scenarios]     (each library runs in a process of its own)"""
 import os, subprocess, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from conflict_rez_amd import engine, scenarios
+    from disturbance_binding import SIGMA
     lib, S, out = sys.argv[2], int(sys.argv[3]), sys.argv[4]
     engine._lib = engine.load_library(lib)
     spec = scenarios.parking_lot_spec()
     table, _ = scenarios.load_reference_table(kind="planned")
     k0, noise = scenarios.sample_scenarios(S, table, seed=11)  # raw draws: restorations, status 4 / 5 among them
     x0, ref, nbr, zu = scenarios.mpc_batch_from_table(spec, table, k0, noise)
+    V = table.shape[0]
     e = engine.Engine(spec, max_batch=len(x0))
     r = e.solve(x0, ref, nbr, zu, want_duals=False)
-    e.loop_init(table, k0, noise)
-    its = e.loop_run(6)
-    g = e.loop_get()
-    np.savez(out, status=r["status"], iters=r["iters"], zu=r["zu"], ms=r["solve_ms"], loop_status=g["status"], loop_iters=g["iters"], loop_pred=g["pred"], loop_state=g["state"], its=its)
+    res = dict(status=r["status"], iters=r["iters"], zu=r["zu"], ms=r["solve_ms"])
+
+    def loop(tag, setup, go):  # one closed loop from the same start; its end point and record under <tag>_*
+        e.loop_init(table, k0, noise)
+        setup()
+        e.loop_record(8)
+        res[tag + "_its"] = go() or 0
+        res.update({f"{tag}_{k}": v for k, v in {**e.loop_get(), **e.loop_history()}.items()})
+
+    def three_steps():
+        for _ in range(3):
+            e.loop_step()
+
+    order = np.stack([np.random.default_rng(5).permutation(V) for _ in range(S)]).astype(np.int32)
+    loop("loop", lambda: None, lambda: e.loop_run(6))
+    loop("step", lambda: None, three_steps)
+    loop("seq", lambda: e.loop_set_order(order), lambda: e.loop_run(4))
+    loop("seqstep", lambda: e.loop_set_order(order), three_steps)
+    loop("dist", lambda: e.loop_set_disturbance(2024, **SIGMA), lambda: e.loop_run(4))
+    np.savez(out, **res)
     sys.exit(0)
 S = int(sys.argv[3]) if len(sys.argv) > 3 else 256
 res = []
@@ -29,7 +50,9 @@ with tempfile.TemporaryDirectory() as d:
         res.append(dict(np.load(out)))
 a, b = res
 print(f"{4 * S} cold solves: iterations {int(a['iters'].sum())} / {int(b['iters'].sum())}, kernel {float(a['ms']):.2f} / {float(b['ms']):.2f} ms")
-for k in ("status", "iters", "zu", "loop_status", "loop_iters", "loop_pred", "loop_state"):
+for k in a:
+    if k == "ms" or k.endswith("_its"):
+        continue
     same = np.array_equal(a[k], b[k])
     print(f"  {k}: {'equal bit for bit' if same else 'DIFFERENT: %d entries, max %.3e' % (int((a[k] != b[k]).sum()), float(np.abs(a[k].astype(float) - b[k].astype(float)).max()))}")
-print("closed loop iterations", int(a["its"]), int(b["its"]))
+print("closed loop iterations", int(a["loop_its"]), int(b["loop_its"]))
