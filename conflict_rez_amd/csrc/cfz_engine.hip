@@ -9,6 +9,7 @@
 //                  (scenario, vehicle, iteration) work items, hand-offs between workgroups at agent scope
 //   loop_kernel_seq  the same with the sequential exchange of cfz_loop_set_order (one body: cfz_loop_body.inl)
 //   loop_kernel_dist, loop_kernel_seq_dist  the same two with the disturbances of cfz_loop_set_disturbance (cfz_disturb.inl)
+//   loop_kernel_comm, loop_kernel_seq_comm  the same two with the lossy exchange of cfz_loop_set_comm (cfz_comm.inl) and disturbances
 //   loop_prep      stepwise closed loop (cfz_loop_step): parameters and shifted warm start of every vehicle from the
 //                  previous predictions (reference vehicle_follower.py:432-476, 636-637), the measurement under a disturbance
 //   loop_post      stepwise closed loop: read-back or shift fallback, plant integration, clock
@@ -21,7 +22,7 @@
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
 // (loop_release).  cfz_loop_step is loop_round (prep, solve, post) once for Jacobi or V times for the sequential exchange;
-// cfz_loop_run picks its kernel from kLoopKernel[disturbed][sequential].
+// cfz_loop_run picks its kernel from kLoopKernel[setting][sequential].
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -39,6 +40,7 @@
 #include "cfz_solver.inl"
 #include "cfz_audit.inl"
 #include "cfz_disturb.inl"
+#include "cfz_comm.inl"
 #include "cfz_common.h"
 
 thread_local std::string cfz_g_err;  // cfz_last_error(); shared with cfz_planning.hip (cfz_common.h)
@@ -100,8 +102,12 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
 // plan[T][7] at clock k0, clamped at the last sample; its own prediction own[7][N] and the neighbours' advanced one step
 // (_adv_onestep, :413-426).  others[V][rows][N] holds x, y, psi of the scenario's V vehicles in the first three of `rows` rows; v is
 // the instance's vehicle.  rank[V] (NULL: none) with r: the vehicles ranked before r are read as they stand.
+// cm (cfz_loop_set_comm; cm.p_drop NULL: none, every neighbour's newest prediction from `others`): the lossy exchange of
+// cfz_comm.inl in iteration t of scenario s.  Neighbour u is read from the message the age rule gives, in its slot of the ring
+// (rows of 7), at the row comm_row gives; with no loss that is the slot and the row read without it.
 __device__ inline void prep_stage(int b, int k, int N, int T, int V, int v, const double *plan, int k0, const double *own,
-                                  const double *others, int rows, const int32_t *rank, int r, double *ref, double *nbr, double *zu) {
+                                  const double *others, int rows, const int32_t *rank, int r, const cfz::CommArgs &cm, int s, int t,
+                                  double *ref, double *nbr, double *zu) {
   const int ka = (k + 1 < N) ? k + 1 : N - 1;
   int kr = k0 + k; if (kr > T - 1) kr = T - 1;
   for (int c = 0; c < 3; ++c) ref[((size_t)b * 3 + c) * N + k] = plan[(size_t)kr * 7 + c];
@@ -109,8 +115,16 @@ __device__ inline void prep_stage(int b, int k, int N, int T, int V, int v, cons
   int o = 0;
   for (int u = 0; u < V; ++u) {
     if (u == v) continue;
-    const int ku = (rank && rank[u] < r) ? k : ka;
-    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + o) * 3 + c) * N + k] = others[((size_t)u * rows + c) * N + ku];
+    const bool earlier = rank && rank[u] < r;
+    const double *src = others + (size_t)u * rows * N;
+    int a = 0;
+    if (cm.p_drop) {
+      const int want = cfz::comm_want(t, earlier);
+      a = cfz::comm_age(cm, s, v, u, want);
+      src = cm.ring + (size_t)cfz::comm_slot(want - a, cm.max_age) * cm.slot_stride + ((size_t)s * V + u) * 7 * N;
+    }
+    const int ku = cfz::comm_row(k, earlier ? 0 : 1, cm.compensate, a, N);
+    for (int c = 0; c < 3; ++c) nbr[(((size_t)b * (V - 1) + o) * 3 + c) * N + k] = src[(size_t)c * N + ku];
     ++o;
   }
 }
@@ -120,9 +134,10 @@ __device__ inline void prep_stage(int b, int k, int N, int T, int V, int v, cons
 // v = xperm[s][r]; the neighbours ranked before it have already posted this step's prediction to `pred`, which starts at this
 // step's time and is read as it stands; the others' (and v's own warm start) are the previous step's, advanced.
 // dz (cfz_loop_set_disturbance; dz.sigma NULL: none): the solver's x0 is the measurement, state + d[0:5] of this `step`.
+// cm (cfz_loop_set_comm; cm.p_drop NULL: none): the neighbours come from the ring of messages by the age rule (prep_stage).
 __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, const int32_t *table_of, const int32_t *kidx,
                           const double *pred, const double *state, double *x0, double *ref, double *nbr,
-                          double *zu, int r, const int32_t *xperm, const int32_t *xrank, cfz::DisturbArgs dz, int step) {
+                          double *zu, int r, const int32_t *xperm, const int32_t *xrank, cfz::DisturbArgs dz, int step, cfz::CommArgs cm) {
   const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= (long)(xperm ? S : S * V) * N) return;
   const int k = (int)(tid % N);
@@ -131,7 +146,7 @@ __global__ void loop_prep(int S, int V, int N, int T, const double *ref_table, c
   const int s = b / V, v = b - s * V;
   if (k < 5) x0[b * 5 + k] = dz.sigma ? cfz::disturb_add(state[b * 5 + k], cfz::disturb_value(dz, s, v, step, k)) : state[b * 5 + k];
   prep_stage(b, k, N, T, V, v, ref_table + ((size_t)table_of[s] * V + v) * T * 7, kidx[s], pred + (size_t)b * 7 * N,
-             pred + (size_t)s * V * 7 * N, 7, xrank ? xrank + (size_t)s * V : nullptr, r, ref, nbr, zu);
+             pred + (size_t)s * V * 7 * N, 7, xrank ? xrank + (size_t)s * V : nullptr, r, cm, s, step, ref, nbr, zu);
 }
 
 __global__ void advance_clock(int S, int K, int32_t *kidx) {
@@ -147,10 +162,11 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
 // [w_lo, w_hi]; the plant starts from the true state and d[7:12] is added to what it returns; the record keeps both.
 // carry (NULL: none; cfz_vsl_step): the carry flag of the next iteration, a vehicle whose solve converged starts its next one from
 // these multipliers.
+// msg (NULL: none; cfz_loop_set_comm): this iteration's slot [S][V][7][N] of the ring of messages, which takes the posted prediction too.
 __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
                           const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
                           int32_t *rec_si, int r, const int32_t *xperm, cfz::DisturbArgs dz, int step, double a_lo, double a_hi,
-                          double w_lo, double w_hi, int32_t *carry) {
+                          double w_lo, double w_hi, int32_t *carry, double *msg) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (xperm ? S : S * V)) return;
   if (xperm) b = b * V + xperm[b * V + r];
@@ -161,6 +177,8 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
     for (int c = 0; c < 7; ++c)
       for (int k = 0; k + 1 < N; ++k) pb[c * N + k] = pb[c * N + k + 1];
   }
+  if (msg)
+    for (int i = 0; i < 7 * N; ++i) msg[(size_t)b * 7 * N + i] = pb[i];
   double z[5], out[5];
   for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
   double a0 = pb[5 * N], w0 = pb[6 * N];
@@ -199,7 +217,7 @@ __global__ void vs_prep(int S, int V, int n_own, int N, int T, const int32_t *ow
   const int s = b / n_own, o = b - s * n_own;
   if (k < 5) x0[b * 5 + k] = state[b * 5 + k];
   prep_stage(b, k, N, T, V, own[o], table + (size_t)o * T * 7, k0[s] + t, pred + (size_t)b * 7 * N, allpred + (size_t)s * V * 3 * N, 3,
-             nullptr, 0, ref, nbr, zu);
+             nullptr, 0, cfz::comm_none(), s, t, ref, nbr, zu);
 }
 
 // Longest-processing-time-first dispatch order for the next step: instances sorted by the iteration count of
@@ -262,7 +280,8 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(cons
                                                         int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
                                                         double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
                                                         double *rec, int32_t *rec_si) {
-  constexpr bool kSeq = false, kDist = false;
+  constexpr bool kSeq = false, kDist = false, kComm = false;
+  const cfz::CommArgs cm = cfz::comm_none();
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
   const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
   const int step0 = 0;
@@ -275,7 +294,8 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(
                                                             int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
                                                             double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
                                                             double *rec, int32_t *rec_si, const int32_t *xperm, const int32_t *xrank) {
-  constexpr bool kSeq = true, kDist = false;
+  constexpr bool kSeq = true, kDist = false, kComm = false;
+  const cfz::CommArgs cm = cfz::comm_none();
   const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
   const int step0 = 0;
 #include "cfz_loop_body.inl"
@@ -290,7 +310,8 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_dist
                                                              int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
                                                              double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
                                                              double *rec, int32_t *rec_si, cfz::DisturbArgs dz, int step0) {
-  constexpr bool kSeq = false, kDist = true;
+  constexpr bool kSeq = false, kDist = true, kComm = false;
+  const cfz::CommArgs cm = cfz::comm_none();
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
 #include "cfz_loop_body.inl"
 }
@@ -302,13 +323,52 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
                                                                  double *stats, int32_t *iter_sum, double *wst, int wst_stride,
                                                                  int prio_lag, double *rec, int32_t *rec_si, const int32_t *xperm,
                                                                  const int32_t *xrank, cfz::DisturbArgs dz, int step0) {
-  constexpr bool kSeq = true, kDist = true;
+  constexpr bool kSeq = true, kDist = true, kComm = false;
+  const cfz::CommArgs cm = cfz::comm_none();
 #include "cfz_loop_body.inl"
 }
 
-// the persistent kernel of a setting, [disturbed][sequential]
-const void *const kLoopKernel[2][2] = {{(const void *)loop_kernel, (const void *)loop_kernel_seq},
-                                       {(const void *)loop_kernel_dist, (const void *)loop_kernel_seq_dist}};
+// The lossy exchange of cfz_loop_set_comm (kComm; cfz_comm.inl): cm is the setting, its ring of messages stands in for the parity
+// pair `pred` (unused here), indexed by the absolute iteration step0 + t.  Compiled with kDist, so that noise and loss combine
+// without further variants; with no noise set, dz is an all-zero sigma, which is bit-neutral.  Kernels of their own again: the
+// four above keep their code.  The release / acquire edges are those of the kernels above: the older slots a reader may take were
+// published by earlier iterations of the same scenario, which the chain of edges to this item covers.
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_comm(const KArgs *__restrict__ ka, int S, int V, int K, int T,
+                                                             const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
+                                                             int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
+                                                             int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
+                                                             double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
+                                                             double *rec, int32_t *rec_si, cfz::DisturbArgs dz, int step0,
+                                                             cfz::CommArgs cm) {
+  constexpr bool kSeq = false, kDist = true, kComm = true;
+  const int32_t *const xperm = nullptr, *const xrank = nullptr;
+#include "cfz_loop_body.inl"
+}
+
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_comm(const KArgs *__restrict__ ka, int S, int V, int K, int T,
+                                                                 const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
+                                                                 int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
+                                                                 int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
+                                                                 double *stats, int32_t *iter_sum, double *wst, int wst_stride,
+                                                                 int prio_lag, double *rec, int32_t *rec_si, const int32_t *xperm,
+                                                                 const int32_t *xrank, cfz::DisturbArgs dz, int step0, cfz::CommArgs cm) {
+  constexpr bool kSeq = true, kDist = true, kComm = true;
+#include "cfz_loop_body.inl"
+}
+
+// the persistent kernel of a setting, [0 plain, 1 disturbed, 2 lossy exchange (with or without disturbance)][sequential]
+const void *const kLoopKernel[3][2] = {{(const void *)loop_kernel, (const void *)loop_kernel_seq},
+                                       {(const void *)loop_kernel_dist, (const void *)loop_kernel_seq_dist},
+                                       {(const void *)loop_kernel_comm, (const void *)loop_kernel_seq_comm}};
+
+// delivered[K][S][V][V]: the delivery bits of messages [tau0, tau0 + K) (cfz_loop_comm), receiver before sender, diagonal 1; one thread
+// each, through the function the loop uses
+__global__ void comm_fill(cfz::CommArgs cm, int S, int V, int tau0, long n, int32_t *delivered) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int u = (int)(i % V), v = (int)((i / V) % V), s = (int)((i / ((long)V * V)) % S), k = (int)(i / ((long)V * V * S));
+  delivered[i] = u == v ? 1 : (cfz::comm_delivered(cm.seed, cm.stream[s], v, u, tau0 + k, cm.p_drop[s]) ? 1 : 0);
+}
 
 // d[K][S][V][12]: the disturbances of steps [t0, t0 + K) (cfz_loop_disturbance), one thread each, through the function the loop uses
 __global__ void disturb_fill(cfz::DisturbArgs dz, int S, int V, int t0, long n, double *d) {
@@ -570,6 +630,14 @@ struct cfz_handle {
     void *dz_buf = nullptr;
     uint64_t dz_seed = 0;
     bool dz_on = false;
+    // lossy exchange (cfz_loop_set_comm; cm_on false: none): one device buffer cm_buf = p_drop[S] | zero sigma[12] | zero level[S] |
+    // stream[S] (uint32), the zero setting being what the comm kernels take for dz while no disturbance is set; cm_ring[D][S][V][7][N]
+    // the ring of messages, D = cm_max_age + 2; cm_tau_on the message history starts at
+    void *cm_buf = nullptr;
+    double *cm_ring = nullptr;
+    uint64_t cm_seed = 0;
+    int cm_max_age = 0, cm_compensate = 0, cm_tau_on = 0, cm_ring_slots = 0;
+    bool cm_on = false;
     // persistent loop
     double *pred2 = nullptr, *scratch = nullptr;
     int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
@@ -909,7 +977,7 @@ int cfz_vsl_step(cfz_handle *h, int S, int V, int n_own, const int32_t *d_own, i
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, d_status, d_iters, d_stats, false, st)) return -1;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, S, n_own, N, h->ks.dt, h->ks.wb, kPlantSubsteps, d_status,
                      nullptr, h->zu, d_pred, d_state, nullptr, nullptr, nullptr, 0, nullptr, cfz::DisturbArgs{0, nullptr, nullptr, nullptr}, 0,
-                     0.0, 0.0, 0.0, 0.0, d_carry);
+                     0.0, 0.0, 0.0, 0.0, d_carry, nullptr);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -978,10 +1046,15 @@ void disturb_free(cfz_handle *h) {
   h->lp.dz_on = false; h->lp.dz_seed = 0;
 }
 
-// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance setting and the
+void comm_free(cfz_handle *h) {
+  dev_free(h->lp.cm_buf); dev_free(h->lp.cm_ring);
+  h->lp.cm_on = false; h->lp.cm_ring_slots = 0;
+}
+
+// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance and comm setting and the
 // persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
 void loop_release(cfz_handle *h) {
-  record_free(h); exchange_free(h); disturb_free(h);
+  record_free(h); exchange_free(h); disturb_free(h); comm_free(h);
   dev_free(h->lp.ref_table); dev_free(h->lp.table_of); dev_free(h->lp.pred); dev_free(h->lp.state); dev_free(h->lp.kidx); dev_free(h->lp.order);
   dev_free(h->lp.pred2); dev_free(h->lp.scratch); dev_free(h->lp.queue); dev_free(h->lp.ctrl); dev_free(h->lp.done); dev_free(h->lp.iter_sum);
   h->lp = cfz_handle::Loop();
@@ -992,6 +1065,27 @@ cfz::DisturbArgs disturb_args(const cfz_handle *h) {
   if (!h->lp.dz_on) return {0, nullptr, nullptr, nullptr};
   const double *f = static_cast<const double *>(h->lp.dz_buf);
   return {h->lp.dz_seed, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
+}
+
+// the comm setting in force as the kernels take it (p_drop NULL: none)
+cfz::CommArgs comm_args(const cfz_handle *h) {
+  if (!h->lp.cm_on) return cfz::comm_none();
+  const double *f = static_cast<const double *>(h->lp.cm_buf);
+  const size_t S = (size_t)h->lp.S;
+  return {h->lp.cm_seed, f, reinterpret_cast<const uint32_t *>(f + 2 * S + cfz::kDisturbN), h->lp.cm_ring, h->lp.cm_max_age, h->lp.cm_compensate,
+          h->lp.cm_tau_on, S * (h->ks.n_nbr + 1) * 7 * h->ks.N};
+}
+
+// what the comm kernels take for dz: the disturbance in force, or the all-zero setting of cm_buf
+cfz::DisturbArgs comm_disturb_args(const cfz_handle *h) {
+  if (h->lp.dz_on) return disturb_args(h);
+  const double *f = static_cast<const double *>(h->lp.cm_buf) + h->lp.S;
+  return {0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
+}
+
+// the slot of message tau in the ring (comm on)
+double *comm_message(const cfz_handle *h, int tau) {
+  return h->lp.cm_ring + (size_t)cfz::comm_slot(tau, h->lp.cm_max_age) * comm_args(h).slot_stride;
 }
 
 // room for `steps` more steps in the record (or no record at all)
@@ -1015,15 +1109,16 @@ int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const 
   double *rec; int32_t *rec_si;
   record_slice(h, rec, rec_si);
   const cfz::DisturbArgs dz = disturb_args(h);
+  const cfz::CommArgs cm = comm_args(h);
   const double *bd = h->ks.bounds;  // (the input box: a in [bd[8], bd[9]], w in [bd[10], bd[11]])
   const long nt = (long)n_inst * N;
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->lp.T, h->lp.ref_table,
-                     h->lp.table_of, h->lp.kidx, h->lp.pred, h->lp.state, h->x0, h->ref, h->nbr, h->zu, r, xperm, xrank, dz, h->lp.steps_done);
+                     h->lp.table_of, h->lp.kidx, h->lp.pred, h->lp.state, h->x0, h->ref, h->nbr, h->zu, r, xperm, xrank, dz, h->lp.steps_done, cm);
   HIP_OK(hipGetLastError());
   if (launch_solve(h, S * V, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, dispatch, 1, n_inst)) return -1;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
                      h->status, h->iters, h->zu, h->lp.pred, h->lp.state, h->lp.kidx, rec, rec_si, r, xperm, dz, h->lp.steps_done, bd[8], bd[9], bd[10],
-                     bd[11], nullptr);
+                     bd[11], nullptr, h->lp.cm_on ? comm_message(h, h->lp.steps_done) : nullptr);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1080,7 +1175,7 @@ int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *table
     if (tof[s] < 0 || tof[s] >= P) return fail("table_of[s] outside [0, P)");
   }
   HIP_OK(hipSetDevice(h->device));
-  loop_release(h);  // record, exchange order and disturbance included: back to the undisturbed Jacobi loop at step 0
+  loop_release(h);  // record, exchange order, disturbance and comm setting included: back to the undisturbed, lossless Jacobi loop at step 0
   h->lp.S = S; h->lp.T = T; h->lp.P = P;
   const size_t B = (size_t)S * V;
   HIP_OK(hipMalloc(&h->lp.ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->lp.pred, B * 7 * N * 8));
@@ -1238,6 +1333,56 @@ int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d) {
   return 0;
 }
 
+int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop, int max_age, int compensate, const uint32_t *stream) {
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (!p_drop) { h->lp.cm_on = false; return 0; }  // off: the kernels without it
+  if (max_age < 1 || max_age > CFZ_MAX_AGE) return fail("max_age outside 1..CFZ_MAX_AGE");
+  if (compensate != 0 && compensate != 1) return fail("compensate must be 0 or 1");
+  const int S = h->lp.S, V = h->ks.n_nbr + 1, N = h->ks.N;
+  for (int s = 0; s < S; ++s)
+    if (!(p_drop[s] >= 0.0 && p_drop[s] <= 1.0)) return fail("a p_drop is outside [0, 1] or not finite");
+  // p_drop[S] | zero sigma[12] | zero level[S] | stream[S]
+  std::vector<double> f(2 * (size_t)S + cfz::kDisturbN, 0.0);
+  std::copy(p_drop, p_drop + S, f.begin());
+  std::vector<uint32_t> id((size_t)S);
+  for (int s = 0; s < S; ++s) id[s] = stream ? stream[s] : (uint32_t)s;
+  const size_t slot = (size_t)S * V * 7 * N;
+  if (h->lp.cm_ring_slots != max_age + 2) {
+    double *ring = nullptr;
+    HIP_OK(hipMalloc(&ring, (size_t)(max_age + 2) * slot * 8));
+    dev_free(h->lp.cm_ring);
+    h->lp.cm_ring = ring; h->lp.cm_ring_slots = max_age + 2;
+  }
+  if (!h->lp.cm_buf) HIP_OK(hipMalloc(&h->lp.cm_buf, f.size() * 8 + id.size() * 4));
+  HIP_OK(hipMemcpy(h->lp.cm_buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(static_cast<char *>(h->lp.cm_buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  h->lp.cm_seed = seed; h->lp.cm_max_age = max_age; h->lp.cm_compensate = compensate; h->lp.cm_on = true;
+  // history restarts at the message standing in pred, that of the last iteration done
+  h->lp.cm_tau_on = h->lp.steps_done - 1;
+  HIP_OK(hipMemcpy(comm_message(h, h->lp.cm_tau_on), h->lp.pred, slot * 8, hipMemcpyDeviceToDevice));
+  return 0;
+}
+
+int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered) {
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (!h->lp.cm_on) return fail("no lossy exchange is set (cfz_loop_set_comm)");
+  if (tau0 < 0 || K < 1 || !delivered) return fail("tau0 must not be negative, K must be positive and delivered not NULL");
+  HIP_OK(hipSetDevice(h->device));
+  const int S = h->lp.S, V = h->ks.n_nbr + 1;
+  const size_t n = (size_t)K * S * V * V;
+  if (n > ((size_t)1 << 31)) return fail("window too large");
+  if (arena_reset(h->arena)) return -1;
+  int32_t *dd = nullptr;
+  ARENA_ALLOC(h->arena, dd, n * 4);
+  hipLaunchKernelGGL(comm_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, comm_args(h), S, V, tau0, (long)n, dd);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(delivered, dd, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
 int cfz_loop_step(cfz_handle *h) {
   if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   if (record_room(h, 1)) return -1;
@@ -1284,8 +1429,8 @@ int cfz_loop_run(cfz_handle *h, int K) {
   int ncu = 0;
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
-  const bool seq = h->lp.xperm != nullptr, dist = h->lp.dz_on;
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kLoopKernel[dist][seq], cfz::kNL, h->lds_bytes));
+  const bool seq = h->lp.xperm != nullptr, dist = h->lp.dz_on, comm = h->lp.cm_on;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kLoopKernel[comm ? 2 : dist][seq], cfz::kNL, h->lds_bytes));
   per_cu = std::min(per_cu, h->blocks_per_cu);  // the 2 KiB LDS granules (cfz_create): what the hardware really keeps resident
   if (per_cu < 1) return fail("loop kernel does not fit on a CU");
   // one workgroup per resident slot: more would only queue behind them (any workgroup can serve any item, so a surplus
@@ -1308,8 +1453,8 @@ int cfz_loop_run(cfz_handle *h, int K) {
     if (h->lp.queue) (void)hipFree(h->lp.queue);
     HIP_OK(hipMalloc(&h->lp.queue, qwords * 4)); h->lp.queue_cap = (int)qwords;
   }
-  // parity 0 of the double buffer <- current predictions; queue <- all items of iteration 0
-  HIP_OK(hipMemcpyAsync(h->lp.pred2, h->lp.pred, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
+  // parity 0 of the double buffer <- current predictions (the ring of messages already holds them); queue <- all items of iteration 0
+  if (!comm) HIP_OK(hipMemcpyAsync(h->lp.pred2, h->lp.pred, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
   HIP_OK(hipMemsetAsync(h->lp.queue, 0, 2 * (size_t)K * 4, h->stream));
   HIP_OK(hipMemsetAsync(h->lp.queue + 2 * K, 0xff, total * 4, h->stream));
   {
@@ -1330,13 +1475,15 @@ int cfz_loop_run(cfz_handle *h, int K) {
   record_slice(h, rec, rec_si);
   const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
   const cfz::DisturbArgs dz = disturb_args(h);
-  // the four kernels share their arguments up to the record; `tail` is the exchange order and / or the disturbance setting
+  // the six kernels share their arguments up to the record; `tail` is the exchange order, the disturbance and the comm setting
   auto launch = [&](auto kernel, auto... tail) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->lp.T, h->lp.ref_table, h->lp.table_of,
                        h->lp.kidx, 0, h->lp.pred2, h->lp.state, h->lp.scratch, h->lp.queue, h->lp.ctrl, h->lp.done, h->status, h->iters, h->stats, h->lp.iter_sum,
                        h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, tail...);
   };
-  if (dist && seq) launch(loop_kernel_seq_dist, h->lp.xperm, h->lp.xrank, dz, h->lp.steps_done);
+  if (comm && seq) launch(loop_kernel_seq_comm, h->lp.xperm, h->lp.xrank, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
+  else if (comm) launch(loop_kernel_comm, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
+  else if (dist && seq) launch(loop_kernel_seq_dist, h->lp.xperm, h->lp.xrank, dz, h->lp.steps_done);
   else if (dist) launch(loop_kernel_dist, dz, h->lp.steps_done);
   else if (seq) launch(loop_kernel_seq, h->lp.xperm, h->lp.xrank);
   else launch(loop_kernel);
@@ -1344,8 +1491,8 @@ int cfz_loop_run(cfz_handle *h, int K) {
   if (h->lp.rec) h->lp.rec_used += K;
   h->lp.steps_done += K;
   HIP_OK(hipEventRecord(h->ev1, h->stream));
-  // predictions after K iterations live in parity K%2; advance the scenario clocks by K
-  HIP_OK(hipMemcpyAsync(h->lp.pred, h->lp.pred2 + (size_t)(K & 1) * B * 7 * N, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
+  // predictions after K iterations live in parity K%2 (comm: in the newest message's slot); advance the scenario clocks by K
+  HIP_OK(hipMemcpyAsync(h->lp.pred, comm ? comm_message(h, h->lp.steps_done - 1) : h->lp.pred2 + (size_t)(K & 1) * B * 7 * N, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
   hipLaunchKernelGGL(advance_clock, dim3((S + 255) / 256), dim3(256), 0, h->stream, S, K, h->lp.kidx);
   HIP_OK(hipGetLastError());
   if (const char *dbg = std::getenv("CFZ_LOOP_WATCHDOG")) {

@@ -1,7 +1,9 @@
-// cfz_loop_body.inl -- the body of the persistent closed-loop kernels loop_kernel, loop_kernel_seq and their disturbed variants
-// loop_kernel_dist, loop_kernel_seq_dist (cfz_engine.hip), included inside all four.  The including kernel defines `constexpr bool
-// kSeq` and the exchange order arrays `xperm`, `xrank` (nullptr for the Jacobi kernels), `constexpr bool kDist` and the disturbance
-// setting `dz` with the step count `step0` (unused constants in the undisturbed kernels); everything else is the kernel's arguments.
+// cfz_loop_body.inl -- the body of the persistent closed-loop kernels loop_kernel, loop_kernel_seq, their disturbed variants
+// loop_kernel_dist, loop_kernel_seq_dist and the lossy-exchange variants loop_kernel_comm, loop_kernel_seq_comm (cfz_engine.hip),
+// included inside all six.  The including kernel defines `constexpr bool kSeq` and the exchange order arrays `xperm`, `xrank`
+// (nullptr for the Jacobi kernels), `constexpr bool kDist` and the disturbance setting `dz` with the step count `step0` (unused
+// constants in the undisturbed kernels), `constexpr bool kComm` and the comm setting `cm` (an unused constant in the kernels
+// without it); everything else is the kernel's arguments.
   extern __shared__ double smem[];
   const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
   const int N = sp.N, nn = sp.n_nbr, B = S * V, tid = threadIdx.x, lane = tid & 63;
@@ -64,10 +66,25 @@
       if (t <= CFZ_LD(&ctrl[0]) + prio_lag) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
     }
     const int s = b / V, v = b - s * V;
-    const double *pin = pred + (size_t)(t & 1) * B * 7 * N;   // predictions after iteration t-1
-    double *pout = pred + (size_t)((t + 1) & 1) * B * 7 * N;
+    // kComm: the ring of messages indexed by the absolute iteration instead of the parity pair (cfz_comm.inl)
+    const double *pin = kComm ? cm.ring + (size_t)cfz::comm_slot(step0 + t - 1, cm.max_age) * cm.slot_stride
+                              : pred + (size_t)(t & 1) * B * 7 * N;   // predictions after iteration t-1
+    double *pout = kComm ? cm.ring + (size_t)cfz::comm_slot(step0 + t, cm.max_age) * cm.slot_stride : pred + (size_t)((t + 1) & 1) * B * 7 * N;
     const double *tab = ref_table + (size_t)table_of[s] * V * T * 7;
     const int rv = kSeq ? xrank[b] : 0;  // v's rank in its scenario's exchange order
+    // kComm: the age of what v reads of each neighbour, three bits each in neighbour order.  Every thread makes the at most
+    // (V - 1) * max_age draws itself (they depend on the item alone), so the ages need no LDS; the value is wavefront-uniform.
+    uint32_t ages = 0;
+    if (kComm) {
+      int o = 0;
+      for (int u = 0; u < V; ++u) {
+        if (u == v) continue;
+        const bool cur = kSeq && xrank[s * V + u] < rv;
+        ages |= (uint32_t)cfz::comm_age(cm, s, v, u, cfz::comm_want(step0 + t, cur)) << (3 * o);
+        ++o;
+      }
+      ages = __builtin_amdgcn_readfirstlane(ages);
+    }
     // ---- parameters and shifted warm start (vehicle_follower.py:432-476), straight into the solver's workspace: measured
     // state, neighbours' poses with cos / sin, warm start (solve_instance's `preloaded` form); only the reference goes through
     // a global record (the solver reads it from there in every iteration)
@@ -91,7 +108,12 @@
         double *q = smem + L.nb4 + (k * nn + o) * 4;
         const bool cur = kSeq && xrank[bo] < rv;  // ranked before v: its prediction of this iteration, not advanced
         const double *pu = cur ? pout : pin;
-        const int ku = cur ? k : ka;
+        int ku = cur ? k : ka;
+        if (kComm) {  // the message the age rule gives, at the row of cfz_comm.inl (age 0: the slot and the row above)
+          const int a = (ages >> (3 * o)) & 7;
+          pu = cm.ring + (size_t)cfz::comm_slot(cfz::comm_want(step0 + t, cur) - a, cm.max_age) * cm.slot_stride;
+          ku = cfz::comm_row(k, cur ? 0 : 1, cm.compensate, a, N);
+        }
         const double po = pu[(bo * 7 + 2) * N + ku];
         q[0] = pu[(bo * 7 + 0) * N + ku]; q[1] = pu[(bo * 7 + 1) * N + ku]; q[2] = cos(po); q[3] = sin(po);
         ++o;

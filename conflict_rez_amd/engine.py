@@ -164,6 +164,9 @@ def load_library(path=None):
     if hasattr(lib, "cfz_loop_set_disturbance"):  # (tools/gpu_lib_compare.py loads the build before this export through `path`)
         lib.cfz_loop_set_disturbance.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
         lib.cfz_loop_disturbance.argtypes = [vp, C.c_int, C.c_int, vp]
+    if hasattr(lib, "cfz_loop_set_comm"):
+        lib.cfz_loop_set_comm.argtypes = [vp, C.c_uint64, vp, C.c_int, C.c_int, vp]
+        lib.cfz_loop_comm.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.cfz_loop_record.argtypes = [vp, C.c_int]
     lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -177,7 +180,7 @@ EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
-    "cfz_loop_set_disturbance cfz_loop_disturbance"
+    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -632,6 +635,45 @@ class Engine:
         d = np.empty((max(int(K), 0), S, V, 12))
         self._ck(self.lib.cfz_loop_disturbance(self._h, int(t0), int(K), _ptr(d)), "cfz_loop_disturbance")
         return d
+
+    def loop_set_comm(self, seed, p_drop=None, max_age=3, compensate=True, stream=None):
+        """`cfz_loop_set_comm`: a lossy prediction exchange on the later steps and runs of the closed loop (include/confrez_hip.h).  A
+        neighbour's message of an iteration is lost with probability p_drop (a scalar, or [S] per scenario; None: lossless again, what
+        `loop_init` restores), drawn on the device from counter-based streams keyed by `seed`; a vehicle then plans against the newest
+        message that arrived, at most max_age (1..6) iterations old, advanced by its age (compensate) or as if it were new (the
+        reference's node).  stream [S] is each scenario's stream id (None: s).  Every call that switches it on restarts the message
+        history at the current predictions."""
+        S = getattr(self, "_S", 0)
+        if p_drop is None or not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+            p = None if p_drop is None else np.zeros(1)
+            self._ck(self.lib.cfz_loop_set_comm(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(p), 1, 0, None), "cfz_loop_set_comm")
+            return
+        p = np.asarray(p_drop)
+        if p.dtype.kind not in "fiu":
+            raise ValueError(f"p_drop must hold real numbers, got dtype {p.dtype}")
+        if p.shape == ():
+            p = np.broadcast_to(p, (S,))
+        if p.shape != (S,):
+            raise ValueError(f"p_drop must be a scalar or have shape ({S},), got {np.shape(p_drop)}")
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        for name, val in (("max_age", max_age), ("compensate", compensate)):
+            if not isinstance(val, (bool, int, np.integer, np.bool_)):
+                raise ValueError(f"{name} must be an integer, got {type(val).__name__}")
+        if stream is not None:
+            st = np.asarray(stream)
+            if st.dtype.kind not in "iu" or st.shape != (S,) or (st < 0).any() or (st > 0xFFFFFFFF).any():
+                raise ValueError(f"stream must hold {S} integers in [0, 2^32)")
+            stream = np.ascontiguousarray(st, dtype=np.uint32)
+        self._ck(self.lib.cfz_loop_set_comm(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(p), int(max_age), int(compensate),
+                                            _ptr(stream)), "cfz_loop_set_comm")
+
+    def loop_comm(self, tau0=0, K=1):
+        """`cfz_loop_comm`: bool [K,S,V,V], the delivery bits of the messages of iterations [tau0, tau0 + K) under the setting in force;
+        [k, s, v, u] is the message from vehicle u to vehicle v, the diagonal True; iterations count from `loop_init`."""
+        S, V = getattr(self, "_S", 1), getattr(self, "_V", self.spec.n_nbr + 1)
+        b = np.empty((max(int(K), 0), S, V, V), np.int32)
+        self._ck(self.lib.cfz_loop_comm(self._h, int(tau0), int(K), _ptr(b)), "cfz_loop_comm")
+        return b.astype(bool)
 
     def loop_step(self):
         self._ck(self.lib.cfz_loop_step(self._h), "cfz_loop_step")

@@ -12,9 +12,14 @@
    --noise-levels 0,0.5,1,2: every (strategy, start) runs once per level in the same launch, disturbed by level x NOISE_SIGMA
    (`Engine.loop_set_disturbance`: measurement, actuator and process noise drawn on the device); the replicas of a start share one
    stream id, so the levels are compared on common random numbers.  The table gains the share of scenarios with contact per level.
+   --drop-rates 0,0.1,0.3: every (strategy, start) (and noise level) runs once per rate in the same launch, each neighbour's prediction
+   message lost with that probability (`Engine.loop_set_comm`: a vehicle plans against the newest message that arrived, at most
+   --max-age iterations old, advanced by its age unless --no-compensate); the replicas of a start share one stream id, so the rates
+   are compared on common random numbers.  Contact-free starts and the smallest clearances are printed per rate.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
                                               [--noise-levels L0,L1,...] [--noise-seed SEED]
+                                              [--drop-rates P0,P1,...] [--max-age A] [--no-compensate] [--comm-seed SEED]
 """
 import argparse
 import os
@@ -40,6 +45,11 @@ def main():
     ap.add_argument("--noise-levels", type=lambda t: [float(x) for x in t.split(",")], default=None,
                     help="comma-separated scales of NOISE_SIGMA, e.g. 0,0.5,1,2: one replica of every start per level, in one launch")
     ap.add_argument("--noise-seed", type=int, default=2024, help="seed of the disturbance streams")
+    ap.add_argument("--drop-rates", type=lambda t: [float(x) for x in t.split(",")], default=None,
+                    help="comma-separated loss rates of the prediction messages, e.g. 0,0.1,0.3: one replica of every start per rate, in one launch")
+    ap.add_argument("--max-age", type=int, default=3, help="oldest message a vehicle plans against, in iterations (1..6)")
+    ap.add_argument("--no-compensate", action="store_true", help="advance a stale message as if it were new (the reference's node), not by its age")
+    ap.add_argument("--comm-seed", type=int, default=2024, help="seed of the delivery streams")
     a = ap.parse_args()
 
     import torch
@@ -78,6 +88,18 @@ def main():
         lvl, streams = np.repeat(np.asarray(levels, float), S0), np.tile(np.arange(S0, dtype=np.uint32), L)
         print(f"noise levels {levels} x sigma: meas {NOISE_SIGMA['meas']}, act {NOISE_SIGMA['act']}, proc {NOISE_SIGMA['proc']}; "
               f"noise seed {a.noise_seed}, one stream per start shared by its {L} replicas")
+    rates = a.drop_rates
+    drop = None
+    if rates:
+        # replicas again: block r is the whole batch so far (noise levels included) at rate r, every replica on the stream of its start
+        S1, R = len(k0), len(rates)
+        base = np.arange(S1, dtype=np.uint32) % np.uint32(len(k0s) * M)
+        k0, noise, tof = np.tile(k0, R), np.tile(noise, (R, 1, 1)), np.tile(tof, R)
+        if levels:
+            lvl, streams = np.tile(lvl, R), np.tile(streams, R)
+        drop, comm_streams = np.repeat(np.asarray(rates, float), S1), np.tile(base, R)
+        print(f"drop rates {rates}, max age {a.max_age}, {'no ' if a.no_compensate else ''}age compensation; comm seed {a.comm_seed}, "
+              f"one stream per start shared by its replicas")
     S = len(k0)
     eng = engine.Engine(spec, max_batch=S * V, device=a.device)
     eng.loop_init(plan["tables"], k0, noise, table_of=tof)
@@ -85,6 +107,8 @@ def main():
         eng.loop_set_disturbance(a.noise_seed, level=lvl, stream=streams, **NOISE_SIGMA)
     if a.exchange == "sequential":
         eng.loop_set_order(np.array([combos[p][0][0] for p in tof], np.int32))
+    if rates:
+        eng.loop_set_comm(a.comm_seed, drop, max_age=a.max_age, compensate=not a.no_compensate, stream=comm_streams)
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -110,13 +134,18 @@ def main():
         done = arr.min(1) >= 0  # every vehicle of the scenario arrived
         last = arr.max(1)[done]
         n_contact = int((aud["first_contact"][sel] >= 0).sum())
-        n_sel = int(sel.sum())  # M starts x noise levels
+        n_sel = int(sel.sum())  # M starts x noise levels x drop rates
         print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{n_sel:<2d} "
               f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
               + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or []))
         if n_contact == 0:
             no_contact.append(p)
-    print(f"strategies whose {M * len(levels or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
+    for r in rates or []:
+        sel = drop == r
+        free = int((aud["first_contact"][sel] < 0).sum())
+        print(f"drop rate {r:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
+              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
+    print(f"strategies whose {M * len(levels or [1]) * len(rates or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms")
     eng.close()
 

@@ -434,6 +434,41 @@ int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_me
                              const uint32_t *stream /* [S] or NULL: s */);
 int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d /* [K][S][V][12] */);
 
+/* ---- lossy prediction exchange of the closed loop ---------------------------------------------------------------------------------
+ * Above, every vehicle receives every neighbour's newest prediction, complete and on time.  The reference's deployment does not: a
+ * callback overwrites others_pred[other] with whichever VehiclePredictionMsg arrived last (ros2_ws/src/confrez_ros/src/vehicle_node.py:
+ * 154-163), timer_callback steps on a timer with whatever is there (:171-189), and step() advances that message by one stage whatever
+ * its age (_adv_onestep, vehicle_follower.py:413-426): a late or lost message means a stale prediction, read time-shifted.  With a
+ * comm setting, cfz_loop_step and cfz_loop_run alike, under either exchange rule (csrc/cfz_comm.inl states the model once):
+ *   Messages.  In MPC iteration tau (counted since cfz_loop_init / cfz_loop_init_tables) vehicle u of scenario s publishes its
+ *     prediction after that iteration, the solution or the shift fallback: message tau, which starts at time tau.
+ *   Delivery.  delivered(s, v <- u, tau) = u1 > p_drop[s], u1 in (0, 1] the first uniform of the Philox4x32-10 call with key
+ *     (seed & 0xffffffff, seed >> 32) and counter (stream[s], v, tau + 1, 8 + u), v the receiver; u1 = (((w0 >> 5) << 26) + (w1 >> 6)
+ *     + 1) * 2^-53.  Word 3 is 8..15: never a noise pair 0..5 of cfz_loop_set_disturbance, even under an equal seed.  p_drop = 0
+ *     delivers everything, p_drop = 1 nothing.  A bit depends on (seed, stream id, receiver, sender, tau) alone: not on S, on the
+ *     workgroup, on the exchange rule or on stepping against running.
+ *   Want.  In iteration t vehicle v wants message tau* = t - 1 of a neighbour (Jacobi), tau* = t of one ranked before it (sequential).
+ *   Age.  v reads message tau* - a, a the smallest a >= 0 with delivered(tau* - a), or a = min(max_age, tau* - tau_on): tau_on is the
+ *     message standing in the predictions when cfz_loop_set_comm was called; it counts as delivered and history starts there.  A message
+ *     of age max_age always gets through: the staleness is bounded.
+ *   Row.  Stage k of the neighbour's block reads row min(k + fresh + (compensate ? a : 0), N - 1) of that message, fresh = 1 under
+ *     Jacobi and 0 for a vehicle ranked before (what is read without loss).  compensate = 0 is the reference node, the last message
+ *     advanced as if it were new; compensate = 1 advances it by its age.
+ * The vehicle's own warm start, reference window, carried multipliers, read-back, fallback, plant, record, audit and disturbances are
+ * unaffected: a vehicle never loses its own prediction.  cfz_loop_get, the record and the audit see the newest messages.
+ * cfz_loop_set_comm: p_drop NULL switches the exchange back to lossless (the kernels that ran before run again).  stream[S] NULL: s.
+ * Every call that switches it on restarts history at the current predictions.  cfz_loop_init / cfz_loop_init_tables switch it off.
+ * Refused, the loop's state and the setting in force staying: a call before cfz_loop_init, a p_drop outside [0, 1] or not finite,
+ * max_age outside 1..CFZ_MAX_AGE, compensate other than 0 or 1.
+ * cfz_loop_comm: the delivery bits of messages [tau0, tau0 + K) under the setting in force, past or future (a pure function of the
+ * setting), delivered[k][s][v][u] for receiver v and sender u, the diagonal 1.  The bits, not the ages: a host replay states the age
+ * rule itself.  Refused when no comm setting is on, tau0 < 0, K < 1.
+ * cfz_vsl_step is untouched: its caller gathers the predictions and owns their delivery. */
+#define CFZ_MAX_AGE 6
+int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop /* [S], NULL: off */, int max_age /* 1..CFZ_MAX_AGE */,
+                      int compensate /* 0 | 1 */, const uint32_t *stream /* [S] or NULL: s */);
+int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered /* [K][S][V][V], diagonal 1 */);
+
 /* ---- closed loop over per-scenario plans -------------------------------------------------------
  * tables[P][V][T][7]: a pool of P plan sets (each what cfz_loop_init takes as ref_table); scenario s follows set table_of[s]
  * (NULL: set s, which needs P == S).  Otherwise exactly cfz_loop_init, which is this call with P = 1 and every scenario on set 0.

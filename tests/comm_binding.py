@@ -1,0 +1,192 @@
+"""The closed loop's lossy prediction exchange (`cfz_loop_set_comm`; conflict_rez_amd/csrc/cfz_comm.inl), stated a second time for the
+tests: a ctypes binding of the test-only CPU build of the kernel source (tests/emu/cfz_comm_emu.cpp), an independent numpy statement
+of the delivery bits on top of `disturbance_binding.philox4x32_10`, the age rule in plain Python, and a host replay of the closed loop
+that keeps the message history and takes every neighbour from it by that rule."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from disturbance_binding import philox4x32_10  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_comm_emu.so")
+_lib = None
+MAX_AGE = 6  # CFZ_MAX_AGE
+
+
+def build(force=False):
+    csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
+    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_comm_emu.cpp"), os.path.join(csrc, "cfz_comm.inl"), os.path.join(csrc, "cfz_disturb.inl")]
+    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(s) for s in srcs):
+        os.makedirs(os.path.dirname(_LIB), exist_ok=True)
+        tmp = _LIB + ".%d.tmp" % os.getpid()
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, srcs[0]])
+        os.replace(tmp, _LIB)
+    return _LIB
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = C.CDLL(build())
+        vp, i = C.c_void_p, C.c_int
+        _lib.cfz_emu_delivered.argtypes = [C.c_long] + [vp] * 8
+        _lib.cfz_emu_comm.argtypes = [C.c_uint64, vp, vp, i, i, i, i, vp]
+        _lib.cfz_emu_age.argtypes = [vp, i, i, i, i]
+        _lib.cfz_emu_age_drawn.argtypes = [C.c_uint64, vp, vp, i, i, i, i, i, i]
+        _lib.cfz_emu_want.argtypes = [i, i]
+        _lib.cfz_emu_slot.argtypes = [i, i]
+        _lib.cfz_emu_row.argtypes = [i] * 5
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def emu_delivered(seed, stream, v, u, tau, p):
+    """Arrays [n] -> (bit [n] bool, ctr [n,4] uint32: the Philox counter of each draw)."""
+    seed = np.ascontiguousarray(seed, np.uint64); n = len(seed)
+    stream = np.ascontiguousarray(np.broadcast_to(stream, n), np.uint32)
+    v, u, tau = (np.ascontiguousarray(np.broadcast_to(a, n), np.int32) for a in (v, u, tau))
+    p = np.ascontiguousarray(np.broadcast_to(p, n), float)
+    bit, ctr = np.empty(n, np.int32), np.empty((n, 4), np.uint32)
+    lib().cfz_emu_delivered(n, _p(seed), _p(stream), _p(v), _p(u), _p(tau), _p(p), _p(bit), _p(ctr))
+    return bit.astype(bool), ctr
+
+
+def emu_comm(seed, p_drop, stream, V, tau0, K):
+    p_drop = np.ascontiguousarray(p_drop, float); stream = np.ascontiguousarray(stream, np.uint32)
+    out = np.empty((K, len(p_drop), V, V), np.int32)
+    lib().cfz_emu_comm(C.c_uint64(int(seed)), _p(p_drop), _p(stream), len(p_drop), V, int(tau0), int(K), _p(out))
+    return out.astype(bool)
+
+
+def emu_age(bits, base, tau_star, max_age, tau_on):
+    bits = np.ascontiguousarray(bits, np.int32)
+    return lib().cfz_emu_age(_p(bits), int(base), int(tau_star), int(max_age), int(tau_on))
+
+
+def emu_age_drawn(seed, p_drop, stream, max_age, tau_on, s, v, u, tau_star):
+    p_drop = np.ascontiguousarray(p_drop, float); stream = np.ascontiguousarray(stream, np.uint32)
+    return lib().cfz_emu_age_drawn(C.c_uint64(int(seed)), _p(p_drop), _p(stream), int(max_age), int(tau_on), int(s), int(v), int(u), int(tau_star))
+
+
+# ---- numpy statement of the delivery bits ------------------------------------------------------------------------------------------
+def counters(stream, v, u, tau):
+    """The Philox counter (stream, receiver, tau + 1, 8 + sender) of broadcastable integer arrays -> [..., 4] uint64."""
+    a = np.broadcast_arrays(*(np.asarray(x).astype(np.int64) for x in (stream, v, np.asarray(tau).astype(np.int64) + 1, np.asarray(u).astype(np.int64) + 8)))
+    return np.stack(a, -1).astype(np.uint64)
+
+
+def u1_of(seed, stream, v, u, tau):
+    """The first uniform of the draw, in (0, 1]: an exact 53-bit value."""
+    ctr = counters(stream, v, u, tau)
+    seed = np.broadcast_to(np.asarray(seed, np.uint64), ctr.shape[:-1])
+    key = np.stack([seed & np.uint64(0xFFFFFFFF), seed >> np.uint64(32)], -1)
+    w = philox4x32_10(ctr, key).astype(np.uint64)
+    return (((w[..., 0] >> np.uint64(5)) << np.uint64(26)) + (w[..., 1] >> np.uint64(6)) + np.uint64(1)).astype(float) * 2.0 ** -53
+
+
+def delivered_bits(seed, stream, v, u, tau, p):
+    return u1_of(seed, stream, v, u, tau) > np.asarray(p, float)
+
+
+def delivered(seed, p_drop, stream, V, tau0, K):
+    """bool [K, S, V, V] of messages [tau0, tau0 + K): [k, s, v, u] is the bit of receiver v, sender u; the diagonal is True."""
+    p_drop = np.asarray(p_drop, float); stream = np.asarray(stream)
+    tau = (tau0 + np.arange(K))[:, None, None, None]
+    b = delivered_bits(np.uint64(int(seed)), stream[None, :, None, None], np.arange(V)[None, None, :, None], np.arange(V)[None, None, None, :], tau,
+                       p_drop[None, :, None, None])
+    b = np.array(b)
+    b[:, :, np.arange(V), np.arange(V)] = True
+    return b
+
+
+# ---- the age rule and the read row, in plain Python --------------------------------------------------------------------------------
+def want(t, earlier):
+    """The message a vehicle wants of a neighbour in iteration t: t - 1, or t of a neighbour ranked before it (sequential exchange)."""
+    return t if earlier else t - 1
+
+
+def age_rule(bit, tau_star, max_age, tau_on):
+    """Smallest a >= 0 with bit(tau_star - a), or min(max_age, tau_star - tau_on): the message tau_on counts as delivered, and so does
+    one of age max_age."""
+    a_eff = min(max_age, tau_star - tau_on)
+    for a in range(a_eff):
+        if bit(tau_star - a):
+            return a
+    return a_eff
+
+
+def rows(N, fresh, compensate, a):
+    return np.minimum(np.arange(N) + fresh + (a if compensate else 0), N - 1)
+
+
+class Setting:
+    """A comm setting of the replay.  bits [T, S, V, V] (bool, indexed by the message number tau from 0; `Engine.loop_comm(0, T)`) or
+    age: a function (t, s, v, u, earlier) -> the age outright; tau_on: the message history starts at."""
+
+    def __init__(self, max_age, compensate, tau_on, bits=None, age=None):
+        self.max_age, self.compensate, self.tau_on, self.bits, self.age = int(max_age), bool(compensate), int(tau_on), bits, age
+
+    def age_of(self, t, s, v, u, earlier):
+        if self.age is not None:
+            return self.age(t, s, v, u, earlier)
+        return age_rule(lambda tau: bool(self.bits[tau, s, v, u]), want(t, earlier), self.max_age, self.tau_on)
+
+
+# ---- host replay with message history ----------------------------------------------------------------------------------------------
+def replay(ospec, table, k0, noise, steps, comm, dt=0.1, wb=2.5, *, order=None, d=None, box=None, ages=None):
+    """The closed loop on the host with the lossy exchange: after every iteration yields (state [S,V,5], pred [S,V,7,N], status [S,V],
+    iters [S,V]).  comm(t) -> the Setting in force in iteration t, or None (lossless).  order, d, box: as `oracle.closed_loop.replay`.
+    ages (a list, or None): receives (t, s, v, u, a) of every neighbour read under a setting.
+    History: message tau is the prediction array after iteration tau (tau = -1: the seed); iteration t's own messages are read by the
+    vehicles ranked later in the same iteration."""
+    from oracle import port
+    from oracle.closed_loop import seed
+    from oracle.dynamics import plant_step
+
+    S, V, N, T = len(k0), table.shape[0], ospec.N, table.shape[1]
+    state, pred = seed(table, k0, noise, N)
+    hist = {-1: pred}
+    carry = [[None] * V for _ in range(S)]
+    adv = np.minimum(np.arange(N) + 1, N - 1)
+    for t in range(steps):
+        cm = comm(t)
+        newp = hist[t - 1].copy()
+        hist[t] = newp
+        status = np.zeros((S, V), int); iters = np.zeros((S, V), int)
+        for s in range(S):
+            done = []
+            for v in (range(V) if order is None else order[s]):
+                nb = []
+                for u in range(V):
+                    if u == v:
+                        continue
+                    earlier = u in done
+                    a = 0 if cm is None else cm.age_of(t, s, v, u, earlier)
+                    if cm is not None and ages is not None:
+                        ages.append((t, s, v, u, a))
+                    msg = hist[want(t, earlier) - a][s, u]
+                    nb.append(msg[:3][:, rows(N, 0 if earlier else 1, cm is not None and cm.compensate, a)])
+                w = hist[t - 1][s, v][:, adv]
+                ref = table[v, np.minimum(k0[s] + t + np.arange(N), T - 1), :3].T
+                dd = None if d is None else d[t, s, v]
+                x0 = state[s, v] if dd is None else state[s, v] + dd[:5]
+                r = port.solve(ospec, x0, ref, np.stack(nb), w.T.copy(), carry=carry[s][v])
+                carry[s][v] = r["carry"]
+                newp[s, v] = r["p"].T if r["status"] == 0 else w
+                inp = newp[s, v][5:7, 0] if dd is None else np.clip(newp[s, v][5:7, 0] + dd[5:7], box[:, 0], box[:, 1])
+                state[s, v] = plant_step(state[s, v], inp, dt, wb)
+                if dd is not None:
+                    state[s, v] += dd[7:12]
+                status[s, v], iters[s, v] = r["status"], r["iters"]
+                if order is not None:
+                    done.append(v)
+        hist.pop(t - 2 - MAX_AGE, None)
+        yield state.copy(), newp.copy(), status, iters
