@@ -10,6 +10,9 @@
 //   loop_kernel_seq  the same with the sequential exchange of cfz_loop_set_order (one body: cfz_loop_body.inl)
 //   loop_kernel_dist, loop_kernel_seq_dist  the same two with the disturbances of cfz_loop_set_disturbance (cfz_disturb.inl)
 //   loop_kernel_comm, loop_kernel_seq_comm  the same two with the lossy exchange of cfz_loop_set_comm (cfz_comm.inl) and disturbances
+//   loop_kernel_pool, loop_kernel_seq_pool, loop_kernel_pool_comm, loop_kernel_seq_pool_comm  the disturbed and the lossy pairs with the
+//                  per-scenario problem constants of cfz_loop_set_problems: an item reads the KArgs block of its scenario's problem
+//   solve_kernel_pool  solve_kernel with the same selection, for the stepwise closed loop while a pool is set
 //   loop_prep      stepwise closed loop (cfz_loop_step): parameters and shifted warm start of every vehicle from the
 //                  previous predictions (reference vehicle_follower.py:432-476, 636-637), the measurement under a disturbance
 //   loop_post      stepwise closed loop: read-back or shift fallback, plant integration, clock
@@ -22,7 +25,7 @@
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
 // (loop_release).  cfz_loop_step is loop_round (prep, solve, post) once for Jacobi or V times for the sequential exchange;
-// cfz_loop_run picks its kernel from kLoopKernel[setting][sequential].
+// cfz_loop_run picks its kernel from kLoopKernel[pool][setting][sequential].
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -82,6 +85,38 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
   }
   // carry record of the instance's slot (default: slot b): used when the caller says that this solve is the successor of
   // the previous one in that slot
+  const int slot = slots ? slots[b] : b;
+  cfz::solve_instance(sp, dv, x0 + (size_t)b * 5, ref + (size_t)b * 3 * N, nbr + (size_t)b * nn * 3 * N,
+                      zu + (size_t)b * 7 * N, smem, L, oi, od, duo, wst ? wst + (size_t)slot * wst_stride : nullptr,
+                      carry_all || (carry && carry[b]));
+  if (threadIdx.x == 0) {
+    iters[b] = oi[0]; status[b] = oi[1];
+    stats[b * 3 + 0] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
+  }
+}
+
+// solve_kernel for the stepwise closed loop under cfz_loop_set_problems: instance b = (scenario s, vehicle) of V solves the problem
+// pool[problem_of[s]] (its spec and derived constants; the layout is the handle's, ka->L).  The index depends on the workgroup alone,
+// so the block is read through scalar loads as ka is.  A kernel of its own: solve_kernel keeps its code.
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel_pool(const KArgs *__restrict__ ka, int B, const double *x0,
+                                                   const double *ref, const double *nbr, double *zu, int32_t *status,
+                                                   int32_t *iters, double *stats, DualPtrs du, const int32_t *order,
+                                                   double *wst, int wst_stride, const int32_t *carry, int carry_all,
+                                                   const int32_t *slots, const KArgs *__restrict__ pool,
+                                                   const int32_t *__restrict__ problem_of, int V) {
+  extern __shared__ double smem[];
+  if ((int)blockIdx.x >= B) return;
+  const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
+  const KArgs *const kp = pool + __builtin_amdgcn_readfirstlane(problem_of[b / V]);
+  const cfz::KSpec &sp = kp->sp; const cfz::KDer &dv = kp->dv; const cfz::Lay &L = ka->L;
+  const int N = ka->sp.N, no = ka->sp.n_obs, nn = ka->sp.n_nbr;
+  int oi[2]; double od[3];
+  cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (du.l) {
+    duo.l = du.l + (size_t)b * N * 4 * no; duo.mm = du.m + (size_t)b * N * 4 * no;
+    duo.lam_ij = du.lam_ij + (size_t)b * nn * N * 4; duo.lam_ji = du.lam_ji + (size_t)b * nn * N * 4;
+    duo.s = du.s + (size_t)b * nn * N * 2;
+  }
   const int slot = slots ? slots[b] : b;
   cfz::solve_instance(sp, dv, x0 + (size_t)b * 5, ref + (size_t)b * 3 * N, nbr + (size_t)b * nn * 3 * N,
                       zu + (size_t)b * 7 * N, smem, L, oi, od, duo, wst ? wst + (size_t)slot * wst_stride : nullptr,
@@ -163,10 +198,12 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
 // carry (NULL: none; cfz_vsl_step): the carry flag of the next iteration, a vehicle whose solve converged starts its next one from
 // these multipliers.
 // msg (NULL: none; cfz_loop_set_comm): this iteration's slot [S][V][7][N] of the ring of messages, which takes the posted prediction too.
+// pool, problem_of (NULL: none; cfz_loop_set_problems): the input box is that of the scenario's problem instead of the four scalars.
 __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
                           const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
                           int32_t *rec_si, int r, const int32_t *xperm, cfz::DisturbArgs dz, int step, double a_lo, double a_hi,
-                          double w_lo, double w_hi, int32_t *carry, double *msg) {
+                          double w_lo, double w_hi, int32_t *carry, double *msg, const KArgs *pool,
+                          const int32_t *problem_of) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (xperm ? S : S * V)) return;
   if (xperm) b = b * V + xperm[b * V + r];
@@ -184,6 +221,10 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
   double a0 = pb[5 * N], w0 = pb[6 * N];
   const int s = b / V, v = b - s * V;
   if (dz.sigma) {
+    if (pool) {
+      const double *bd = pool[problem_of[s]].sp.bounds;
+      a_lo = bd[8]; a_hi = bd[9]; w_lo = bd[10]; w_hi = bd[11];
+    }
     a0 = cfz::disturb_clip(cfz::disturb_add(a0, cfz::disturb_value(dz, s, v, step, 5)), a_lo, a_hi);
     w0 = cfz::disturb_clip(cfz::disturb_add(w0, cfz::disturb_value(dz, s, v, step, 6)), w_lo, w_hi);
   }
@@ -274,13 +315,14 @@ __global__ __launch_bounds__(1024) void order_by_iters(int B, const int32_t *ite
 // Two kernels, one body (cfz_loop_body.inl, included into both): loop_kernel keeps its symbol (profiles and bench.py name rows
 // by it), takes no argument for the exchange rule and compiles to the Jacobi loop's code alone (a __device__ template with the
 // `__restrict__` parameter moved the kernel's register allocation: 16 more VGPR spills).
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                        const double *ref_table, const int32_t *table_of, const int32_t *kidx0, int t_base,
-                                                        double *pred, double *state, double *scratch, int32_t *qbuf,
-                                                        int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                        double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
-                                                        double *rec, int32_t *rec_si) {
-  constexpr bool kSeq = false, kDist = false, kComm = false;
+// the arguments every persistent kernel takes, before those of its own setting
+#define CFZ_LOOP_ARGS const KArgs *__restrict__ ka, int S, int V, int K, int T, const double *ref_table, const int32_t *table_of,        \
+                      const int32_t *kidx0, int t_base, double *pred, double *state, double *scratch, int32_t *qbuf, int32_t *ctrl,       \
+                      int32_t *done, int32_t *status, int32_t *iters, double *stats, int32_t *iter_sum, double *wst, int wst_stride,     \
+                      int prio_lag, double *rec, int32_t *rec_si
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(CFZ_LOOP_ARGS) {
+  constexpr bool kSeq = false, kDist = false, kComm = false, kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
   const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
@@ -288,13 +330,9 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(cons
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                            const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
-                                                            int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
-                                                            int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                            double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
-                                                            double *rec, int32_t *rec_si, const int32_t *xperm, const int32_t *xrank) {
-  constexpr bool kSeq = true, kDist = false, kComm = false;
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank) {
+  constexpr bool kSeq = true, kDist = false, kComm = false, kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
   const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
   const int step0 = 0;
@@ -304,26 +342,18 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(
 // The two kernels above with the disturbances of cfz_loop_set_disturbance (kDist): dz is the setting, step0 the MPC iterations done
 // since cfz_loop_init* (iteration t of this launch is step step0 + t of the streams).  Kernels of their own, made as loop_kernel_seq
 // was, so that the two undisturbed kernels keep the code they had before disturbances existed.
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_dist(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                             const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
-                                                             int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
-                                                             int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                             double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
-                                                             double *rec, int32_t *rec_si, cfz::DisturbArgs dz, int step0) {
-  constexpr bool kSeq = false, kDist = true, kComm = false;
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_dist(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0) {
+  constexpr bool kSeq = false, kDist = true, kComm = false, kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_dist(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                                 const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
-                                                                 int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
-                                                                 int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                                 double *stats, int32_t *iter_sum, double *wst, int wst_stride,
-                                                                 int prio_lag, double *rec, int32_t *rec_si, const int32_t *xperm,
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_dist(CFZ_LOOP_ARGS, const int32_t *xperm,
                                                                  const int32_t *xrank, cfz::DisturbArgs dz, int step0) {
-  constexpr bool kSeq = true, kDist = true, kComm = false;
+  constexpr bool kSeq = true, kDist = true, kComm = false, kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
 #include "cfz_loop_body.inl"
 }
@@ -333,33 +363,66 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
 // without further variants; with no noise set, dz is an all-zero sigma, which is bit-neutral.  Kernels of their own again: the
 // four above keep their code.  The release / acquire edges are those of the kernels above: the older slots a reader may take were
 // published by earlier iterations of the same scenario, which the chain of edges to this item covers.
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_comm(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                             const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
-                                                             int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
-                                                             int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                             double *stats, int32_t *iter_sum, double *wst, int wst_stride, int prio_lag,
-                                                             double *rec, int32_t *rec_si, cfz::DisturbArgs dz, int step0,
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_comm(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0,
                                                              cfz::CommArgs cm) {
-  constexpr bool kSeq = false, kDist = true, kComm = true;
+  constexpr bool kSeq = false, kDist = true, kComm = true, kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_comm(const KArgs *__restrict__ ka, int S, int V, int K, int T,
-                                                                 const double *ref_table, const int32_t *table_of, const int32_t *kidx0,
-                                                                 int t_base, double *pred, double *state, double *scratch, int32_t *qbuf,
-                                                                 int32_t *ctrl, int32_t *done, int32_t *status, int32_t *iters,
-                                                                 double *stats, int32_t *iter_sum, double *wst, int wst_stride,
-                                                                 int prio_lag, double *rec, int32_t *rec_si, const int32_t *xperm,
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_comm(CFZ_LOOP_ARGS, const int32_t *xperm,
                                                                  const int32_t *xrank, cfz::DisturbArgs dz, int step0, cfz::CommArgs cm) {
-  constexpr bool kSeq = true, kDist = true, kComm = true;
+  constexpr bool kSeq = true, kDist = true, kComm = true, kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
 #include "cfz_loop_body.inl"
 }
 
-// the persistent kernel of a setting, [0 plain, 1 disturbed, 2 lossy exchange (with or without disturbance)][sequential]
-const void *const kLoopKernel[3][2] = {{(const void *)loop_kernel, (const void *)loop_kernel_seq},
-                                       {(const void *)loop_kernel_dist, (const void *)loop_kernel_seq_dist},
-                                       {(const void *)loop_kernel_comm, (const void *)loop_kernel_seq_comm}};
+// The problem pool of cfz_loop_set_problems (kPool): pool[P] holds one KArgs block per problem, problem_of[S] the problem of every
+// scenario; an item binds the spec and the derived constants of its scenario's problem and keeps the handle's layout.  Compiled as the
+// comm kernels were, with kDist, so that the pool combines with noise and loss without a full cross product: with no noise set, dz is
+// an all-zero sigma, which is bit-neutral once the clip of the applied input is left out as well (dz_clip 0: the undisturbed loop clips
+// nothing, and a prediction seeded from the plan may lie outside a problem's tighter input box).  Kernels of their own once more: the
+// six above keep their code.
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_pool(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0,
+                                                             const KArgs *__restrict__ pool, const int32_t *__restrict__ problem_of, int dz_clip) {
+  constexpr bool kSeq = false, kDist = true, kComm = false, kPool = true;
+  const cfz::CommArgs cm = cfz::comm_none();
+  const int32_t *const xperm = nullptr, *const xrank = nullptr;
+#include "cfz_loop_body.inl"
+}
+
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_pool(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank,
+                                                                 cfz::DisturbArgs dz, int step0, const KArgs *__restrict__ pool,
+                                                                 const int32_t *__restrict__ problem_of, int dz_clip) {
+  constexpr bool kSeq = true, kDist = true, kComm = false, kPool = true;
+  const cfz::CommArgs cm = cfz::comm_none();
+#include "cfz_loop_body.inl"
+}
+
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_pool_comm(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0, cfz::CommArgs cm,
+                                                                  const KArgs *__restrict__ pool, const int32_t *__restrict__ problem_of, int dz_clip) {
+  constexpr bool kSeq = false, kDist = true, kComm = true, kPool = true;
+  const int32_t *const xperm = nullptr, *const xrank = nullptr;
+#include "cfz_loop_body.inl"
+}
+
+__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_pool_comm(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank,
+                                                                      cfz::DisturbArgs dz, int step0, cfz::CommArgs cm,
+                                                                      const KArgs *__restrict__ pool, const int32_t *__restrict__ problem_of, int dz_clip) {
+  constexpr bool kSeq = true, kDist = true, kComm = true, kPool = true;
+#include "cfz_loop_body.inl"
+}
+#undef CFZ_LOOP_ARGS
+
+// the persistent kernel of a setting, [problem pool][0 plain, 1 disturbed, 2 lossy exchange (with or without disturbance)][sequential];
+// the pool kernels are compiled with disturbances, so plain and disturbed share one pair
+const void *const kLoopKernel[2][3][2] = {{{(const void *)loop_kernel, (const void *)loop_kernel_seq},
+                                           {(const void *)loop_kernel_dist, (const void *)loop_kernel_seq_dist},
+                                           {(const void *)loop_kernel_comm, (const void *)loop_kernel_seq_comm}},
+                                          {{(const void *)loop_kernel_pool, (const void *)loop_kernel_seq_pool},
+                                           {(const void *)loop_kernel_pool, (const void *)loop_kernel_seq_pool},
+                                           {(const void *)loop_kernel_pool_comm, (const void *)loop_kernel_seq_pool_comm}}};
 
 // delivered[K][S][V][V]: the delivery bits of messages [tau0, tau0 + K) (cfz_loop_comm), receiver before sender, diagonal 1; one thread
 // each, through the function the loop uses
@@ -591,6 +654,8 @@ struct cfz_handle {
   int device = 0, max_batch = 0;
   cfz::KSpec ks;
   cfz::Lay lay;
+  cfz_spec spec0;    // what cfz_create was given: the base a pool entry is checked against and the default of its options
+  cfz_options opt0;
   size_t lds_bytes = 0;
   int blocks_per_cu = 0;
   hipStream_t stream = nullptr;
@@ -638,6 +703,14 @@ struct cfz_handle {
     uint64_t cm_seed = 0;
     int cm_max_age = 0, cm_compensate = 0, cm_tau_on = 0, cm_ring_slots = 0;
     bool cm_on = false;
+    // problem pool (cfz_loop_set_problems; pb_on false: none): pb_pool[pb_cap] the KArgs block {ks_p, derive(ks_p), lay} of every problem
+    // (obs_tab the handle's), pb_of[S] the problem of each scenario; pb_dz = zero sigma[12] | zero level[S] | zero stream[S] (uint32),
+    // what the pool kernels take for dz while neither a disturbance nor a lossy exchange is set
+    KArgs *pb_pool = nullptr;
+    int32_t *pb_of = nullptr;
+    void *pb_dz = nullptr;
+    int pb_cap = 0;
+    bool pb_on = false;
     // persistent loop
     double *pred2 = nullptr, *scratch = nullptr;
     int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
@@ -652,14 +725,20 @@ namespace {
 // grid (0: B) workgroups solve the instances order[0 .. grid) of the B (order NULL: 0 .. B)
 int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, const double *nbr, double *zu,
                  int32_t *status, int32_t *iters, double *stats, bool duals, hipStream_t st,
-                 const int32_t *order = nullptr, int carry_all = 0, int grid = 0) {
+                 const int32_t *order = nullptr, int carry_all = 0, int grid = 0, bool pool = false) {
   DualPtrs du = {nullptr, nullptr, nullptr, nullptr, nullptr};
   if (duals) du = {h->l, h->m, h->lam_ij, h->lam_ji, h->s};
   if ((h->carry_set || h->slots_set) && st != h->stream) HIP_OK(hipStreamWaitEvent(st, h->ev_stage, 0));  // staged on the handle's stream
   HIP_OK(hipEventRecord(h->ev0, st));
-  hipLaunchKernelGGL(solve_kernel, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
-                     iters, stats, du, order, h->carry_duals ? h->wst : nullptr, h->wst_stride,
-                     h->carry_ext ? h->carry_ext : (h->carry_set ? h->carry : nullptr), carry_all, h->slots_set ? h->slots : nullptr);
+  const int32_t *carry = h->carry_ext ? h->carry_ext : (h->carry_set ? h->carry : nullptr);
+  if (pool)  // the stepwise closed loop under cfz_loop_set_problems: instance b solves the problem of scenario b / V
+    hipLaunchKernelGGL(solve_kernel_pool, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
+                       iters, stats, du, order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all,
+                       h->slots_set ? h->slots : nullptr, h->lp.pb_pool, h->lp.pb_of, h->ks.n_nbr + 1);
+  else
+    hipLaunchKernelGGL(solve_kernel, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
+                       iters, stats, du, order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all,
+                       h->slots_set ? h->slots : nullptr);
   h->carry_set = false; h->slots_set = false; h->carry_ext = nullptr;  // the flags of cfz_mpc_set_carry / cfz_mpc_set_slots hold for one solve
   h->ms_pending = true;
   HIP_OK(hipGetLastError());
@@ -669,6 +748,43 @@ int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, cons
 
 int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt);
 void loop_release(cfz_handle *h);
+
+// the value checks of cfz_create on a spec's sizes and on the options (cfz_problem_check makes the same ones)
+int spec_shape_ok(const cfz_spec *spec) {
+  if (spec->N < 2 || spec->N > CFZ_MAX_N) return fail("N out of range");
+  if (spec->n_obs < 0 || spec->n_obs > CFZ_MAX_OBS || spec->n_nbr < 0 || spec->n_nbr > CFZ_MAX_NBR)
+    return fail("n_obs / n_nbr out of range");
+  if (spec->N > cfz::kMaxN) return fail("N exceeds the four-lanes-per-stage kernel");
+  return 0;
+}
+
+int options_ok(const cfz_options *opt) {
+  if (opt->filter_cap < 1 || opt->filter_cap > 32) return fail("filter_cap must be in 1..32");
+  if (opt->restoration < 0 || !(opt->reg_dual_rows >= 0.0) || !(opt->resto_first >= 0.0)) return fail("restoration, reg_dual_rows, resto_first must not be negative");
+  return 0;
+}
+
+// the kernel's form of (spec, opt), obs_tab left NULL; refused: an obstacle that is no bounded quadrilateral
+int fill_kspec(cfz::KSpec &k, const cfz_spec *spec, const cfz_options *opt) {
+  memset(&k, 0, sizeof k);
+  k.N = spec->N; k.n_obs = spec->n_obs; k.n_nbr = spec->n_nbr; k.rk_substeps = spec->rk_substeps;
+  k.max_iter = opt->max_iter; k.max_backtrack = opt->max_backtrack; k.filter_cap = opt->filter_cap;
+  k.dt = spec->dt; k.wb = spec->wb; k.dmin = spec->dmin;
+  memcpy(k.g, spec->g, sizeof k.g); memcpy(k.bounds, spec->bounds, sizeof k.bounds);
+  memcpy(k.weights, spec->weights, sizeof k.weights);
+  for (int j = 0; j < spec->n_obs; ++j) {
+    memcpy(k.A_obs[j], spec->A_obs[j], sizeof k.A_obs[j]); memcpy(k.b_obs[j], spec->b_obs[j], sizeof k.b_obs[j]);
+    if (!quad_vertices(spec->A_obs[j], spec->b_obs[j], k.V_obs[j])) return fail("obstacle is not a bounded quadrilateral");
+  }
+  k.tol = opt->tol; k.constr_viol_tol = opt->constr_viol_tol; k.dual_inf_tol = opt->dual_inf_tol;
+  k.compl_inf_tol = opt->compl_inf_tol; k.mu_init = opt->mu_init; k.kappa_eps = opt->kappa_eps;
+  k.kappa_mu = opt->kappa_mu; k.theta_mu = opt->theta_mu; k.tau_min = opt->tau_min; k.bound_push = opt->bound_push;
+  k.bound_frac = opt->bound_frac; k.s_max = opt->s_max; k.kappa_sigma = opt->kappa_sigma; k.eta_phi = opt->eta_phi;
+  k.gamma_theta = opt->gamma_theta; k.gamma_phi = opt->gamma_phi; k.delta_sw = opt->delta_sw;
+  k.s_theta = opt->s_theta; k.s_phi = opt->s_phi; k.reg_primal = opt->reg_primal;
+  k.stall_iters = opt->stall_iters; k.stall_kappa = opt->stall_kappa; k.row_curvature = opt->row_curvature; k.vv_rows = opt->vv_rows; k.shift_after = opt->shift_after; k.resto = opt->restoration; k.stag_win = opt->shift_stagnation; k.err_stall = opt->err_stall_iters; k.carry_shift = opt->carry_shift ? 1 : 0; k.pad_ks = 0; k.warm_push = opt->warm_push; k.reg_dual_rows = opt->reg_dual_rows; k.resto_first = opt->resto_first;
+  return 0;
+}
 
 int check(cfz_handle *h, int B) {
   if (!h) return fail("null handle");
@@ -714,13 +830,9 @@ int cfz_create(const cfz_spec *spec, const cfz_options *opt, int device, int max
   if (!spec || !out) return fail("null argument");
   cfz_options od;
   if (!opt) { cfz_default_options(&od); opt = &od; }
-  if (spec->N < 2 || spec->N > CFZ_MAX_N) return fail("N out of range");
-  if (spec->n_obs < 0 || spec->n_obs > CFZ_MAX_OBS || spec->n_nbr < 0 || spec->n_nbr > CFZ_MAX_NBR)
-    return fail("n_obs / n_nbr out of range");
-  if (spec->N > cfz::kMaxN) return fail("N exceeds the four-lanes-per-stage kernel");
+  if (spec_shape_ok(spec)) return -1;
   if (max_batch < 1) return fail("max_batch must be positive");
-  if (opt->filter_cap < 1 || opt->filter_cap > 32) return fail("filter_cap must be in 1..32");
-  if (opt->restoration < 0 || !(opt->reg_dual_rows >= 0.0) || !(opt->resto_first >= 0.0)) return fail("restoration, reg_dual_rows, resto_first must not be negative");
+  if (options_ok(opt)) return -1;
   int ndev = 0;
   HIP_OK(hipGetDeviceCount(&ndev));
   if (ndev == 0) return fail("no HIP device: libconfrez_hip has no CPU path");
@@ -740,29 +852,15 @@ namespace {
 int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
   const int max_batch = h->max_batch;
   cfz::KSpec &k = h->ks;
-  memset(&k, 0, sizeof k);
-  k.N = spec->N; k.n_obs = spec->n_obs; k.n_nbr = spec->n_nbr; k.rk_substeps = spec->rk_substeps;
-  k.max_iter = opt->max_iter; k.max_backtrack = opt->max_backtrack; k.filter_cap = opt->filter_cap;
-  k.dt = spec->dt; k.wb = spec->wb; k.dmin = spec->dmin;
-  memcpy(k.g, spec->g, sizeof k.g); memcpy(k.bounds, spec->bounds, sizeof k.bounds);
-  memcpy(k.weights, spec->weights, sizeof k.weights);
-  for (int j = 0; j < spec->n_obs; ++j) {
-    memcpy(k.A_obs[j], spec->A_obs[j], sizeof k.A_obs[j]); memcpy(k.b_obs[j], spec->b_obs[j], sizeof k.b_obs[j]);
-    if (!quad_vertices(spec->A_obs[j], spec->b_obs[j], k.V_obs[j])) return fail("obstacle is not a bounded quadrilateral");
-  }
-  k.tol = opt->tol; k.constr_viol_tol = opt->constr_viol_tol; k.dual_inf_tol = opt->dual_inf_tol;
-  k.compl_inf_tol = opt->compl_inf_tol; k.mu_init = opt->mu_init; k.kappa_eps = opt->kappa_eps;
-  k.kappa_mu = opt->kappa_mu; k.theta_mu = opt->theta_mu; k.tau_min = opt->tau_min; k.bound_push = opt->bound_push;
-  k.bound_frac = opt->bound_frac; k.s_max = opt->s_max; k.kappa_sigma = opt->kappa_sigma; k.eta_phi = opt->eta_phi;
-  k.gamma_theta = opt->gamma_theta; k.gamma_phi = opt->gamma_phi; k.delta_sw = opt->delta_sw;
-  k.s_theta = opt->s_theta; k.s_phi = opt->s_phi; k.reg_primal = opt->reg_primal;
-  k.stall_iters = opt->stall_iters; k.stall_kappa = opt->stall_kappa; k.row_curvature = opt->row_curvature; k.vv_rows = opt->vv_rows; k.shift_after = opt->shift_after; k.resto = opt->restoration; k.stag_win = opt->shift_stagnation; k.err_stall = opt->err_stall_iters; k.carry_shift = opt->carry_shift ? 1 : 0; k.pad_ks = 0; k.warm_push = opt->warm_push; k.reg_dual_rows = opt->reg_dual_rows; k.resto_first = opt->resto_first;
+  if (fill_kspec(k, spec, opt)) return -1;
+  h->spec0 = *spec; h->opt0 = *opt;
   h->lay = cfz::make_layout(k.N, k.n_obs + k.n_nbr, k.n_nbr);
   h->lds_bytes = (size_t)h->lay.total * sizeof(double);
   if (const char *pad = std::getenv("CFZ_LDS_PAD")) h->lds_bytes += (size_t)std::atoi(pad);  // occupancy experiments only
   if (h->lds_bytes > 160 * 1024) return fail("problem does not fit the 160 KiB LDS of one CU");
   if (h->lds_bytes > 64 * 1024) {
-    for (const void *kern : {(const void *)solve_kernel, kLoopKernel[0][0], kLoopKernel[0][1], kLoopKernel[1][0], kLoopKernel[1][1]}) {
+    for (const void *kern : {(const void *)solve_kernel, kLoopKernel[0][0][0], kLoopKernel[0][0][1], kLoopKernel[0][1][0], kLoopKernel[0][1][1],
+                             (const void *)solve_kernel_pool, kLoopKernel[1][0][0], kLoopKernel[1][0][1], kLoopKernel[1][2][0], kLoopKernel[1][2][1]}) {
       const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
       if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
     }
@@ -977,7 +1075,7 @@ int cfz_vsl_step(cfz_handle *h, int S, int V, int n_own, const int32_t *d_own, i
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, d_status, d_iters, d_stats, false, st)) return -1;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, S, n_own, N, h->ks.dt, h->ks.wb, kPlantSubsteps, d_status,
                      nullptr, h->zu, d_pred, d_state, nullptr, nullptr, nullptr, 0, nullptr, cfz::DisturbArgs{0, nullptr, nullptr, nullptr}, 0,
-                     0.0, 0.0, 0.0, 0.0, d_carry, nullptr);
+                     0.0, 0.0, 0.0, 0.0, d_carry, nullptr, nullptr, nullptr);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1051,10 +1149,15 @@ void comm_free(cfz_handle *h) {
   h->lp.cm_on = false; h->lp.cm_ring_slots = 0;
 }
 
-// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance and comm setting and the
+void problems_free(cfz_handle *h) {
+  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of); dev_free(h->lp.pb_dz);
+  h->lp.pb_on = false; h->lp.pb_cap = 0;
+}
+
+// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance and comm setting, problem pool and the
 // persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
 void loop_release(cfz_handle *h) {
-  record_free(h); exchange_free(h); disturb_free(h); comm_free(h);
+  record_free(h); exchange_free(h); disturb_free(h); comm_free(h); problems_free(h);
   dev_free(h->lp.ref_table); dev_free(h->lp.table_of); dev_free(h->lp.pred); dev_free(h->lp.state); dev_free(h->lp.kidx); dev_free(h->lp.order);
   dev_free(h->lp.pred2); dev_free(h->lp.scratch); dev_free(h->lp.queue); dev_free(h->lp.ctrl); dev_free(h->lp.done); dev_free(h->lp.iter_sum);
   h->lp = cfz_handle::Loop();
@@ -1083,6 +1186,14 @@ cfz::DisturbArgs comm_disturb_args(const cfz_handle *h) {
   return {0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
 }
 
+// what the pool kernels take for dz: the disturbance in force, the comm setting's zeros, or the pool's own
+cfz::DisturbArgs pool_disturb_args(const cfz_handle *h) {
+  if (h->lp.dz_on) return disturb_args(h);
+  if (h->lp.cm_on) return comm_disturb_args(h);
+  const double *f = static_cast<const double *>(h->lp.pb_dz);
+  return {0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
+}
+
 // the slot of message tau in the ring (comm on)
 double *comm_message(const cfz_handle *h, int tau) {
   return h->lp.cm_ring + (size_t)cfz::comm_slot(tau, h->lp.cm_max_age) * comm_args(h).slot_stride;
@@ -1101,7 +1212,7 @@ void record_slice(const cfz_handle *h, double *&rec, int32_t *&rec_si) {
   rec_si = h->lp.rec ? h->lp.rec_si + (size_t)h->lp.rec_used * 2 * B : nullptr;
 }
 
-// One round of a stepwise iteration (cfz_loop_step): loop_prep, solve_kernel, loop_post for n_inst instances.  Jacobi: all B of them,
+// One round of a stepwise iteration (cfz_loop_step): loop_prep, solve_kernel (solve_kernel_pool while a problem pool is set), loop_post for n_inst instances.  Jacobi: all B of them,
 // xperm and xrank NULL; round r of the sequential exchange: the S vehicles of rank r.  dispatch (NULL: index order) lists the instance
 // ids in the order the solve's workgroups take them; the carry slot of instance b is b either way.
 int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const int32_t *xperm, const int32_t *xrank) {
@@ -1115,10 +1226,12 @@ int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const 
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->lp.T, h->lp.ref_table,
                      h->lp.table_of, h->lp.kidx, h->lp.pred, h->lp.state, h->x0, h->ref, h->nbr, h->zu, r, xperm, xrank, dz, h->lp.steps_done, cm);
   HIP_OK(hipGetLastError());
-  if (launch_solve(h, S * V, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, dispatch, 1, n_inst)) return -1;
+  const bool pool = h->lp.pb_on;  // the scenario's own problem: solve_kernel_pool, and its input box in loop_post
+  if (launch_solve(h, S * V, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, dispatch, 1, n_inst, pool)) return -1;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
                      h->status, h->iters, h->zu, h->lp.pred, h->lp.state, h->lp.kidx, rec, rec_si, r, xperm, dz, h->lp.steps_done, bd[8], bd[9], bd[10],
-                     bd[11], nullptr, h->lp.cm_on ? comm_message(h, h->lp.steps_done) : nullptr);
+                     bd[11], nullptr, h->lp.cm_on ? comm_message(h, h->lp.steps_done) : nullptr, pool ? h->lp.pb_pool : nullptr,
+                     pool ? h->lp.pb_of : nullptr);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1365,6 +1478,72 @@ int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop, int ma
   return 0;
 }
 
+int cfz_problem_check(const cfz_spec *base, const cfz_options *base_opt, const cfz_spec *spec, const cfz_options *opt) {
+  if (!base || !spec) return fail("null argument");
+  cfz_options bd;
+  if (!base_opt) { cfz_default_options(&bd); base_opt = &bd; }
+  if (!opt) opt = base_opt;
+  if (spec_shape_ok(spec) || options_ok(opt)) return -1;
+  // geometry and time base are the handle's: the plant, the audit, the layout and the carry records are built from them
+  if (spec->N != base->N) return fail("problem differs from the handle in N");
+  if (spec->n_obs != base->n_obs) return fail("problem differs from the handle in n_obs");
+  if (spec->n_nbr != base->n_nbr) return fail("problem differs from the handle in n_nbr");
+  if (spec->rk_substeps != base->rk_substeps) return fail("problem differs from the handle in rk_substeps");
+  if (spec->dt != base->dt) return fail("problem differs from the handle in dt");
+  if (spec->wb != base->wb) return fail("problem differs from the handle in wb");
+  if (memcmp(spec->g, base->g, sizeof spec->g)) return fail("problem differs from the handle in g");
+  for (int j = 0; j < spec->n_obs; ++j) {
+    if (memcmp(spec->A_obs[j], base->A_obs[j], sizeof spec->A_obs[j])) return fail(("problem differs from the handle in A_obs[" + std::to_string(j) + "]").c_str());
+    if (memcmp(spec->b_obs[j], base->b_obs[j], sizeof spec->b_obs[j])) return fail(("problem differs from the handle in b_obs[" + std::to_string(j) + "]").c_str());
+  }
+  if ((opt->carry_duals != 0) != (base_opt->carry_duals != 0)) return fail("problem differs from the handle in carry_duals");
+  static const char *const box[6] = {"x", "y", "v", "delta", "a", "w"};
+  for (int i = 0; i < 6; ++i)
+    if (!(spec->bounds[2 * i] <= spec->bounds[2 * i + 1]) || !std::isfinite(spec->bounds[2 * i]) || !std::isfinite(spec->bounds[2 * i + 1]))
+      return fail((std::string("bounds: the box of ") + box[i] + " has lo > hi or is not finite").c_str());
+  cfz::KSpec k;
+  return fill_kspec(k, spec, opt);
+}
+
+int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz_options *opts, const int32_t *problem_of) {
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (P < 0) return fail("P must not be negative");
+  HIP_OK(hipSetDevice(h->device));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (P == 0 || !specs) { h->lp.pb_on = false; return 0; }  // off: the kernels without it
+  if (!problem_of) return fail("null problem_of");
+  const int S = h->lp.S;
+  for (int s = 0; s < S; ++s)
+    if (problem_of[s] < 0 || problem_of[s] >= P) return fail("problem_of[s] outside [0, P)");
+  std::vector<KArgs> pool((size_t)P);
+  for (int p = 0; p < P; ++p) {
+    const cfz_options *o = opts ? &opts[p] : &h->opt0;
+    if (cfz_problem_check(&h->spec0, &h->opt0, &specs[p], o)) { cfz_g_err = "problem " + std::to_string(p) + ": " + cfz_g_err; return -1; }
+    if (fill_kspec(pool[p].sp, &specs[p], o)) return -1;
+    pool[p].sp.obs_tab = h->obs_tab;
+    pool[p].dv = cfz::derive(pool[p].sp); pool[p].L = h->lay;
+  }
+  if (!h->lp.pb_dz) {  // kept only once it is all zero: a failure here leaves no buffer that a later call would take for one
+    const size_t nz = ((size_t)cfz::kDisturbN + S) * 8 + (size_t)S * 4;
+    void *z = nullptr;
+    HIP_OK(hipMalloc(&z, nz));
+    if (hipMemset(z, 0, nz) != hipSuccess) { dev_free(z); return fail("hipMemset of the pool's zero disturbance failed"); }
+    h->lp.pb_dz = z;
+  }
+  // the new setting is written into blocks of its own and swapped in once it is complete: a failure leaves the one in force as it was
+  KArgs *d = nullptr;
+  int32_t *of = nullptr;
+  hipError_t e = hipMalloc(&d, (size_t)P * sizeof(KArgs));
+  if (e == hipSuccess) e = hipMalloc(&of, (size_t)S * 4);
+  if (e == hipSuccess) e = hipMemcpy(d, pool.data(), (size_t)P * sizeof(KArgs), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(of, problem_of, (size_t)S * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { dev_free(d); dev_free(of); return fail("cfz_loop_set_problems: device copy of the pool", e); }
+  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
+  h->lp.pb_pool = d; h->lp.pb_of = of; h->lp.pb_cap = P;
+  h->lp.pb_on = true;
+  return 0;
+}
+
 int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered) {
   if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
   if (!h->lp.cm_on) return fail("no lossy exchange is set (cfz_loop_set_comm)");
@@ -1429,8 +1608,8 @@ int cfz_loop_run(cfz_handle *h, int K) {
   int ncu = 0;
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
-  const bool seq = h->lp.xperm != nullptr, dist = h->lp.dz_on, comm = h->lp.cm_on;
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kLoopKernel[comm ? 2 : dist][seq], cfz::kNL, h->lds_bytes));
+  const bool seq = h->lp.xperm != nullptr, dist = h->lp.dz_on, comm = h->lp.cm_on, pool = h->lp.pb_on;
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kLoopKernel[pool][comm ? 2 : dist][seq], cfz::kNL, h->lds_bytes));
   per_cu = std::min(per_cu, h->blocks_per_cu);  // the 2 KiB LDS granules (cfz_create): what the hardware really keeps resident
   if (per_cu < 1) return fail("loop kernel does not fit on a CU");
   // one workgroup per resident slot: more would only queue behind them (any workgroup can serve any item, so a surplus
@@ -1475,13 +1654,17 @@ int cfz_loop_run(cfz_handle *h, int K) {
   record_slice(h, rec, rec_si);
   const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
   const cfz::DisturbArgs dz = disturb_args(h);
-  // the six kernels share their arguments up to the record; `tail` is the exchange order, the disturbance and the comm setting
+  // the ten kernels share their arguments up to the record; `tail` is the exchange order, the disturbance, the comm setting and the pool
   auto launch = [&](auto kernel, auto... tail) {
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->lp.T, h->lp.ref_table, h->lp.table_of,
                        h->lp.kidx, 0, h->lp.pred2, h->lp.state, h->lp.scratch, h->lp.queue, h->lp.ctrl, h->lp.done, h->status, h->iters, h->stats, h->lp.iter_sum,
                        h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, tail...);
   };
-  if (comm && seq) launch(loop_kernel_seq_comm, h->lp.xperm, h->lp.xrank, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
+  if (pool && comm && seq) launch(loop_kernel_seq_pool_comm, h->lp.xperm, h->lp.xrank, pool_disturb_args(h), h->lp.steps_done, comm_args(h), h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
+  else if (pool && comm) launch(loop_kernel_pool_comm, pool_disturb_args(h), h->lp.steps_done, comm_args(h), h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
+  else if (pool && seq) launch(loop_kernel_seq_pool, h->lp.xperm, h->lp.xrank, pool_disturb_args(h), h->lp.steps_done, h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
+  else if (pool) launch(loop_kernel_pool, pool_disturb_args(h), h->lp.steps_done, h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
+  else if (comm && seq) launch(loop_kernel_seq_comm, h->lp.xperm, h->lp.xrank, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
   else if (comm) launch(loop_kernel_comm, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
   else if (dist && seq) launch(loop_kernel_seq_dist, h->lp.xperm, h->lp.xrank, dz, h->lp.steps_done);
   else if (dist) launch(loop_kernel_dist, dz, h->lp.steps_done);

@@ -1,9 +1,11 @@
 // cfz_loop_body.inl -- the body of the persistent closed-loop kernels loop_kernel, loop_kernel_seq, their disturbed variants
-// loop_kernel_dist, loop_kernel_seq_dist and the lossy-exchange variants loop_kernel_comm, loop_kernel_seq_comm (cfz_engine.hip),
-// included inside all six.  The including kernel defines `constexpr bool kSeq` and the exchange order arrays `xperm`, `xrank`
+// loop_kernel_dist, loop_kernel_seq_dist, the lossy-exchange variants loop_kernel_comm, loop_kernel_seq_comm and the problem-pool variants
+// loop_kernel_pool, loop_kernel_seq_pool, loop_kernel_pool_comm, loop_kernel_seq_pool_comm (cfz_engine.hip), included inside all ten.  The including kernel defines `constexpr bool kSeq` and the exchange order arrays `xperm`, `xrank`
 // (nullptr for the Jacobi kernels), `constexpr bool kDist` and the disturbance setting `dz` with the step count `step0` (unused
 // constants in the undisturbed kernels), `constexpr bool kComm` and the comm setting `cm` (an unused constant in the kernels
-// without it); everything else is the kernel's arguments.
+// without it), `constexpr bool kPool`, the pool of problems `pool`, `problem_of` of cfz_loop_set_problems (nullptr constants in the
+// kernels without it) and `dz_clip`, whether a disturbance is set and the applied input is therefore clipped to the problem's input box
+// (the pool kernels' argument; true in the others, which run only under a setting that clips); everything else is the kernel's arguments.
   extern __shared__ double smem[];
   const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
   const int N = sp.N, nn = sp.n_nbr, B = S * V, tid = threadIdx.x, lane = tid & 63;
@@ -66,6 +68,11 @@
       if (t <= CFZ_LD(&ctrl[0]) + prio_lag) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
     }
     const int s = b / V, v = b - s * V;
+    // kPool: the constants of the scenario's problem, pool[problem_of[s]], in place of the handle's block; the index is the same in
+    // every lane of both wavefronts, so the block is still read through scalar loads.  N, n_nbr and the layout L stay the handle's.
+    const KArgs *const kp = kPool ? pool + __builtin_amdgcn_readfirstlane(problem_of[s]) : ka;
+    const cfz::KSpec &spi = kPool ? kp->sp : sp;
+    const cfz::KDer &dvi = kPool ? kp->dv : dv;
     // kComm: the ring of messages indexed by the absolute iteration instead of the parity pair (cfz_comm.inl)
     const double *pin = kComm ? cm.ring + (size_t)cfz::comm_slot(step0 + t - 1, cm.max_age) * cm.slot_stride
                               : pred + (size_t)(t & 1) * B * 7 * N;   // predictions after iteration t-1
@@ -123,7 +130,7 @@
     CFZ_MARK(3);
     int oi[2]; double od[3];
     cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    cfz::solve_instance(sp, dv, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
+    cfz::solve_instance(spi, dvi, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
     __syncthreads();
     CFZ_MARK(4);
     // ---- read-back (the solution is still in the workspace) or shift fallback (:484-524), plant (:528-543) ------------
@@ -141,8 +148,12 @@
         for (int i = 0; i < 5; ++i) z[i] = smem[L.x0 + i];
       } else {  // the plant starts from the true state (x0 holds the measurement) with the disturbed, clipped input
         for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
-        a0 = cfz::disturb_clip(cfz::disturb_add(a0, dn[0]), sp.bounds[8], sp.bounds[9]);
-        w0 = cfz::disturb_clip(cfz::disturb_add(w0, dn[1]), sp.bounds[10], sp.bounds[11]);
+        if (!kPool || dz_clip) {
+          a0 = cfz::disturb_clip(cfz::disturb_add(a0, dn[0]), spi.bounds[8], spi.bounds[9]);
+          w0 = cfz::disturb_clip(cfz::disturb_add(w0, dn[1]), spi.bounds[10], spi.bounds[11]);
+        } else {  // a pool kernel standing in for the undisturbed one: no disturbance is set, so nothing is clipped either
+          a0 = cfz::disturb_add(a0, dn[0]); w0 = cfz::disturb_add(w0, dn[1]);
+        }
       }
       cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
       if (kDist)

@@ -167,6 +167,9 @@ def load_library(path=None):
     if hasattr(lib, "cfz_loop_set_comm"):
         lib.cfz_loop_set_comm.argtypes = [vp, C.c_uint64, vp, C.c_int, C.c_int, vp]
         lib.cfz_loop_comm.argtypes = [vp, C.c_int, C.c_int, vp]
+    if hasattr(lib, "cfz_loop_set_problems"):
+        lib.cfz_problem_check.argtypes = [C.POINTER(_CSpec), C.POINTER(_COptions), C.POINTER(_CSpec), C.POINTER(_COptions)]
+        lib.cfz_loop_set_problems.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.cfz_loop_record.argtypes = [vp, C.c_int]
     lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -180,7 +183,7 @@ EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
-    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm"
+    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -196,6 +199,37 @@ def default_options(**overrides):
             raise TypeError(f"unknown solver option {k!r}")
         setattr(o, k, v)
     return o
+
+
+def problem_check(base, spec, base_options=None, **options):
+    """`cfz_problem_check`: may `spec` stand in a problem pool (`Engine.loop_set_problems`) of an engine created with `base` and the
+    default options changed by the dict `base_options`?  `options` are the entry's overrides, applied to the engine's options as
+    `loop_set_problems` applies them.  Host arithmetic, needs no GPU.  Raises ValueError with the library's text, which names the first
+    field that differs from the handle (geometry, time base, carry_duals) or is invalid.  `Engine.problem_check` passes its own."""
+    lib = load_library()
+    base_options = dict(base_options or {})
+    cb, cs, bo, co = base.to_c(), spec.to_c(), default_options(**base_options), default_options(**{**base_options, **options})
+    if lib.cfz_problem_check(C.byref(cb), C.byref(bo), C.byref(cs), C.byref(co)) != 0:
+        raise ValueError("cfz_problem_check: " + lib.cfz_last_error().decode())
+
+
+def pack_problems(problems, options=None):
+    """The arrays `cfz_loop_set_problems` takes: problems is a sequence of ProblemSpec or (ProblemSpec, {option overrides}), the overrides
+    applied to `options` (a dict of overrides of the default options: what the engine was created with) -> (P, cfz_spec[P], cfz_options[P]);
+    None -> (0, None, None), which switches the pool off."""
+    if problems is None:
+        return 0, None, None
+    problems = list(problems)
+    if not problems:
+        raise ValueError("a problem pool needs at least one problem (None switches it off)")
+    specs, opts = (_CSpec * len(problems))(), (_COptions * len(problems))()
+    for p, item in enumerate(problems):
+        spec, over = item if isinstance(item, tuple) else (item, {})
+        if not isinstance(spec, ProblemSpec) or not isinstance(over, dict):
+            raise TypeError(f"problems[{p}] must be a ProblemSpec or (ProblemSpec, dict of option overrides)")
+        specs[p] = spec.to_c()
+        opts[p] = default_options(**{**(options or {}), **over})
+    return len(problems), specs, opts
 
 
 def _ptr(a):
@@ -443,6 +477,7 @@ class Engine:
         self.lib = load_library()
         self.spec = spec
         self.max_batch = int(max_batch)
+        self.options = dict(options)  # (the base of the overrides of loop_set_problems)
         self._h = C.c_void_p()
         cs, co = spec.to_c(), default_options(**options)
         if self.lib.cfz_create(C.byref(cs), C.byref(co), int(device), self.max_batch, C.byref(self._h)) != 0:
@@ -674,6 +709,26 @@ class Engine:
         b = np.empty((max(int(K), 0), S, V, V), np.int32)
         self._ck(self.lib.cfz_loop_comm(self._h, int(tau0), int(K), _ptr(b)), "cfz_loop_comm")
         return b.astype(bool)
+
+    def problem_check(self, spec, **options):
+        """`problem_check` against this engine's spec and the options it was created with: what `loop_set_problems` will decide."""
+        problem_check(self.spec, spec, self.options, **options)
+
+    def loop_set_problems(self, problems, problem_of=None):
+        """`cfz_loop_set_problems`: per-scenario problem constants on the later steps and runs of the closed loop (include/confrez_hip.h).
+        problems: a sequence of ProblemSpec or (ProblemSpec, {option overrides}), the overrides applied to the options this engine was
+        created with; problem_of [S]: the problem of each scenario.  Every solve of scenario s then uses that problem's dmin, bounds,
+        weights and options; geometry, time base and carry_duals must be the engine's (`problem_check`).  None: off again, what
+        `loop_init` restores."""
+        P, specs, opts = pack_problems(problems, self.options)
+        if P == 0 or not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+            self._ck(self.lib.cfz_loop_set_problems(self._h, P, specs, opts, None), "cfz_loop_set_problems")
+            return
+        po = np.asarray(problem_of)
+        if po.dtype.kind not in "iu" or po.shape != (self._S,):
+            raise ValueError(f"problem_of must hold {self._S} integers, got shape {po.shape}, dtype {po.dtype}")
+        po = np.ascontiguousarray(po, dtype=np.int32)
+        self._ck(self.lib.cfz_loop_set_problems(self._h, P, specs, opts, _ptr(po)), "cfz_loop_set_problems")
 
     def loop_step(self):
         self._ck(self.lib.cfz_loop_step(self._h), "cfz_loop_step")

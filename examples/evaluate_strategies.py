@@ -16,12 +16,17 @@
    message lost with that probability (`Engine.loop_set_comm`: a vehicle plans against the newest message that arrived, at most
    --max-age iterations old, advanced by its age unless --no-compensate); the replicas of a start share one stream id, so the rates
    are compared on common random numbers.  Contact-free starts and the smallest clearances are printed per rate.
+   --dmin 0.05,0.1,0.2: every (strategy, start) (and noise level, and drop rate) runs once per clearance in the same launch, each replica
+   solving the NLP with that dmin (`Engine.loop_set_problems`: a pool of one problem per value); the replicas of a start share its
+   stream ids.  Contact-free starts and the smallest clearances are printed per value.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
                                               [--noise-levels L0,L1,...] [--noise-seed SEED]
                                               [--drop-rates P0,P1,...] [--max-age A] [--no-compensate] [--comm-seed SEED]
+                                              [--dmin D0,D1,...]
 """
 import argparse
+import dataclasses
 import os
 import sys
 import time
@@ -32,6 +37,30 @@ import numpy as np  # noqa: E402
 
 # standard deviations at noise level 1: measurement and process noise on (x, y, psi, v, delta), actuator noise on (a, w)
 NOISE_SIGMA = dict(meas=(0.02, 0.02, 0.005, 0.02, 0.0), act=(0.05, 0.02), proc=(0.005, 0.005, 0.002, 0.01, 0.0))
+
+
+def replicate(k0, noise, tof, levels=None, rates=None, dmins=None):
+    """The batch of one launch: every scenario of (k0 [S0], noise [S0,V,5], tof [S0]) once per noise level, drop rate and clearance.
+    Blocks nest in that order: block l of the first S0 * L scenarios is every start at level l; block r of the first S0 * L * R is all of
+    those at rate r; block d is all of those under problem d.  Every replica of start i keeps stream id i, for the noise and for the
+    delivery alike, so that the values of each axis are compared on common random numbers.
+    -> dict(k0, noise, tof, level, stream, drop, problem_of), each [S] (level, drop, problem_of None where that axis is not given)."""
+    S0 = len(k0)
+    out = dict(k0=np.asarray(k0), noise=np.asarray(noise), tof=np.asarray(tof), level=None, stream=np.arange(S0, dtype=np.uint32), drop=None,
+               problem_of=None)
+
+    def tile(n):
+        for k in ("k0", "tof", "level", "stream", "drop", "problem_of"):
+            if out[k] is not None:
+                out[k] = np.tile(out[k], n)
+        out["noise"] = np.tile(out["noise"], (n, 1, 1))
+
+    for name, values, dtype in (("level", levels, float), ("drop", rates, float), ("problem_of", None if not dmins else range(len(dmins)), np.int32)):
+        if values:
+            S = len(out["k0"])
+            tile(len(values))
+            out[name] = np.repeat(np.asarray(values, dtype), S)
+    return out
 
 
 def main():
@@ -50,6 +79,8 @@ def main():
     ap.add_argument("--max-age", type=int, default=3, help="oldest message a vehicle plans against, in iterations (1..6)")
     ap.add_argument("--no-compensate", action="store_true", help="advance a stale message as if it were new (the reference's node), not by its age")
     ap.add_argument("--comm-seed", type=int, default=2024, help="seed of the delivery streams")
+    ap.add_argument("--dmin", type=lambda t: [float(x) for x in t.split(",")], default=None,
+                    help="comma-separated clearances of the NLP, e.g. 0.05,0.1,0.2: one replica of every start per value, in one launch")
     a = ap.parse_args()
 
     import torch
@@ -79,27 +110,18 @@ def main():
         k0, nz = scenarios.sample_scenarios(M, plan["tables"][p], seed=a.seed + int(p), spec=spec)
         k0s.append(k0); noises.append(nz); tof.append(np.full(M, p, np.int32))
     k0, noise, tof = np.concatenate(k0s), np.concatenate(noises), np.concatenate(tof)
-    levels = a.noise_levels
-    lvl = None
+    levels, rates, dmins = a.noise_levels, a.drop_rates, a.dmin
+    rep = replicate(k0, noise, tof, levels, rates, dmins)
+    k0, noise, tof, lvl, streams, drop, pof = (rep[k] for k in ("k0", "noise", "tof", "level", "stream", "drop", "problem_of"))
+    comm_streams = streams
     if levels:
-        # replicas: block l of the batch is every (strategy, start) at level l, on the stream of its start
-        S0, L = len(k0), len(levels)
-        k0, noise, tof = np.tile(k0, L), np.tile(noise, (L, 1, 1)), np.tile(tof, L)
-        lvl, streams = np.repeat(np.asarray(levels, float), S0), np.tile(np.arange(S0, dtype=np.uint32), L)
         print(f"noise levels {levels} x sigma: meas {NOISE_SIGMA['meas']}, act {NOISE_SIGMA['act']}, proc {NOISE_SIGMA['proc']}; "
-              f"noise seed {a.noise_seed}, one stream per start shared by its {L} replicas")
-    rates = a.drop_rates
-    drop = None
+              f"noise seed {a.noise_seed}, one stream per start shared by its {len(levels)} replicas")
     if rates:
-        # replicas again: block r is the whole batch so far (noise levels included) at rate r, every replica on the stream of its start
-        S1, R = len(k0), len(rates)
-        base = np.arange(S1, dtype=np.uint32) % np.uint32(len(k0s) * M)
-        k0, noise, tof = np.tile(k0, R), np.tile(noise, (R, 1, 1)), np.tile(tof, R)
-        if levels:
-            lvl, streams = np.tile(lvl, R), np.tile(streams, R)
-        drop, comm_streams = np.repeat(np.asarray(rates, float), S1), np.tile(base, R)
         print(f"drop rates {rates}, max age {a.max_age}, {'no ' if a.no_compensate else ''}age compensation; comm seed {a.comm_seed}, "
               f"one stream per start shared by its replicas")
+    if dmins:
+        print(f"clearances dmin {dmins}: one problem per value in the pool, every replica of a start on its streams")
     S = len(k0)
     eng = engine.Engine(spec, max_batch=S * V, device=a.device)
     eng.loop_init(plan["tables"], k0, noise, table_of=tof)
@@ -109,6 +131,8 @@ def main():
         eng.loop_set_order(np.array([combos[p][0][0] for p in tof], np.int32))
     if rates:
         eng.loop_set_comm(a.comm_seed, drop, max_age=a.max_age, compensate=not a.no_compensate, stream=comm_streams)
+    if dmins:
+        eng.loop_set_problems([dataclasses.replace(spec, dmin=d) for d in dmins], pof)
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -134,7 +158,7 @@ def main():
         done = arr.min(1) >= 0  # every vehicle of the scenario arrived
         last = arr.max(1)[done]
         n_contact = int((aud["first_contact"][sel] >= 0).sum())
-        n_sel = int(sel.sum())  # M starts x noise levels x drop rates
+        n_sel = int(sel.sum())  # M starts x noise levels x drop rates x clearances
         print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{n_sel:<2d} "
               f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
               + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or []))
@@ -145,7 +169,12 @@ def main():
         free = int((aud["first_contact"][sel] < 0).sum())
         print(f"drop rate {r:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
               f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
-    print(f"strategies whose {M * len(levels or [1]) * len(rates or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
+    for i, d in enumerate(dmins or []):
+        sel = pof == i
+        free = int((aud["first_contact"][sel] < 0).sum())
+        print(f"dmin {d:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
+              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
+    print(f"strategies whose {M * len(levels or [1]) * len(rates or [1]) * len(dmins or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms")
     eng.close()
 

@@ -469,6 +469,34 @@ int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop /* [S],
                       int compensate /* 0 | 1 */, const uint32_t *stream /* [S] or NULL: s */);
 int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered /* [K][S][V][V], diagonal 1 */);
 
+/* ---- per-scenario problem constants of the closed loop ------------------------------------------------------------------------------
+ * The constants of the NLP are what `setup_controller(dt, N, dmin)` bakes into the graph once per follower (vehicle_follower.py:146-368);
+ * above they are the handle's, one set for every scenario.  A *problem* is a pair (cfz_spec, cfz_options).  With a pool of P problems
+ * and problem_of[S], every solve of scenario s (cfz_loop_step and cfz_loop_run alike, under either exchange rule, with or without
+ * disturbances and lossy exchange) uses problem problem_of[s]: its dmin, bounds and weights, every field of cfz_options, the constants
+ * derived from them, and the stage-0 feasibility test that yields status 4.  The clip of the disturbed input (cfz_loop_set_disturbance,
+ * step 3) uses that problem's input box, and happens only while a disturbance is set: with none set the applied input is clipped to
+ * no box, under cfz_loop_step and cfz_loop_run alike.  (Without a pool, cfz_loop_run under cfz_loop_set_comm alone does clip to the
+ * handle's box.  A pool of the handle's own problem therefore equals no pool under comm as long as every applied input lies inside
+ * that box: a converged solve's always does, a shift fallback's does when the inputs of the plan that seeded the predictions do.)
+ * The handle's, whatever the pool says: geometry and time base (N, n_obs, n_nbr, rk_substeps, dt, wb, g, A_obs, b_obs: the plant, the
+ * audit, the workspace layout and the carry records are built from them) and cfz_options.carry_duals (the carry records are sized by
+ * cfz_create).  A pool entry that differs from the handle in any of these is refused, and cfz_last_error names the field.
+ * Everything else about a step is unchanged and per scenario as before: reference window, warm start, carried multipliers (slot b),
+ * exchange rule, disturbances, lossy exchange, read-back or fallback, plant, record, audit (which measures signed distance, not dmin).
+ * The setting holds until it is changed and may change between calls, at a step boundary; carried multipliers stay (a warm start, not
+ * a promise).  cfz_loop_init / cfz_loop_init_tables switch it off.  Off is the default, and with it off the kernels that ran before
+ * run again.  cfz_vsl_step and the host-buffer path cfz_mpc_solve* always use the handle's constants.
+ * cfz_problem_check: host arithmetic, no device.  0 if (spec, opt) may stand in a pool of a handle created with (base, base_opt), else -1
+ * and cfz_last_error names the first field that differs or is invalid.  The value checks are cfz_create's own (sizes, filter_cap,
+ * restoration, reg_dual_rows, resto_first, obstacles that are bounded quadrilaterals), and every box of `bounds` must have lo <= hi, both
+ * finite.  base_opt NULL: the default options; opt NULL: base_opt.
+ * cfz_loop_set_problems: specs[P], opts[P] (NULL: the handle's options for every entry), problem_of[S]; P = 0 or specs NULL: off.
+ * Refused, the loop's state and the setting in force staying: a call before cfz_loop_init, P < 0, a problem_of[s] outside [0, P), any
+ * entry that cfz_problem_check refuses (the text is then prefixed with "problem p: "). */
+int cfz_problem_check(const cfz_spec *base, const cfz_options *base_opt, const cfz_spec *spec, const cfz_options *opt);
+int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz_options *opts, const int32_t *problem_of);
+
 /* ---- closed loop over per-scenario plans -------------------------------------------------------
  * tables[P][V][T][7]: a pool of P plan sets (each what cfz_loop_init takes as ref_table); scenario s follows set table_of[s]
  * (NULL: set s, which needs P == S).  Otherwise exactly cfz_loop_init, which is this call with P = 1 and every scenario on set 0.
