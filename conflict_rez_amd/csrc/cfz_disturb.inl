@@ -46,6 +46,8 @@ struct DisturbArgs {
   const uint32_t *stream;
 };
 
+CFZ_CALL DisturbArgs disturb_none() { return {0, nullptr, nullptr, nullptr}; }
+
 CFZ_CALL uint32_t disturb_mulhi(uint32_t a, uint32_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __umulhi(a, b);

@@ -25,7 +25,10 @@
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
 // (loop_release).  cfz_loop_step is loop_round (prep, solve, post) once for Jacobi or V times for the sequential exchange;
-// cfz_loop_run picks its kernel from kLoopKernel[pool][setting][sequential].
+// cfz_loop_run picks its kernel from kLoopVariants, the one list of the persistent kernels (loop_variant maps the setting in force
+// to its row).  A setting is stated once on the host side: its fields in cfz_handle::Loop, its device block through upload_setting,
+// its kernel arguments through disturb_args / comm_args, its kernels as rows of kLoopVariants and lines of cfz_loop_run's chain.
+// Entry points of the closed loop open with loop_ready.
 
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -37,6 +40,7 @@
 #include <unistd.h>
 #include <cmath>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/confrez_hip.h"
@@ -62,37 +66,15 @@ struct KArgs { cfz::KSpec sp; cfz::KDer dv; cfz::Lay L; };
 #ifndef CFZ_WAVES_PER_SIMD
 #define CFZ_WAVES_PER_SIMD 2
 #endif
+// Two kernels, one body (cfz_solve_body.inl, included into both, as the persistent kernels share cfz_loop_body.inl).
 __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(const KArgs *__restrict__ ka, int B, const double *x0,
                                                    const double *ref, const double *nbr, double *zu, int32_t *status,
                                                    int32_t *iters, double *stats, DualPtrs du, const int32_t *order,
                                                    double *wst, int wst_stride, const int32_t *carry, int carry_all,
                                                    const int32_t *slots) {
-  extern __shared__ double smem[];
-  if ((int)blockIdx.x >= B) return;
-  const cfz::KSpec &sp = ka->sp; const cfz::KDer &dv = ka->dv; const cfz::Lay &L = ka->L;
-  // workgroups are dispatched in index order: `order` puts the instances expected to run longest first
-  const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
-  const int N = sp.N, no = sp.n_obs, nn = sp.n_nbr;
-  int oi[2]; double od[3];
-  cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-#ifdef CFZ_STAMPS
-  duo.stamps = reinterpret_cast<unsigned long long *>(stats) + (size_t)B * 3 + (size_t)b * 24;  // diagnostic build: stats has room
-#endif
-  if (du.l) {
-    duo.l = du.l + (size_t)b * N * 4 * no; duo.mm = du.m + (size_t)b * N * 4 * no;
-    duo.lam_ij = du.lam_ij + (size_t)b * nn * N * 4; duo.lam_ji = du.lam_ji + (size_t)b * nn * N * 4;
-    duo.s = du.s + (size_t)b * nn * N * 2;
-  }
-  // carry record of the instance's slot (default: slot b): used when the caller says that this solve is the successor of
-  // the previous one in that slot
-  const int slot = slots ? slots[b] : b;
-  cfz::solve_instance(sp, dv, x0 + (size_t)b * 5, ref + (size_t)b * 3 * N, nbr + (size_t)b * nn * 3 * N,
-                      zu + (size_t)b * 7 * N, smem, L, oi, od, duo, wst ? wst + (size_t)slot * wst_stride : nullptr,
-                      carry_all || (carry && carry[b]));
-  if (threadIdx.x == 0) {
-    iters[b] = oi[0]; status[b] = oi[1];
-    stats[b * 3 + 0] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
-  }
+  constexpr bool kPool = false;
+  const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr int V = 1;
+#include "cfz_solve_body.inl"
 }
 
 // solve_kernel for the stepwise closed loop under cfz_loop_set_problems: instance b = (scenario s, vehicle) of V solves the problem
@@ -104,27 +86,8 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel_poo
                                                    double *wst, int wst_stride, const int32_t *carry, int carry_all,
                                                    const int32_t *slots, const KArgs *__restrict__ pool,
                                                    const int32_t *__restrict__ problem_of, int V) {
-  extern __shared__ double smem[];
-  if ((int)blockIdx.x >= B) return;
-  const int b = order ? order[blockIdx.x] : (int)blockIdx.x;
-  const KArgs *const kp = pool + __builtin_amdgcn_readfirstlane(problem_of[b / V]);
-  const cfz::KSpec &sp = kp->sp; const cfz::KDer &dv = kp->dv; const cfz::Lay &L = ka->L;
-  const int N = ka->sp.N, no = ka->sp.n_obs, nn = ka->sp.n_nbr;
-  int oi[2]; double od[3];
-  cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (du.l) {
-    duo.l = du.l + (size_t)b * N * 4 * no; duo.mm = du.m + (size_t)b * N * 4 * no;
-    duo.lam_ij = du.lam_ij + (size_t)b * nn * N * 4; duo.lam_ji = du.lam_ji + (size_t)b * nn * N * 4;
-    duo.s = du.s + (size_t)b * nn * N * 2;
-  }
-  const int slot = slots ? slots[b] : b;
-  cfz::solve_instance(sp, dv, x0 + (size_t)b * 5, ref + (size_t)b * 3 * N, nbr + (size_t)b * nn * 3 * N,
-                      zu + (size_t)b * 7 * N, smem, L, oi, od, duo, wst ? wst + (size_t)slot * wst_stride : nullptr,
-                      carry_all || (carry && carry[b]));
-  if (threadIdx.x == 0) {
-    iters[b] = oi[0]; status[b] = oi[1];
-    stats[b * 3 + 0] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
-  }
+  constexpr bool kPool = true;
+#include "cfz_solve_body.inl"
 }
 
 // ---- closed loop ------------------------------------------------------------------------------
@@ -198,12 +161,11 @@ __global__ void advance_clock(int S, int K, int32_t *kidx) {
 // carry (NULL: none; cfz_vsl_step): the carry flag of the next iteration, a vehicle whose solve converged starts its next one from
 // these multipliers.
 // msg (NULL: none; cfz_loop_set_comm): this iteration's slot [S][V][7][N] of the ring of messages, which takes the posted prediction too.
-// pool, problem_of (NULL: none; cfz_loop_set_problems): the input box is that of the scenario's problem instead of the four scalars.
-__global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_substeps, const int32_t *status,
-                          const int32_t *iters, const double *zu, double *pred, double *state, int32_t *kidx, double *rec,
-                          int32_t *rec_si, int r, const int32_t *xperm, cfz::DisturbArgs dz, int step, double a_lo, double a_hi,
-                          double w_lo, double w_hi, int32_t *carry, double *msg, const KArgs *pool,
-                          const int32_t *problem_of) {
+// ka: the handle's block, which gives dt, wb and the input box (bounds[8:12]); pool, problem_of (NULL: none; cfz_loop_set_problems):
+// the block of the scenario's problem instead (dt and wb are the handle's in every problem, cfz_problem_check).
+__global__ void loop_post(int S, int V, int N, const KArgs *ka, const int32_t *status, const int32_t *iters, const double *zu,
+                          double *pred, double *state, int32_t *kidx, double *rec, int32_t *rec_si, int r, const int32_t *xperm,
+                          cfz::DisturbArgs dz, int step, int32_t *carry, double *msg, const KArgs *pool, const int32_t *problem_of) {
   int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (xperm ? S : S * V)) return;
   if (xperm) b = b * V + xperm[b * V + r];
@@ -220,15 +182,12 @@ __global__ void loop_post(int S, int V, int N, double dt, double wb, int plant_s
   for (int i = 0; i < 5; ++i) z[i] = state[b * 5 + i];
   double a0 = pb[5 * N], w0 = pb[6 * N];
   const int s = b / V, v = b - s * V;
+  const cfz::KSpec &sp = (pool ? pool + problem_of[s] : ka)->sp;
   if (dz.sigma) {
-    if (pool) {
-      const double *bd = pool[problem_of[s]].sp.bounds;
-      a_lo = bd[8]; a_hi = bd[9]; w_lo = bd[10]; w_hi = bd[11];
-    }
-    a0 = cfz::disturb_clip(cfz::disturb_add(a0, cfz::disturb_value(dz, s, v, step, 5)), a_lo, a_hi);
-    w0 = cfz::disturb_clip(cfz::disturb_add(w0, cfz::disturb_value(dz, s, v, step, 6)), w_lo, w_hi);
+    a0 = cfz::disturb_clip(cfz::disturb_add(a0, cfz::disturb_value(dz, s, v, step, 5)), sp.bounds[8], sp.bounds[9]);
+    w0 = cfz::disturb_clip(cfz::disturb_add(w0, cfz::disturb_value(dz, s, v, step, 6)), sp.bounds[10], sp.bounds[11]);
   }
-  cfz::rk4_step<false>(z, a0, w0, dt, wb, plant_substeps, out, nullptr);
+  cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
   if (dz.sigma)
     for (int i = 0; i < 5; ++i) out[i] = cfz::disturb_add(out[i], cfz::disturb_value(dz, s, v, step, 7 + i));
   for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
@@ -325,7 +284,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(CFZ_
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
-  const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
+  const cfz::DisturbArgs dz = cfz::disturb_none();
   const int step0 = 0;
 #include "cfz_loop_body.inl"
 }
@@ -334,7 +293,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(
   constexpr bool kSeq = true, kDist = false, kComm = false, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
-  const cfz::DisturbArgs dz = {0, nullptr, nullptr, nullptr};
+  const cfz::DisturbArgs dz = cfz::disturb_none();
   const int step0 = 0;
 #include "cfz_loop_body.inl"
 }
@@ -415,14 +374,26 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
 }
 #undef CFZ_LOOP_ARGS
 
-// the persistent kernel of a setting, [problem pool][0 plain, 1 disturbed, 2 lossy exchange (with or without disturbance)][sequential];
-// the pool kernels are compiled with disturbances, so plain and disturbed share one pair
-const void *const kLoopKernel[2][3][2] = {{{(const void *)loop_kernel, (const void *)loop_kernel_seq},
-                                           {(const void *)loop_kernel_dist, (const void *)loop_kernel_seq_dist},
-                                           {(const void *)loop_kernel_comm, (const void *)loop_kernel_seq_comm}},
-                                          {{(const void *)loop_kernel_pool, (const void *)loop_kernel_seq_pool},
-                                           {(const void *)loop_kernel_pool, (const void *)loop_kernel_seq_pool},
-                                           {(const void *)loop_kernel_pool_comm, (const void *)loop_kernel_seq_pool_comm}}};
+// The ten persistent kernels, stated once: what each was compiled with (dist: kDist, and so on).  create_fill, the occupancy query and
+// the launch of cfz_loop_run all go through this table; a new kernel is one more row here and one more line in cfz_loop_run's chain.
+struct LoopVariant { const void *fn; bool seq, dist, comm, pool; };
+const LoopVariant kLoopVariants[10] = {
+    {(const void *)loop_kernel, false, false, false, false},          {(const void *)loop_kernel_seq, true, false, false, false},
+    {(const void *)loop_kernel_dist, false, true, false, false},      {(const void *)loop_kernel_seq_dist, true, true, false, false},
+    {(const void *)loop_kernel_comm, false, true, true, false},       {(const void *)loop_kernel_seq_comm, true, true, true, false},
+    {(const void *)loop_kernel_pool, false, true, false, true},       {(const void *)loop_kernel_seq_pool, true, true, false, true},
+    {(const void *)loop_kernel_pool_comm, false, true, true, true},   {(const void *)loop_kernel_seq_pool_comm, true, true, true, true}};
+
+// The row that runs the setting in force.  The comm and the pool kernels exist only with kDist (no full cross product): while no
+// disturbance is set they take the zero-noise block (disturb_args), so every one of the 16 settings has exactly one row.
+int loop_variant(bool seq, bool dz_on, bool cm_on, bool pb_on) {
+  const bool dist = dz_on || cm_on || pb_on;
+  for (int i = 0; i < 10; ++i) {
+    const LoopVariant &v = kLoopVariants[i];
+    if (v.seq == seq && v.dist == dist && v.comm == cm_on && v.pool == pb_on) return i;
+  }
+  return -1;  // (not reached: the ten rows cover the 16 settings)
+}
 
 // delivered[K][S][V][V]: the delivery bits of messages [tau0, tau0 + K) (cfz_loop_comm), receiver before sender, diagonal 1; one thread
 // each, through the function the loop uses
@@ -691,24 +662,24 @@ struct cfz_handle {
     int32_t *rec_si = nullptr;
     int rec_cap = 0, rec_used = 0;
     // disturbances (cfz_loop_set_disturbance; dz_on false: none): one device buffer dz_buf = sigma[12] | level[S] | stream[S] (uint32);
-    // steps_done below is the step count of the streams
-    void *dz_buf = nullptr;
+    // steps_done below is the step count of the streams.  dz_zero: the same block, all zero, from cfz_loop_init_tables on: what the kernels
+    // compiled with kDist take for dz while no disturbance is set (disturb_args).  Zero sigma and level make every d a signed zero
+    // whatever the stream id, and x + (+-0) is x for every x (only the sign of a zero x can follow the stream), so one block with
+    // zero ids serves the comm and the pool kernels alike.
+    void *dz_buf = nullptr, *dz_zero = nullptr;
     uint64_t dz_seed = 0;
     bool dz_on = false;
-    // lossy exchange (cfz_loop_set_comm; cm_on false: none): one device buffer cm_buf = p_drop[S] | zero sigma[12] | zero level[S] |
-    // stream[S] (uint32), the zero setting being what the comm kernels take for dz while no disturbance is set; cm_ring[D][S][V][7][N]
-    // the ring of messages, D = cm_max_age + 2; cm_tau_on the message history starts at
+    // lossy exchange (cfz_loop_set_comm; cm_on false: none): one device buffer cm_buf = p_drop[S] | stream[S] (uint32);
+    // cm_ring[D][S][V][7][N] the ring of messages, D = cm_max_age + 2; cm_tau_on the message history starts at
     void *cm_buf = nullptr;
     double *cm_ring = nullptr;
     uint64_t cm_seed = 0;
     int cm_max_age = 0, cm_compensate = 0, cm_tau_on = 0, cm_ring_slots = 0;
     bool cm_on = false;
     // problem pool (cfz_loop_set_problems; pb_on false: none): pb_pool[pb_cap] the KArgs block {ks_p, derive(ks_p), lay} of every problem
-    // (obs_tab the handle's), pb_of[S] the problem of each scenario; pb_dz = zero sigma[12] | zero level[S] | zero stream[S] (uint32),
-    // what the pool kernels take for dz while neither a disturbance nor a lossy exchange is set
+    // (obs_tab the handle's), pb_of[S] the problem of each scenario
     KArgs *pb_pool = nullptr;
     int32_t *pb_of = nullptr;
-    void *pb_dz = nullptr;
     int pb_cap = 0;
     bool pb_on = false;
     // persistent loop
@@ -731,14 +702,14 @@ int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, cons
   if ((h->carry_set || h->slots_set) && st != h->stream) HIP_OK(hipStreamWaitEvent(st, h->ev_stage, 0));  // staged on the handle's stream
   HIP_OK(hipEventRecord(h->ev0, st));
   const int32_t *carry = h->carry_ext ? h->carry_ext : (h->carry_set ? h->carry : nullptr);
+  auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status, iters, stats, du,
+                       order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all, h->slots_set ? h->slots : nullptr, tail...);
+  };
   if (pool)  // the stepwise closed loop under cfz_loop_set_problems: instance b solves the problem of scenario b / V
-    hipLaunchKernelGGL(solve_kernel_pool, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
-                       iters, stats, du, order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all,
-                       h->slots_set ? h->slots : nullptr, h->lp.pb_pool, h->lp.pb_of, h->ks.n_nbr + 1);
+    launch(solve_kernel_pool, h->lp.pb_pool, h->lp.pb_of, h->ks.n_nbr + 1);
   else
-    hipLaunchKernelGGL(solve_kernel, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status,
-                       iters, stats, du, order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all,
-                       h->slots_set ? h->slots : nullptr);
+    launch(solve_kernel);
   h->carry_set = false; h->slots_set = false; h->carry_ext = nullptr;  // the flags of cfz_mpc_set_carry / cfz_mpc_set_slots hold for one solve
   h->ms_pending = true;
   HIP_OK(hipGetLastError());
@@ -859,8 +830,10 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
   if (const char *pad = std::getenv("CFZ_LDS_PAD")) h->lds_bytes += (size_t)std::atoi(pad);  // occupancy experiments only
   if (h->lds_bytes > 160 * 1024) return fail("problem does not fit the 160 KiB LDS of one CU");
   if (h->lds_bytes > 64 * 1024) {
-    for (const void *kern : {(const void *)solve_kernel, kLoopKernel[0][0][0], kLoopKernel[0][0][1], kLoopKernel[0][1][0], kLoopKernel[0][1][1],
-                             (const void *)solve_kernel_pool, kLoopKernel[1][0][0], kLoopKernel[1][0][1], kLoopKernel[1][2][0], kLoopKernel[1][2][1]}) {
+    // (no shape the ABI admits gets here: the widest, N 32 with 8 obstacles and 7 neighbours, takes 60,216 B (tools/src/loop_variant_check.hip prints it); CFZ_LDS_PAD does)
+    std::vector<const void *> kerns = {(const void *)solve_kernel, (const void *)solve_kernel_pool};
+    for (const LoopVariant &v : kLoopVariants) kerns.push_back(v.fn);
+    for (const void *kern : kerns) {
       const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes);
       if (e != hipSuccess) return fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize)", e);
     }
@@ -1073,9 +1046,8 @@ int cfz_vsl_step(cfz_handle *h, int S, int V, int n_own, const int32_t *d_own, i
   HIP_OK(hipGetLastError());
   h->carry_ext = t > 0 ? d_carry : nullptr;  // iteration 0 has nothing to carry
   if (launch_solve(h, B, h->x0, h->ref, h->nbr, h->zu, d_status, d_iters, d_stats, false, st)) return -1;
-  hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, S, n_own, N, h->ks.dt, h->ks.wb, kPlantSubsteps, d_status,
-                     nullptr, h->zu, d_pred, d_state, nullptr, nullptr, nullptr, 0, nullptr, cfz::DisturbArgs{0, nullptr, nullptr, nullptr}, 0,
-                     0.0, 0.0, 0.0, 0.0, d_carry, nullptr, nullptr, nullptr);
+  hipLaunchKernelGGL(loop_post, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, S, n_own, N, h->kargs, d_status, nullptr, h->zu, d_pred,
+                     d_state, nullptr, nullptr, nullptr, 0, nullptr, cfz::disturb_none(), 0, d_carry, nullptr, nullptr, nullptr);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1150,7 +1122,7 @@ void comm_free(cfz_handle *h) {
 }
 
 void problems_free(cfz_handle *h) {
-  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of); dev_free(h->lp.pb_dz);
+  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
   h->lp.pb_on = false; h->lp.pb_cap = 0;
 }
 
@@ -1158,16 +1130,18 @@ void problems_free(cfz_handle *h) {
 // persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
 void loop_release(cfz_handle *h) {
   record_free(h); exchange_free(h); disturb_free(h); comm_free(h); problems_free(h);
+  dev_free(h->lp.dz_zero);
   dev_free(h->lp.ref_table); dev_free(h->lp.table_of); dev_free(h->lp.pred); dev_free(h->lp.state); dev_free(h->lp.kidx); dev_free(h->lp.order);
   dev_free(h->lp.pred2); dev_free(h->lp.scratch); dev_free(h->lp.queue); dev_free(h->lp.ctrl); dev_free(h->lp.done); dev_free(h->lp.iter_sum);
   h->lp = cfz_handle::Loop();
 }
 
-// the setting in force as the kernels take it (sigma NULL: none)
-cfz::DisturbArgs disturb_args(const cfz_handle *h) {
-  if (!h->lp.dz_on) return {0, nullptr, nullptr, nullptr};
-  const double *f = static_cast<const double *>(h->lp.dz_buf);
-  return {h->lp.dz_seed, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
+// the disturbance in force as the kernels take it (sigma NULL: none).  zero_if_off: for a kernel compiled with kDist that stands in
+// for one without (the comm and the pool kernels): the all-zero block instead of none
+cfz::DisturbArgs disturb_args(const cfz_handle *h, bool zero_if_off = false) {
+  if (!h->lp.dz_on && !zero_if_off) return cfz::disturb_none();
+  const double *f = static_cast<const double *>(h->lp.dz_on ? h->lp.dz_buf : h->lp.dz_zero);
+  return {h->lp.dz_on ? h->lp.dz_seed : 0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
 }
 
 // the comm setting in force as the kernels take it (p_drop NULL: none)
@@ -1175,23 +1149,26 @@ cfz::CommArgs comm_args(const cfz_handle *h) {
   if (!h->lp.cm_on) return cfz::comm_none();
   const double *f = static_cast<const double *>(h->lp.cm_buf);
   const size_t S = (size_t)h->lp.S;
-  return {h->lp.cm_seed, f, reinterpret_cast<const uint32_t *>(f + 2 * S + cfz::kDisturbN), h->lp.cm_ring, h->lp.cm_max_age, h->lp.cm_compensate,
-          h->lp.cm_tau_on, S * (h->ks.n_nbr + 1) * 7 * h->ks.N};
+  return {h->lp.cm_seed, f, reinterpret_cast<const uint32_t *>(f + S), h->lp.cm_ring, h->lp.cm_max_age, h->lp.cm_compensate, h->lp.cm_tau_on,
+          S * (h->ks.n_nbr + 1) * 7 * h->ks.N};
 }
 
-// what the comm kernels take for dz: the disturbance in force, or the all-zero setting of cm_buf
-cfz::DisturbArgs comm_disturb_args(const cfz_handle *h) {
-  if (h->lp.dz_on) return disturb_args(h);
-  const double *f = static_cast<const double *>(h->lp.cm_buf) + h->lp.S;
-  return {0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
+// what opens the closed loop's entry points: a handle whose loop is set up, its device current and (drain) its stream idle
+int loop_ready(cfz_handle *h, bool drain = false) {
+  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  HIP_OK(hipSetDevice(h->device));
+  if (drain) HIP_OK(hipStreamSynchronize(h->stream));
+  return 0;
 }
 
-// what the pool kernels take for dz: the disturbance in force, the comm setting's zeros, or the pool's own
-cfz::DisturbArgs pool_disturb_args(const cfz_handle *h) {
-  if (h->lp.dz_on) return disturb_args(h);
-  if (h->lp.cm_on) return comm_disturb_args(h);
-  const double *f = static_cast<const double *>(h->lp.pb_dz);
-  return {0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
+// the device block of a setting, f | stream[S] (uint32; NULL: scenario s draws from stream s), allocated at its first upload
+int upload_setting(cfz_handle *h, void *&buf, const std::vector<double> &f, const uint32_t *stream) {
+  std::vector<uint32_t> id((size_t)h->lp.S);
+  for (size_t s = 0; s < id.size(); ++s) id[s] = stream ? stream[s] : (uint32_t)s;
+  if (!buf) HIP_OK(hipMalloc(&buf, f.size() * 8 + id.size() * 4));
+  HIP_OK(hipMemcpy(buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(static_cast<char *>(buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  return 0;
 }
 
 // the slot of message tau in the ring (comm on)
@@ -1221,17 +1198,15 @@ int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const 
   record_slice(h, rec, rec_si);
   const cfz::DisturbArgs dz = disturb_args(h);
   const cfz::CommArgs cm = comm_args(h);
-  const double *bd = h->ks.bounds;  // (the input box: a in [bd[8], bd[9]], w in [bd[10], bd[11]])
   const long nt = (long)n_inst * N;
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->lp.T, h->lp.ref_table,
                      h->lp.table_of, h->lp.kidx, h->lp.pred, h->lp.state, h->x0, h->ref, h->nbr, h->zu, r, xperm, xrank, dz, h->lp.steps_done, cm);
   HIP_OK(hipGetLastError());
   const bool pool = h->lp.pb_on;  // the scenario's own problem: solve_kernel_pool, and its input box in loop_post
   if (launch_solve(h, S * V, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, dispatch, 1, n_inst, pool)) return -1;
-  hipLaunchKernelGGL(loop_post, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->ks.dt, h->ks.wb, kPlantSubsteps,
-                     h->status, h->iters, h->zu, h->lp.pred, h->lp.state, h->lp.kidx, rec, rec_si, r, xperm, dz, h->lp.steps_done, bd[8], bd[9], bd[10],
-                     bd[11], nullptr, h->lp.cm_on ? comm_message(h, h->lp.steps_done) : nullptr, pool ? h->lp.pb_pool : nullptr,
-                     pool ? h->lp.pb_of : nullptr);
+  hipLaunchKernelGGL(loop_post, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->kargs, h->status, h->iters, h->zu,
+                     h->lp.pred, h->lp.state, h->lp.kidx, rec, rec_si, r, xperm, dz, h->lp.steps_done, nullptr,
+                     h->lp.cm_on ? comm_message(h, h->lp.steps_done) : nullptr, pool ? h->lp.pb_pool : nullptr, pool ? h->lp.pb_of : nullptr);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1294,6 +1269,8 @@ int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *table
   HIP_OK(hipMalloc(&h->lp.ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->lp.pred, B * 7 * N * 8));
   HIP_OK(hipMalloc(&h->lp.state, B * 5 * 8)); HIP_OK(hipMalloc(&h->lp.kidx, (size_t)S * 4));
   HIP_OK(hipMalloc(&h->lp.order, B * 4)); HIP_OK(hipMalloc(&h->lp.table_of, (size_t)S * 4));
+  const size_t nz = ((size_t)cfz::kDisturbN + S) * 8 + (size_t)S * 4;  // zero sigma[12] | zero level[S] | zero stream[S]
+  HIP_OK(hipMalloc(&h->lp.dz_zero, nz)); HIP_OK(hipMemset(h->lp.dz_zero, 0, nz));
   HIP_OK(hipMemset(h->wst, 0, (size_t)h->max_batch * h->wst_stride * 8));  // first iteration: cold multipliers
   HIP_OK(hipMemcpy(h->lp.ref_table, tables, (size_t)P * V * T * 7 * 8, hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(h->lp.table_of, tof.data(), (size_t)S * 4, hipMemcpyHostToDevice));
@@ -1316,10 +1293,8 @@ int cfz_loop_init(cfz_handle *h, int S, int T, const double *ref_table, const in
 }
 
 int cfz_loop_record(cfz_handle *h, int K) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h, true)) return -1;
   if (K < 0) return fail("K must not be negative");
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
   record_free(h);
   if (K == 0) return 0;
   const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
@@ -1330,9 +1305,8 @@ int cfz_loop_record(cfz_handle *h, int K) {
 }
 
 int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status, int32_t *iters) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h)) return -1;
   if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
-  HIP_OK(hipSetDevice(h->device));
   const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
   if (traj) HIP_OK(hipMemcpy(traj, h->lp.rec + (size_t)t0 * B * 7, (size_t)K * B * 7 * 8, hipMemcpyDeviceToHost));
   if (status || iters) {
@@ -1348,9 +1322,8 @@ int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status
 
 int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
                    int32_t *first_contact, int32_t *arrive) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h)) return -1;
   if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
-  HIP_OK(hipSetDevice(h->device));
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t B = (size_t)S * V;
   if (arena_reset(h->arena)) return -1;
@@ -1377,9 +1350,7 @@ int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const doub
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
+  if (loop_ready(h, true)) return -1;
   if (!order) { exchange_free(h); return 0; }
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   std::vector<int32_t> rank((size_t)S * V), list((size_t)V * S);
@@ -1405,9 +1376,7 @@ int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
 
 int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_meas[5], const double sigma_act[2],
                              const double sigma_proc[5], const double *level, const uint32_t *stream) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
+  if (loop_ready(h, true)) return -1;
   if (!sigma_meas && !sigma_act && !sigma_proc) { h->lp.dz_on = false; return 0; }  // off: the plain kernels
   const int S = h->lp.S;
   std::vector<double> f((size_t)cfz::kDisturbN + S, 0.0);
@@ -1419,20 +1388,15 @@ int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_me
     f[cfz::kDisturbN + s] = level ? level[s] : 1.0;
     if (!(f[cfz::kDisturbN + s] >= 0.0) || !std::isfinite(f[cfz::kDisturbN + s])) return fail("a level is negative or not finite");
   }
-  std::vector<uint32_t> id((size_t)S);
-  for (int s = 0; s < S; ++s) id[s] = stream ? stream[s] : (uint32_t)s;
-  if (!h->lp.dz_buf) HIP_OK(hipMalloc(&h->lp.dz_buf, f.size() * 8 + id.size() * 4));
-  HIP_OK(hipMemcpy(h->lp.dz_buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(static_cast<char *>(h->lp.dz_buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  if (upload_setting(h, h->lp.dz_buf, f, stream)) return -1;
   h->lp.dz_seed = seed; h->lp.dz_on = true;
   return 0;
 }
 
 int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h)) return -1;
   if (!h->lp.dz_on) return fail("no disturbance is set (cfz_loop_set_disturbance)");
   if (t0 < 0 || K < 1 || !d) return fail("t0 must not be negative, K must be positive and d not NULL");
-  HIP_OK(hipSetDevice(h->device));
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t n = (size_t)K * S * V * cfz::kDisturbN;
   if (n > ((size_t)1 << 31)) return fail("window too large");
@@ -1447,20 +1411,13 @@ int cfz_loop_disturbance(cfz_handle *h, int t0, int K, double *d) {
 }
 
 int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop, int max_age, int compensate, const uint32_t *stream) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
+  if (loop_ready(h, true)) return -1;
   if (!p_drop) { h->lp.cm_on = false; return 0; }  // off: the kernels without it
   if (max_age < 1 || max_age > CFZ_MAX_AGE) return fail("max_age outside 1..CFZ_MAX_AGE");
   if (compensate != 0 && compensate != 1) return fail("compensate must be 0 or 1");
   const int S = h->lp.S, V = h->ks.n_nbr + 1, N = h->ks.N;
   for (int s = 0; s < S; ++s)
     if (!(p_drop[s] >= 0.0 && p_drop[s] <= 1.0)) return fail("a p_drop is outside [0, 1] or not finite");
-  // p_drop[S] | zero sigma[12] | zero level[S] | stream[S]
-  std::vector<double> f(2 * (size_t)S + cfz::kDisturbN, 0.0);
-  std::copy(p_drop, p_drop + S, f.begin());
-  std::vector<uint32_t> id((size_t)S);
-  for (int s = 0; s < S; ++s) id[s] = stream ? stream[s] : (uint32_t)s;
   const size_t slot = (size_t)S * V * 7 * N;
   if (h->lp.cm_ring_slots != max_age + 2) {
     double *ring = nullptr;
@@ -1468,9 +1425,7 @@ int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop, int ma
     dev_free(h->lp.cm_ring);
     h->lp.cm_ring = ring; h->lp.cm_ring_slots = max_age + 2;
   }
-  if (!h->lp.cm_buf) HIP_OK(hipMalloc(&h->lp.cm_buf, f.size() * 8 + id.size() * 4));
-  HIP_OK(hipMemcpy(h->lp.cm_buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(static_cast<char *>(h->lp.cm_buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  if (upload_setting(h, h->lp.cm_buf, std::vector<double>(p_drop, p_drop + S), stream)) return -1;  // p_drop[S] | stream[S]
   h->lp.cm_seed = seed; h->lp.cm_max_age = max_age; h->lp.cm_compensate = compensate; h->lp.cm_on = true;
   // history restarts at the message standing in pred, that of the last iteration done
   h->lp.cm_tau_on = h->lp.steps_done - 1;
@@ -1506,10 +1461,8 @@ int cfz_problem_check(const cfz_spec *base, const cfz_options *base_opt, const c
 }
 
 int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz_options *opts, const int32_t *problem_of) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h, true)) return -1;
   if (P < 0) return fail("P must not be negative");
-  HIP_OK(hipSetDevice(h->device));
-  HIP_OK(hipStreamSynchronize(h->stream));
   if (P == 0 || !specs) { h->lp.pb_on = false; return 0; }  // off: the kernels without it
   if (!problem_of) return fail("null problem_of");
   const int S = h->lp.S;
@@ -1522,13 +1475,6 @@ int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz
     if (fill_kspec(pool[p].sp, &specs[p], o)) return -1;
     pool[p].sp.obs_tab = h->obs_tab;
     pool[p].dv = cfz::derive(pool[p].sp); pool[p].L = h->lay;
-  }
-  if (!h->lp.pb_dz) {  // kept only once it is all zero: a failure here leaves no buffer that a later call would take for one
-    const size_t nz = ((size_t)cfz::kDisturbN + S) * 8 + (size_t)S * 4;
-    void *z = nullptr;
-    HIP_OK(hipMalloc(&z, nz));
-    if (hipMemset(z, 0, nz) != hipSuccess) { dev_free(z); return fail("hipMemset of the pool's zero disturbance failed"); }
-    h->lp.pb_dz = z;
   }
   // the new setting is written into blocks of its own and swapped in once it is complete: a failure leaves the one in force as it was
   KArgs *d = nullptr;
@@ -1545,10 +1491,9 @@ int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz
 }
 
 int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h)) return -1;
   if (!h->lp.cm_on) return fail("no lossy exchange is set (cfz_loop_set_comm)");
   if (tau0 < 0 || K < 1 || !delivered) return fail("tau0 must not be negative, K must be positive and delivered not NULL");
-  HIP_OK(hipSetDevice(h->device));
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t n = (size_t)K * S * V * V;
   if (n > ((size_t)1 << 31)) return fail("window too large");
@@ -1563,9 +1508,7 @@ int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered) {
 }
 
 int cfz_loop_step(cfz_handle *h) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
-  if (record_room(h, 1)) return -1;
-  HIP_OK(hipSetDevice(h->device));
+  if (loop_ready(h) || record_room(h, 1)) return -1;
   const int V = h->ks.n_nbr + 1, S = h->lp.S, B = S * V;
   float total_ms = 0.f;
   if (h->lp.xperm) {
@@ -1598,18 +1541,20 @@ int cfz_loop_step(cfz_handle *h) {
 }
 
 int cfz_loop_run(cfz_handle *h, int K) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
+  if (loop_ready(h)) return -1;
   if (K < 1) return fail("K must be positive");
   if (record_room(h, K)) return -1;
-  HIP_OK(hipSetDevice(h->device));
   const int V = h->ks.n_nbr + 1, N = h->ks.N, S = h->lp.S, B = S * V;
   const size_t total = (size_t)B * K;
   if (total > (size_t)1 << 30) return fail("too many work items");
   int ncu = 0;
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
-  const bool seq = h->lp.xperm != nullptr, dist = h->lp.dz_on, comm = h->lp.cm_on, pool = h->lp.pb_on;
-  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kLoopKernel[pool][comm ? 2 : dist][seq], cfz::kNL, h->lds_bytes));
+  const bool seq = h->lp.xperm != nullptr, comm = h->lp.cm_on;
+  const int variant = loop_variant(seq, h->lp.dz_on, comm, h->lp.pb_on);
+  if (variant < 0) return fail("no persistent kernel for this setting");
+  const LoopVariant &var = kLoopVariants[variant];
+  HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, var.fn, cfz::kNL, h->lds_bytes));
   per_cu = std::min(per_cu, h->blocks_per_cu);  // the 2 KiB LDS granules (cfz_create): what the hardware really keeps resident
   if (per_cu < 1) return fail("loop kernel does not fit on a CU");
   // one workgroup per resident slot: more would only queue behind them (any workgroup can serve any item, so a surplus
@@ -1653,23 +1598,35 @@ int cfz_loop_run(cfz_handle *h, int K) {
   double *rec; int32_t *rec_si;
   record_slice(h, rec, rec_si);
   const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
-  const cfz::DisturbArgs dz = disturb_args(h);
-  // the ten kernels share their arguments up to the record; `tail` is the exchange order, the disturbance, the comm setting and the pool
-  auto launch = [&](auto kernel, auto... tail) {
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->lp.T, h->lp.ref_table, h->lp.table_of,
-                       h->lp.kidx, 0, h->lp.pred2, h->lp.state, h->lp.scratch, h->lp.queue, h->lp.ctrl, h->lp.done, h->status, h->iters, h->stats, h->lp.iter_sum,
-                       h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, tail...);
+  // The ten kernels share their arguments up to the record; what follows is the tail groups of the settings a kernel was compiled
+  // with, in this order.  One line per row of kLoopVariants, in its order; `launch` refuses a line that names another kernel than its row.
+  const auto xo = std::make_tuple((const int32_t *)h->lp.xperm, (const int32_t *)h->lp.xrank);
+  const auto dz = std::make_tuple(disturb_args(h, true), h->lp.steps_done);  // (dz, step0)
+  const auto cm = std::make_tuple(comm_args(h));
+  const auto pb = std::make_tuple((const KArgs *)h->lp.pb_pool, (const int32_t *)h->lp.pb_of, h->lp.dz_on ? 1 : 0);  // (pool, problem_of, clip)
+  auto launch = [&](auto kernel, const auto &...groups) {
+    if ((const void *)kernel != var.fn) return fail("cfz_loop_run: the launch chain and kLoopVariants name different kernels");
+    std::apply([&](auto... tail) {
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->lp.T, h->lp.ref_table, h->lp.table_of,
+                         h->lp.kidx, 0, h->lp.pred2, h->lp.state, h->lp.scratch, h->lp.queue, h->lp.ctrl, h->lp.done, h->status, h->iters, h->stats,
+                         h->lp.iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, tail...);
+    }, std::tuple_cat(groups...));
+    return 0;
   };
-  if (pool && comm && seq) launch(loop_kernel_seq_pool_comm, h->lp.xperm, h->lp.xrank, pool_disturb_args(h), h->lp.steps_done, comm_args(h), h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
-  else if (pool && comm) launch(loop_kernel_pool_comm, pool_disturb_args(h), h->lp.steps_done, comm_args(h), h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
-  else if (pool && seq) launch(loop_kernel_seq_pool, h->lp.xperm, h->lp.xrank, pool_disturb_args(h), h->lp.steps_done, h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
-  else if (pool) launch(loop_kernel_pool, pool_disturb_args(h), h->lp.steps_done, h->lp.pb_pool, h->lp.pb_of, h->lp.dz_on ? 1 : 0);
-  else if (comm && seq) launch(loop_kernel_seq_comm, h->lp.xperm, h->lp.xrank, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
-  else if (comm) launch(loop_kernel_comm, comm_disturb_args(h), h->lp.steps_done, comm_args(h));
-  else if (dist && seq) launch(loop_kernel_seq_dist, h->lp.xperm, h->lp.xrank, dz, h->lp.steps_done);
-  else if (dist) launch(loop_kernel_dist, dz, h->lp.steps_done);
-  else if (seq) launch(loop_kernel_seq, h->lp.xperm, h->lp.xrank);
-  else launch(loop_kernel);
+  int bad = 0;
+  switch (variant) {
+    case 0: bad = launch(loop_kernel); break;
+    case 1: bad = launch(loop_kernel_seq, xo); break;
+    case 2: bad = launch(loop_kernel_dist, dz); break;
+    case 3: bad = launch(loop_kernel_seq_dist, xo, dz); break;
+    case 4: bad = launch(loop_kernel_comm, dz, cm); break;
+    case 5: bad = launch(loop_kernel_seq_comm, xo, dz, cm); break;
+    case 6: bad = launch(loop_kernel_pool, dz, pb); break;
+    case 7: bad = launch(loop_kernel_seq_pool, xo, dz, pb); break;
+    case 8: bad = launch(loop_kernel_pool_comm, dz, cm, pb); break;
+    case 9: bad = launch(loop_kernel_seq_pool_comm, xo, dz, cm, pb); break;
+  }
+  if (bad) return -1;
   HIP_OK(hipGetLastError());
   if (h->lp.rec) h->lp.rec_used += K;
   h->lp.steps_done += K;
@@ -1725,8 +1682,7 @@ int cfz_loop_last_status_counts(const cfz_handle *h, long counts[6]) {
 }
 
 int cfz_loop_get(cfz_handle *h, double *state, double *pred, int32_t *status, int32_t *iters) {
-  if (!h || !h->lp.pred) return fail("cfz_loop_init has not been called");
-  HIP_OK(hipSetDevice(h->device));
+  if (loop_ready(h)) return -1;
   const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1), N = h->ks.N;
   if (state) HIP_OK(hipMemcpy(state, h->lp.state, B * 5 * 8, hipMemcpyDeviceToHost));
   if (pred) HIP_OK(hipMemcpy(pred, h->lp.pred, B * 7 * N * 8, hipMemcpyDeviceToHost));

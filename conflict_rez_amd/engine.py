@@ -236,6 +236,21 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _seed64(seed):
+    """The 64-bit key of a counter-based stream, as the C ABI takes it."""
+    return C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _stream_ids(stream, S):
+    """Per-scenario stream ids [S] as uint32 (None: the library's default, scenario s draws from stream s)."""
+    if stream is None:
+        return None
+    st = np.asarray(stream)
+    if st.dtype.kind not in "iu" or st.shape != (S,) or (st < 0).any() or (st > 0xFFFFFFFF).any():
+        raise ValueError(f"stream must hold {S} integers in [0, 2^32)")
+    return np.ascontiguousarray(st, dtype=np.uint32)
+
+
 def _f64(a, shape):
     a = np.ascontiguousarray(a, dtype=np.float64)
     if a.shape != tuple(shape):
@@ -479,6 +494,8 @@ class Engine:
         self.max_batch = int(max_batch)
         self.options = dict(options)  # (the base of the overrides of loop_set_problems)
         self._h = C.c_void_p()
+        self._S = self._V = 0  # scenarios and vehicles of the closed loop; 0 until loop_init (the library refuses loop calls before it)
+        self._rec_cap = self._rec_used = 0
         cs, co = spec.to_c(), default_options(**options)
         if self.lib.cfz_create(C.byref(cs), C.byref(co), int(device), self.max_batch, C.byref(self._h)) != 0:
             raise RuntimeError("cfz_create: " + self.lib.cfz_last_error().decode())
@@ -618,7 +635,7 @@ class Engine:
         (one order for every scenario) or [S, V] integers (one per scenario): the vehicles of a scenario solve one after another
         in that order, each against the predictions of those before it from the same iteration (not advanced) and the previous
         iteration's predictions of the others, advanced."""
-        if order is None or not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+        if order is None or not self._S:  # (before loop_init the library refuses the call)
             self._ck(self.lib.cfz_loop_set_order(self._h, None), "cfz_loop_set_order")
             return
         S, V = self._S, self._V
@@ -641,7 +658,7 @@ class Engine:
         delta) the solver is pinned to, act [2] of the applied input (a, w; clipped to the input box afterwards), proc [5] of the state
         after the plant; None: zeros, all three None: off (what `loop_init` restores).  level [S] scales the three groups per scenario
         (None: 1), stream [S] is each scenario's stream id (None: s): scenarios with equal ids draw the same noise."""
-        S = getattr(self, "_S", 0)
+        S = self._S
 
         def group(a, n, name):
             if a is None:
@@ -652,21 +669,16 @@ class Engine:
             return a
 
         meas, act, proc = group(meas, 5, "meas"), group(act, 2, "act"), group(proc, 5, "proc")
-        if not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+        if not S:  # (before loop_init the library refuses the call)
             level = stream = None
-        level = group(level, S, "level")
-        if stream is not None:
-            st = np.asarray(stream)
-            if st.dtype.kind not in "iu" or st.shape != (S,) or (st < 0).any() or (st > 0xFFFFFFFF).any():
-                raise ValueError(f"stream must hold {S} integers in [0, 2^32)")
-            stream = np.ascontiguousarray(st, dtype=np.uint32)
-        self._ck(self.lib.cfz_loop_set_disturbance(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(meas), _ptr(act), _ptr(proc),
-                                                   _ptr(level), _ptr(stream)), "cfz_loop_set_disturbance")
+        level, stream = group(level, S, "level"), _stream_ids(stream, S)
+        self._ck(self.lib.cfz_loop_set_disturbance(self._h, _seed64(seed), _ptr(meas), _ptr(act), _ptr(proc), _ptr(level), _ptr(stream)),
+                 "cfz_loop_set_disturbance")
 
     def loop_disturbance(self, t0=0, K=1):
         """`cfz_loop_disturbance`: d [K,S,V,12] that the loop adds at steps [t0, t0 + K) under the setting in force (0:5 measurement,
         5:7 input, 7:12 process); steps count from `loop_init`."""
-        S, V = getattr(self, "_S", 1), getattr(self, "_V", self.spec.n_nbr + 1)
+        S, V = self._S, self._V
         d = np.empty((max(int(K), 0), S, V, 12))
         self._ck(self.lib.cfz_loop_disturbance(self._h, int(t0), int(K), _ptr(d)), "cfz_loop_disturbance")
         return d
@@ -678,10 +690,10 @@ class Engine:
         message that arrived, at most max_age (1..6) iterations old, advanced by its age (compensate) or as if it were new (the
         reference's node).  stream [S] is each scenario's stream id (None: s).  Every call that switches it on restarts the message
         history at the current predictions."""
-        S = getattr(self, "_S", 0)
-        if p_drop is None or not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+        S = self._S
+        if p_drop is None or not S:  # (before loop_init the library refuses the call)
             p = None if p_drop is None else np.zeros(1)
-            self._ck(self.lib.cfz_loop_set_comm(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(p), 1, 0, None), "cfz_loop_set_comm")
+            self._ck(self.lib.cfz_loop_set_comm(self._h, _seed64(seed), _ptr(p), 1, 0, None), "cfz_loop_set_comm")
             return
         p = np.asarray(p_drop)
         if p.dtype.kind not in "fiu":
@@ -694,18 +706,13 @@ class Engine:
         for name, val in (("max_age", max_age), ("compensate", compensate)):
             if not isinstance(val, (bool, int, np.integer, np.bool_)):
                 raise ValueError(f"{name} must be an integer, got {type(val).__name__}")
-        if stream is not None:
-            st = np.asarray(stream)
-            if st.dtype.kind not in "iu" or st.shape != (S,) or (st < 0).any() or (st > 0xFFFFFFFF).any():
-                raise ValueError(f"stream must hold {S} integers in [0, 2^32)")
-            stream = np.ascontiguousarray(st, dtype=np.uint32)
-        self._ck(self.lib.cfz_loop_set_comm(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _ptr(p), int(max_age), int(compensate),
-                                            _ptr(stream)), "cfz_loop_set_comm")
+        stream = _stream_ids(stream, S)
+        self._ck(self.lib.cfz_loop_set_comm(self._h, _seed64(seed), _ptr(p), int(max_age), int(compensate), _ptr(stream)), "cfz_loop_set_comm")
 
     def loop_comm(self, tau0=0, K=1):
         """`cfz_loop_comm`: bool [K,S,V,V], the delivery bits of the messages of iterations [tau0, tau0 + K) under the setting in force;
         [k, s, v, u] is the message from vehicle u to vehicle v, the diagonal True; iterations count from `loop_init`."""
-        S, V = getattr(self, "_S", 1), getattr(self, "_V", self.spec.n_nbr + 1)
+        S, V = self._S, self._V
         b = np.empty((max(int(K), 0), S, V, V), np.int32)
         self._ck(self.lib.cfz_loop_comm(self._h, int(tau0), int(K), _ptr(b)), "cfz_loop_comm")
         return b.astype(bool)
@@ -721,7 +728,7 @@ class Engine:
         weights and options; geometry, time base and carry_duals must be the engine's (`problem_check`).  None: off again, what
         `loop_init` restores."""
         P, specs, opts = pack_problems(problems, self.options)
-        if P == 0 or not hasattr(self, "_S"):  # (before loop_init the library refuses the call)
+        if P == 0 or not self._S:  # (before loop_init the library refuses the call)
             self._ck(self.lib.cfz_loop_set_problems(self._h, P, specs, opts, None), "cfz_loop_set_problems")
             return
         po = np.asarray(problem_of)

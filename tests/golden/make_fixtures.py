@@ -9,6 +9,8 @@
                         (oracle/plan_nlp.py + oracle/ipm.py, exact Hessian), sampled every dt
   mpc_golden.npz        MPC-step instances (inputs) and their solutions by the full-KKT numpy
                         oracle (oracle/ipm.py on oracle/mpc_nlp.py)
+  comm_replay_lossy.npz (`--comm-replay` only) the host replay of the closed loop under a lossy exchange; see
+                        comm_replay_lossy below for what the committed file was recorded with
 """
 import json
 import os
@@ -194,7 +196,30 @@ def colloc_golden():
                         joint_meta=np.array([r2["status"], r2["iters"], r2["f"]]))
 
 
+def comm_replay_lossy():
+    """A regression pin of the host replay under loss (NOT an oracle): the runs of tests/test_comm_host.lossy_replay_runs -- 2 scenarios
+    x 4 steps, p_drop 0.5, max_age 2, Jacobi and sequential, compensate off and on, the last run under a disturbance -- with state,
+    prediction, status, iterations and the age of every neighbour read.  The committed file was recorded with the replay-with-history
+    that tests/comm_binding.py carried until that loop was folded into oracle/closed_loop.replay (`comm=`), to show that the one loop
+    reproduces the other bit for bit; this function records it again with the oracle's loop.  Ages (t, s, v, u, a): 33 of 96 reads
+    above age 0 under Jacobi, 39 of 96 under the sequential rule, the largest 2; all 32 solves of each run converge."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_comm_host as tch
+    from oracle.closed_loop import replay
+
+    g = np.load(os.path.join(HERE, "mpc_golden.npz"))
+    out = tch.lossy_replay_runs(MpcSpec(A_obs=g["A_obs"], b_obs=g["b_obs"], n_nbr=3), replay)
+    for name, *_ in tch.LOSSY_CASES:
+        ages, status = out[f"{name}_ages"], out[f"{name}_status"]
+        print(name, "reads above age 0:", int((ages[:, 4] > 0).sum()), "of", len(ages), "converged", int((status == 0).sum()), "of", status.size)
+        assert (ages[:, 4] > 0).any() and 2 * int((status == 0).sum()) >= status.size
+    np.savez_compressed(os.path.join(HERE, "comm_replay_lossy.npz"), **out)
+
+
 if __name__ == "__main__":
+    if "--comm-replay" in sys.argv:
+        comm_replay_lossy()
+        sys.exit(0)
     if "--mpc-only" in sys.argv:  # the MPC fixtures again on the committed table (after a change of the MPC algorithm)
         mpc_golden(np.load(os.path.join(HERE, "refs_4v.npz"))["table"])
         carry_golden()

@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import comm_binding as cb  # noqa: E402
 import disturbance_binding as db  # noqa: E402
+from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
+from oracle.closed_loop import replay  # noqa: E402
 
 SIG = db.SIGMA
 SEED = 2024  # the comm seed of every test; test_against_the_host_replay's conditions were checked with it on the host
@@ -30,49 +32,6 @@ def eng():
     e = engine.Engine(scenarios.parking_lot_spec(), max_batch=1024)
     yield e
     e.close()
-
-
-def _planned(eng, S, seed=2024):
-    from conflict_rez_amd import scenarios
-
-    table, _ = scenarios.load_reference_table(kind="planned")
-    k0, noise = scenarios.sample_scenarios(S, table, seed=seed, spec=eng.spec)
-    return table, k0, noise
-
-
-def _orders(S, V, seed):
-    rng = np.random.default_rng(seed)
-    o = np.stack([rng.permutation(V) for _ in range(S)]).astype(np.int32)
-    o[0], o[1] = np.arange(V), np.arange(V)[::-1]
-    return o
-
-
-def _run(eng, init, K, how, order=None, setup=None, record=True):
-    """One closed loop of K steps from `init` (the arguments of loop_init): how = "step", "run" or a tuple of run lengths; `setup` is
-    called with the engine after loop_init.  -> loop_get's dict with the record's arrays as rec_*."""
-    eng.loop_init(*init)
-    if order is not None:
-        eng.loop_set_order(order)
-    if setup is not None:
-        setup(eng)
-    if record:
-        eng.loop_record(K)
-    if how == "step":
-        for _ in range(K):
-            eng.loop_step()
-    else:
-        for k in ((K,) if how == "run" else how):
-            eng.loop_run(k)
-    out = eng.loop_get()
-    if record:
-        out.update({"rec_" + k: v for k, v in eng.loop_history().items()})
-    return out
-
-
-def _same(a, b, what, rows=None):
-    for k in a:
-        x = a[k] if rows is None else (a[k][:, rows] if k.startswith("rec_") else a[k][rows])
-        assert np.array_equal(x, b[k]), (what, k)
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
@@ -140,8 +99,8 @@ def test_everything_dropped(eng, ospec, exchange, A):
     table, k0, noise = _planned(eng, S, seed=3)
     order = _orders(S, V, 5) if exchange == "sequential" else None
     fixed = cb.Setting(A, True, -1, age=lambda t, s, v, u, earlier: min(A, cb.want(t, earlier) + 1))
-    ref = list(cb.replay(ospec, table, k0, noise, K, lambda t: fixed, dt=eng.spec.dt, wb=eng.spec.wb, order=order))
-    lossless = list(cb.replay(ospec, table, k0, noise, K, lambda t: None, dt=eng.spec.dt, wb=eng.spec.wb, order=order))
+    ref = list(replay(ospec, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, order=order, comm=lambda t: fixed))
+    lossless = list(replay(ospec, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, order=order))
     assert max(float(np.abs(a[0] - b[0]).max()) for a, b in zip(ref, lossless)) > 1e-4  # the ages matter to what is compared below
     # the same ages from the rule over the downloaded bits
     eng.loop_init(table, k0, noise)
@@ -213,7 +172,7 @@ def test_export(eng):
 @pytest.mark.parametrize("S,exchange,compensate", [(8, "jacobi", True), (4, "sequential", False)])
 def test_against_the_host_replay(eng, ospec, S, exchange, compensate):
     """(5) S scenarios of the planned table (sample_scenarios(S, table, seed=3, spec)), 10 steps at p_drop = 0.3, max_age = 3, comm seed
-    2024, against the host replay with message history (comm_binding.replay) over the bits downloaded by loop_comm: status and iterations
+    2024, against the host replay with message history (oracle/closed_loop.replay with comm_binding.Setting) over the bits downloaded by loop_comm: status and iterations
     equal solve for solve, states within 1e-6 (test_disturbance_gpu's tolerance against its replay).  Not vacuous: at least half of the
     replayed solves converge and at least one neighbour read has age >= 2 (with seed 2024 the replay alone gives 315 of 320 converged
     and 64 such reads under Jacobi, 152 of 160 and 31 under the sequential exchange)."""
@@ -233,8 +192,8 @@ def test_against_the_host_replay(eng, ospec, S, exchange, compensate):
         eng.loop_step()
         got.append(eng.loop_get())
     ages, n_conv, worst = [], 0, 0.0
-    for t, (state, _, status, iters) in enumerate(cb.replay(ospec, table, k0, noise, steps, lambda t: setting, dt=eng.spec.dt, wb=eng.spec.wb,
-                                                            order=order, ages=ages)):
+    for t, (state, _, status, iters) in enumerate(replay(ospec, table, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, order=order,
+                                                         comm=lambda t: setting, ages=ages)):
         assert np.array_equal(got[t]["status"], status) and np.array_equal(got[t]["iters"], iters), t
         worst = max(worst, float(np.abs(got[t]["state"] - state).max()))
         n_conv += int((status == 0).sum())
@@ -264,7 +223,7 @@ def test_setting_at_a_step_boundary(eng, ospec):
     ages = []
     comm = lambda t: None if t < cuts[0] else (first if t < cuts[1] else second)
     worst = 0.0
-    for t, (state, _, status, iters) in enumerate(cb.replay(ospec, table, k0, noise, K, comm, dt=eng.spec.dt, wb=eng.spec.wb, ages=ages)):
+    for t, (state, _, status, iters) in enumerate(replay(ospec, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, comm=comm, ages=ages)):
         assert np.array_equal(h["status"][t], status) and np.array_equal(h["iters"][t], iters), t
         worst = max(worst, float(np.abs(h["traj"][t][..., :5] - state).max()))
     by_t = {t: max(a for tt, *_, a in ages if tt == t) for t in range(cuts[0], K)}

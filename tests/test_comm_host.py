@@ -1,6 +1,6 @@
 """The lossy prediction exchange of the closed loop (conflict_rez_amd/csrc/cfz_comm.inl) on the host: the CPU build of the kernel source
 (tests/emu/cfz_comm_emu.cpp) against the numpy statement of the delivery bits and the plain-Python age rule of tests/comm_binding.py,
-and that file's host replay against oracle/closed_loop.replay where nothing is lost."""
+and oracle/closed_loop.replay under that file's settings: against itself where nothing is lost, against a recorded run where much is."""
 import os
 import sys
 
@@ -111,8 +111,8 @@ def test_row_and_slot():
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
 def test_replay_without_loss_is_the_oracle_replay(ospec, exchange):
-    """1 scenario x 3 steps: the replay with history under p = 0 (every bit set) and with no setting equals oracle/closed_loop.replay:
-    state, prediction, status and iterations, exactly."""
+    """1 scenario x 3 steps: oracle/closed_loop.replay with history under p = 0 (every bit set) and under a `comm` that never gives a
+    setting equals the replay with comm=None: state, prediction, status and iterations, exactly."""
     from conflict_rez_amd import scenarios
     from oracle.closed_loop import replay
 
@@ -125,9 +125,54 @@ def test_replay_without_loss_is_the_oracle_replay(ospec, exchange):
     every = cb.Setting(3, True, -1, bits=np.ones((steps, 1, V, V), bool))
     for comm in (lambda t: None, lambda t: every):
         ages = []
-        got = list(cb.replay(ospec, table, k0, noise, steps, comm, dt=spec.dt, wb=spec.wb, order=order, ages=ages))
+        got = list(replay(ospec, table, k0, noise, steps, dt=spec.dt, wb=spec.wb, order=order, comm=comm, ages=ages))
         for t in range(steps):
             for a, b in zip(ref[t], got[t]):
                 assert np.array_equal(a, b), (exchange, t)
         assert all(a == 0 for *_, a in ages)
     assert sum(int((r[2] == 0).sum()) for r in ref) >= steps * V // 2
+
+
+# ---- the recorded lossy replay (tests/golden/comm_replay_lossy.npz; tests/golden/make_fixtures.py: comm_replay_lossy) ------------------
+LOSSY_CASES = (("jacobi", False, False), ("jacobi_comp", False, True), ("sequential", True, False), ("sequential_comp_d", True, True))
+
+
+def lossy_replay_runs(ospec, replay):
+    """The fixture's runs through `replay` (oracle.closed_loop.replay's signature): 2 scenarios x 4 steps at p_drop 0.5, max_age 2, both
+    exchange rules x both `compensate` values, the last one under a disturbance d.  {name_key: array}, the ages as rows (t, s, v, u, a)."""
+    from conflict_rez_amd import scenarios
+
+    spec = scenarios.parking_lot_spec()
+    table, _ = scenarios.load_reference_table(kind="planned")
+    S, steps, V = 2, 4, table.shape[0]
+    k0, noise = scenarios.sample_scenarios(S, table, seed=3, spec=spec)
+    bits = cb.delivered(2024, np.full(S, 0.5), np.array([7, 2 ** 32 - 1], np.uint32), V, 0, steps)
+    box = np.asarray(spec.bounds, float).reshape(6, 2)[4:6]
+    sigma = np.array([0.02, 0.02, 0.005, 0.02, 0.002, 0.3, 0.1, 0.01, 0.01, 0.002, 0.01, 0.001])
+    out = {"k0": np.asarray(k0), "noise": np.asarray(noise)}
+    for name, sequential, compensate in LOSSY_CASES:
+        setting = cb.Setting(2, compensate, -1, bits=bits)
+        order = np.array([[2, 0, 3, 1], [1, 3, 0, 2]]) if sequential else None
+        d = np.random.default_rng(9).normal(0.0, 1.0, (steps, S, V, 12)) * sigma if name.endswith("_d") else None
+        ages = []
+        run = list(replay(ospec, table, k0, noise, steps, dt=spec.dt, wb=spec.wb, order=order, d=d, box=box, comm=lambda t: setting, ages=ages))
+        for i, key in enumerate(("state", "pred", "status", "iters")):
+            out[f"{name}_{key}"] = np.stack([r[i] for r in run])
+        out[f"{name}_ages"] = np.array(ages, np.int64)
+    return out
+
+
+def test_lossy_replay_reproduces_the_recorded_one(ospec):
+    """oracle/closed_loop.replay under loss against the run recorded with the replay-with-history this module's binding used to carry
+    (before the two host loops became one): state, prediction, status, iterations and every age read, bit for bit.  The record is
+    worth comparing with: some message is read at an age above 0 and at least half of the solves converge."""
+    from oracle.closed_loop import replay
+
+    want = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "comm_replay_lossy.npz"))
+    got = lossy_replay_runs(ospec, replay)
+    assert sorted(got) == sorted(want.files)
+    for key in want.files:
+        assert got[key].dtype == want[key].dtype and np.array_equal(got[key], want[key]), key
+    for name, *_ in LOSSY_CASES:
+        assert (want[f"{name}_ages"][:, 4] > 0).any(), name
+        assert 2 * int((want[f"{name}_status"] == 0).sum()) >= want[f"{name}_status"].size, name

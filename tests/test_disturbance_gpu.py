@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import disturbance_binding as db  # noqa: E402
+from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
 
 SIG = db.SIGMA
 SEED = 2024
@@ -29,49 +30,6 @@ def eng():
     e = engine.Engine(scenarios.parking_lot_spec(), max_batch=1024)
     yield e
     e.close()
-
-
-def _planned(eng, S, seed=2024):
-    from conflict_rez_amd import scenarios
-
-    table, _ = scenarios.load_reference_table(kind="planned")
-    k0, noise = scenarios.sample_scenarios(S, table, seed=seed, spec=eng.spec)
-    return table, k0, noise
-
-
-def _orders(S, V, seed):
-    rng = np.random.default_rng(seed)
-    o = np.stack([rng.permutation(V) for _ in range(S)]).astype(np.int32)
-    o[0], o[1] = np.arange(V), np.arange(V)[::-1]
-    return o
-
-
-def _run(eng, init, K, how, order=None, disturb=None, record=True):
-    """One closed loop of K steps from `init` (the arguments of loop_init): how = "step", "run" or a tuple of run lengths; `disturb`
-    is called with the engine after loop_init.  -> loop_get's dict with the record's arrays as rec_*."""
-    eng.loop_init(*init[0], **init[1])
-    if order is not None:
-        eng.loop_set_order(order)
-    if disturb is not None:
-        disturb(eng)
-    if record:
-        eng.loop_record(K)
-    if how == "step":
-        for _ in range(K):
-            eng.loop_step()
-    else:
-        for k in ((K,) if how == "run" else how):
-            eng.loop_run(k)
-    out = eng.loop_get()
-    if record:
-        out.update({"rec_" + k: v for k, v in eng.loop_history().items()})
-    return out
-
-
-def _same(a, b, what, rows=None):
-    for k in a:
-        x = a[k] if rows is None else (a[k][:, rows] if k.startswith("rec_") else a[k][rows])
-        assert np.array_equal(x, b[k]), (what, k)
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])

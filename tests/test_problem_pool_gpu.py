@@ -25,6 +25,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import disturbance_binding as db  # noqa: E402
 import problem_pool_binding as pb  # noqa: E402
+from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
 
 SIG = db.SIGMA
 SEED = 2024
@@ -59,50 +60,8 @@ def plain_engines(eng, probs):
         e.close()
 
 
-def _planned(eng, S, seed=2024):
-    from conflict_rez_amd import scenarios
-
-    table, _ = scenarios.load_reference_table(kind="planned")
-    k0, noise = scenarios.sample_scenarios(S, table, seed=seed, spec=eng.spec)
-    return table, k0, noise
-
-
-def _orders(S, V, seed):
-    rng = np.random.default_rng(seed)
-    o = np.stack([rng.permutation(V) for _ in range(S)]).astype(np.int32)
-    o[0], o[1] = np.arange(V), np.arange(V)[::-1]
-    return o
-
-
-def _run(e, init, K, how, order=None, setup=None, between=None):
-    """One closed loop of K steps from `init` = (table, k0, noise): how = "step", "run" or a tuple of run lengths; `setup` is called with
-    the engine after loop_init, `between` (how a tuple) between the launches.  -> loop_get's dict with the record's arrays as rec_*."""
-    e.loop_init(*init)
-    if order is not None:
-        e.loop_set_order(order)
-    if setup is not None:
-        setup(e)
-    e.loop_record(K)
-    if how == "step":
-        for _ in range(K):
-            e.loop_step()
-    else:
-        for i, k in enumerate((K,) if how == "run" else how):
-            if i and between is not None:
-                between(e)
-            e.loop_run(k)
-    out = e.loop_get()
-    out.update({"rec_" + k: v for k, v in e.loop_history().items()})
-    return out
-
-
 def _rows(a, rows):
     return {k: (v[:, rows] if k.startswith("rec_") else v[rows]) for k, v in a.items()}
-
-
-def _same(a, b, what):
-    for k in a:
-        assert np.array_equal(a[k], b[k]), (what, k)
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])

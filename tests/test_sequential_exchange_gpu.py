@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import audit_binding as ab  # noqa: E402
+from loop_cases import orders as _orders  # noqa: E402
 
 HYST = 1e-3  # the working set's hysteresis: a row enters it within 1 mm of its bound
 
@@ -27,14 +28,6 @@ def _bench_workload(S):
     table, _ = scenarios.load_reference_table(kind="planned")
     k0, noise = scenarios.sample_scenarios(1024, table, seed=2024, spec=spec)
     return spec, table, k0[:S], noise[:S]
-
-
-def _orders(S, V, seed):
-    """Seeded per-scenario orders; scenario 0 the identity, scenario 1 the reversed order."""
-    rng = np.random.default_rng(seed)
-    o = np.stack([rng.permutation(V) for _ in range(S)]).astype(np.int32)
-    o[0], o[1] = np.arange(V), np.arange(V)[::-1]
-    return o
 
 
 def _violations(spec, pred, status, order, thr):

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Two builds of the library on the same seeded MPC batch: are the results equal bit for bit?  Cold solves; a Jacobi persistent run of 6
 steps; 3 `loop_step`s, Jacobi and under seeded orders; a sequential persistent run of 4; a disturbed persistent run of 4 (the sigmas of
-tests/disturbance_binding.SIGMA).  Every loop is compared at its end point and over its record.
+tests/disturbance_binding.SIGMA); a lossy exchange (p_drop 0.3), Jacobi and sequential, run of 4; the pool of the four problems of
+tests/problem_pool_binding.py under noise, run of 4 and stepped 3 times; and runs of 4 through the remaining persistent kernels
+(sequential + noise, sequential + pool, pool + loss, sequential + pool + loss), so that all ten and both stepwise solve kernels are
+compared.  Every loop is compared at its end point and over its record; the exit status is 1 when anything differs.
 usage: python tools/gpu_lib_compare.py <libA.so> <libB.so> [scenarios]     (each library runs in a process of its own)"""
 import os, subprocess, sys, tempfile
 import numpy as np
@@ -11,6 +14,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from conflict_rez_amd import engine, scenarios
     from disturbance_binding import SIGMA
+    from problem_pool_binding import problems
     lib, S, out = sys.argv[2], int(sys.argv[3]), sys.argv[4]
     engine._lib = engine.load_library(lib)
     spec = scenarios.parking_lot_spec()
@@ -39,6 +43,28 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     loop("seq", lambda: e.loop_set_order(order), lambda: e.loop_run(4))
     loop("seqstep", lambda: e.loop_set_order(order), three_steps)
     loop("dist", lambda: e.loop_set_disturbance(2024, **SIGMA), lambda: e.loop_run(4))
+    probs, pof = problems(spec), np.arange(S) % 4
+
+    def setting(seq=False, noise=False, comm=False, pool=False):
+        def setup():
+            if seq:
+                e.loop_set_order(order)
+            if noise:
+                e.loop_set_disturbance(2024, **SIGMA)
+            if comm:
+                e.loop_set_comm(2024, 0.3, max_age=3)
+            if pool:
+                e.loop_set_problems(probs, pof)
+        return setup
+
+    loop("comm", setting(comm=True), lambda: e.loop_run(4))
+    loop("seqcomm", setting(seq=True, comm=True), lambda: e.loop_run(4))
+    loop("pool", setting(noise=True, pool=True), lambda: e.loop_run(4))
+    loop("poolstep", setting(noise=True, pool=True), three_steps)
+    loop("seqdist", setting(seq=True, noise=True), lambda: e.loop_run(4))
+    loop("seqpool", setting(seq=True, pool=True), lambda: e.loop_run(4))
+    loop("poolcomm", setting(comm=True, pool=True), lambda: e.loop_run(4))
+    loop("seqpoolcomm", setting(seq=True, comm=True, pool=True), lambda: e.loop_run(4))
     np.savez(out, **res)
     sys.exit(0)
 S = int(sys.argv[3]) if len(sys.argv) > 3 else 256
@@ -49,10 +75,18 @@ with tempfile.TemporaryDirectory() as d:
         subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", os.path.abspath(lib), str(S), out])
         res.append(dict(np.load(out)))
 a, b = res
+differ = 0
 print(f"{4 * S} cold solves: iterations {int(a['iters'].sum())} / {int(b['iters'].sum())}, kernel {float(a['ms']):.2f} / {float(b['ms']):.2f} ms")
 for k in a:
     if k == "ms" or k.endswith("_its"):
         continue
     same = np.array_equal(a[k], b[k])
+    differ += not same
     print(f"  {k}: {'equal bit for bit' if same else 'DIFFERENT: %d entries, max %.3e' % (int((a[k] != b[k]).sum()), float(np.abs(a[k].astype(float) - b[k].astype(float)).max()))}")
+for k in a:
+    if k.endswith("_its"):
+        print(f"{k[:-4]}: IPM iterations {int(a[k])} / {int(b[k])}")
+        differ += int(a[k]) != int(b[k])
 print("closed loop iterations", int(a["loop_its"]), int(b["loop_its"]))
+print("ALL EQUAL" if not differ else f"{differ} DIFFERENCES")
+sys.exit(1 if differ else 0)
