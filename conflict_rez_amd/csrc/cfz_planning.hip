@@ -10,7 +10,6 @@
 
 #include <algorithm>
 #include <type_traits>
-#include <cstdio>
 #include <cstdlib>
 #include <cmath>
 #include <string>
@@ -75,6 +74,75 @@ cfz_plan_ws *default_ws(int device) {
   if ((int)cache.size() <= device) cache.resize(device + 1, nullptr);
   if (!cache[device] && cfz_plan_ws_create(device, &cache[device]) != 0) return nullptr;
   return cache[device];
+}
+
+// ---- the host-side rules of the planning entry points, each stated once ----
+// The LDS a workgroup may own.  gfx950: the whole LDS of its CU (160 KB); some runtimes report the smaller legacy figure per block.
+int lds_per_workgroup(int device, int *bytes) {
+  int per_cu = 0;
+  HIP_OK(hipDeviceGetAttribute(bytes, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+  if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device) == hipSuccess) *bytes = std::max(*bytes, per_cu);
+  return 0;
+}
+
+// The interior-point constants the state_ws and the collocation specs share.  reg_dual, the stall exit and everything the option
+// structs carry stay with the callers.
+template <class Spec>
+void set_ip_constants(Spec &p) {
+  p.max_backtrack = 25; p.filter_cap = 16; p.dual_inf_tol = 1.0; p.compl_inf_tol = 1e-4;
+  p.kappa_eps = 10.0; p.kappa_mu = 0.2; p.theta_mu = 1.5; p.tau_min = 0.99; p.bound_push = 1e-2; p.bound_frac = 1e-2; p.s_max = 100.0;
+  p.kappa_sigma = 1e10; p.eta_phi = 1e-8; p.gamma_theta = 1e-5; p.gamma_phi = 1e-8; p.delta_sw = 1.0; p.s_theta = 1.1; p.s_phi = 2.3;
+  p.reg_primal = 1e-8;
+}
+
+typedef std::vector<std::pair<int, int>> PairList;
+
+// The pair rule: a separation row joins vehicles 0 <= a < b < V.
+bool pair_ok(int a, int b, int V) { return 0 <= a && a < b && b < V; }
+
+// The pair list of a joint plan of V vehicles: the n_pairs given, or every pair when pairs is NULL (multi_vehicle_planner.py:56-58).
+int parse_pairs(int V, int n_pairs, const int32_t *pairs, PairList &pr) {
+  if (pairs && V < 2) return fail("vehicle pairs need at least two vehicles");
+  if (pairs) for (int e = 0; e < n_pairs; ++e) {
+    if (!pair_ok(pairs[2 * e], pairs[2 * e + 1], V)) return fail("bad vehicle pair");
+    pr.push_back({pairs[2 * e], pairs[2 * e + 1]});
+  }
+  else for (int a = 0; a < V; ++a) for (int b = a + 1; b < V; ++b) pr.push_back({a, b});
+  return 0;
+}
+
+// The shape of a collocation problem: vehicles, intervals per vehicle, obstacles, pairs.  has_final(a): whether vehicle a ends on a given
+// heading -- the solve paths ask the heading itself, the info path its argument.  Refuses what its array writes cannot hold.
+template <class HasFinal>
+int fill_shape(cfzc::CSpec &p, int V, const int32_t *n_sets, HasFinal has_final, int N_per_set, int n_obs, const PairList &pr) {
+  if (V < 1 || V > cfzc::kMaxVeh || (int)pr.size() > cfzc::kMaxPairs) return fail("problem size outside compiled limits");
+  p.V = V; p.Nps = N_per_set; p.n_obs = n_obs; p.n_pairs = (int)pr.size();
+  for (int a = 0; a < V; ++a) {
+    if (n_sets[a] < 2) return fail("a plan needs at least two strategy steps");
+    p.n_chk[a] = n_sets[a] - 1; p.N[a] = N_per_set * p.n_chk[a]; p.has_final[a] = has_final(a);
+  }
+  for (int e = 0; e < p.n_pairs; ++e) {
+    if (!pair_ok(pr[e].first, pr[e].second, V)) return fail("bad vehicle pair");
+    p.pair_a[e] = pr[e].first; p.pair_b[e] = pr[e].second;
+  }
+  return 0;
+}
+
+// Which elimination a plan of this shape goes through: bit 2 of CSpec::no_prox, the structured one (cfz_struct.inl, cfz_jstruct.inl),
+// unless the pivots are wanted one at a time or a vehicle has more than 255 intervals (its interval count is packed into eight bits).
+// Decided on the host, where the slab is sized and the roofline is priced, not discovered on the device.
+int structured_bit(int structured, int one_pivot, const cfzc::CSpec &shape) {
+  if (!structured || one_pivot) return 0;
+  for (int a = 0; a < shape.V; ++a) if (shape.N[a] > 255) return 0;
+  return 4;
+}
+
+// half-bandwidth of a problem's ordering (51 for one vehicle); < 0: refused
+int half_bandwidth_of(const cfzc::CSpec &p) {
+  const cfzc::CDims d = cfzc::cdims(p);
+  std::vector<int> pos((size_t)d.n + d.m);
+  if (cfzc::build_order(p, pos.data(), pos.data() + d.n) != d.nk) return fail("internal: ordering does not cover the band system");
+  return cfzc::half_bandwidth(p, pos.data(), pos.data() + d.n);
 }
 }  // namespace
 
@@ -169,7 +237,8 @@ int cfz_state_ws_w(cfz_plan_ws *w, int B, const cfz_plan_options *po, const int3
   if (arena_reset(w->arena)) return -1;
   hipStream_t st = w->stream;
   std::vector<cfzp::PSpec> specs(B);
-  std::vector<long long> toff(B), xoff(B), soff(B);
+  std::vector<long long> off((size_t)3 * B);  // per plan: where its tube, its unknowns and its workspace begin
+  long long *toff = off.data(), *xoff = toff + B, *soff = xoff + B;
   long long nt = 0, nx = 0, ns = 0, npts = 0;
   for (int b = 0; b < B; ++b) {
     if (n_sets[b] < 2 || po->N < 1) return fail("a plan needs at least two strategy steps");
@@ -179,14 +248,13 @@ int cfz_state_ws_w(cfz_plan_ws *w, int B, const cfz_plan_options *po, const int3
     p.N = po->N; p.n_chk = n_sets[b] - 1; p.T = po->N * p.n_chk;
     p.has_final = final_heading && final_heading[b] == final_heading[b]; p.final_heading = p.has_final ? final_heading[b] : 0.0;
     p.bounded_input = po->bounded_input;
-    p.max_iter = po->max_iter; p.max_backtrack = 25; p.filter_cap = 16; p.stall_iters = po->stall_iters;
+    set_ip_constants(p);
+    p.max_iter = po->max_iter; p.stall_iters = po->stall_iters;
     p.dt = po->dt; p.wb = po->wb; p.shrink = po->shrink_tube;
     for (int i = 0; i < 3; ++i) p.init_pose[i] = init_pose[b * 3 + i];
     memcpy(p.bounds, po->bounds, sizeof p.bounds);
-    p.tol = po->tol; p.constr_viol_tol = po->constr_viol_tol; p.dual_inf_tol = 1.0; p.compl_inf_tol = 1e-4; p.mu_init = po->mu_init;
-    p.kappa_eps = 10.0; p.kappa_mu = 0.2; p.theta_mu = 1.5; p.tau_min = 0.99; p.bound_push = 1e-2; p.bound_frac = 1e-2; p.s_max = 100.0;
-    p.kappa_sigma = 1e10; p.eta_phi = 1e-8; p.gamma_theta = 1e-5; p.gamma_phi = 1e-8; p.delta_sw = 1.0; p.s_theta = 1.1; p.s_phi = 2.3;
-    p.reg_primal = 1e-8; p.reg_dual = 1e-9; p.curv_kappa = po->curv_kappa; p.stall_kappa = 0.9;
+    p.tol = po->tol; p.constr_viol_tol = po->constr_viol_tol; p.mu_init = po->mu_init;
+    p.reg_dual = 1e-9; p.curv_kappa = po->curv_kappa; p.stall_kappa = 0.9;
     toff[b] = nt; xoff[b] = nx; soff[b] = ns;
     nt += (long long)p.n_chk * 24; nx += cfzp::dims(p).n; ns += (long long)cfzp::work_doubles(p); npts += p.T + 1;
   }
@@ -229,9 +297,7 @@ int cfz_state_ws_w(cfz_plan_ws *w, int B, const cfz_plan_options *po, const int3
   HIP_OK(hipMemcpyAsync(dspec, specs.data(), sizeof(cfzp::PSpec) * B, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(dtube, tube, (size_t)nt * 8, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(dX, X.data(), (size_t)nx * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(doff, toff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(doff + B, xoff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(doff + 2 * B, soff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(doff, off.data(), (size_t)B * 3 * 8, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(dslab, 0, (size_t)ns * 8, st));
   // cfz_plan_options.kernel: WIDE = the sweep's per-stage data in LDS (one plan per CU at a time, 15 % faster per plan), NARROW = in the
   // workspace (several plans share a CU: 1024 plans take 0.13 s instead of 0.20 s); by default LDS while the batch fits the CUs in one
@@ -241,11 +307,7 @@ int cfz_state_ws_w(cfz_plan_ws *w, int B, const cfz_plan_options *po, const int3
   const size_t lds_bytes = (size_t)(cfzp::kSt + cfzp::kFb) * (Tmax + 1) * sizeof(double);
   hipFuncAttributes fa;
   HIP_OK(hipFuncGetAttributes(&fa, (const void *)state_ws_kernel<true>));
-  HIP_OK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, w->device));
-  {  // gfx950: a workgroup may own the whole LDS of its CU; some runtimes report the smaller legacy figure per block (as in colloc_run)
-    int per_cu = 0;
-    if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, w->device) == hipSuccess) lds_max = std::max(lds_max, per_cu);
-  }
+  if (lds_per_workgroup(w->device, &lds_max)) return -1;
   HIP_OK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, w->device));
   const bool want_lds = po->kernel == CFZ_KERNEL_WIDE || (po->kernel == CFZ_KERNEL_AUTO && B <= cus);
   const bool fast = want_lds && lds_bytes + fa.sharedSizeBytes <= (size_t)lds_max &&
@@ -303,7 +365,7 @@ static void radau5_tables(double A[6][6], double B[6]) {
 // B collocation problems in one launch; problem b plans nveh[b] vehicles with one shared dt (1: the single-vehicle plan).
 // Vehicles are numbered through all problems: n_sets, init_pose, final_heading, tube, guess and traj are per vehicle,
 // dt0, dt, status, iters, cost per problem; pairs[b]: vehicle pairs (local indices) with a separation row, per problem.
-static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vector<std::vector<std::pair<int, int>>> &pairs, const cfz_spec *spec,
+static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vector<PairList> &pairs, const cfz_spec *spec,
                       const cfz_colloc_options *co, const int32_t *n_sets, const double *init_pose, const double *final_heading,
                       const double *tube, const double *guess, const double *dt0, double *traj, double *dt, int32_t *status,
                       int32_t *iters, double *cost) {
@@ -311,6 +373,7 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
   if (spec->n_obs < 0 || spec->n_obs > cfzc::kMaxObs || co->N_per_set < 1) return fail("problem size outside compiled limits");
   if (co->kernel != CFZ_KERNEL_AUTO) return fail("cfz_colloc_options.kernel: retired with the one-wavefront collocation kernel (round 4); leave it 0");
   if (co->structured != 0 && co->structured != 1) return fail("cfz_colloc_options.structured must be 0 (band) or 1 (cfz_jstruct.inl); 2, round 4's scheme, was removed in round 6");
+  const bool profile = std::getenv("CFZ_COLLOC_PROFILE") != nullptr;  // per-phase clocks of every plan on stderr
   HIP_OK(hipSetDevice(w->device));
   if (arena_reset(w->arena)) return -1;
   hipStream_t st = w->stream;
@@ -322,64 +385,50 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
     for (int i = 0; i < 4; ++i) { o[2 * i] = spec->A_obs[j][i][0]; o[2 * i + 1] = spec->A_obs[j][i][1]; o[8 + i] = spec->b_obs[j][i];
                                   o[12 + 2 * i] = V[i][0]; o[13 + 2 * i] = V[i][1]; }
   }
-  int nv_total = 0;
+  std::vector<cfzc::CSpec> specs(B);
   long long nt = 0;
-  for (int b = 0; b < B; ++b) {
-    if (nveh[b] < 1 || nveh[b] > cfzc::kMaxVeh || (int)pairs[b].size() > cfzc::kMaxPairs) return fail("problem size outside compiled limits");
-    for (int a = 0; a < nveh[b]; ++a) { if (n_sets[nv_total + a] < 2) return fail("a plan needs at least two strategy steps"); nt += (long long)(n_sets[nv_total + a] - 1) * 24; }
-    nv_total += nveh[b];
+  for (int b = 0, v0 = 0; b < B; v0 += nveh[b++]) {  // every problem's shape first: it sizes the tube
+    cfzc::CSpec &p = specs[b];
+    memset(&p, 0, sizeof p);
+    if (fill_shape(p, nveh[b], n_sets + v0, [&](int a) { return final_heading && final_heading[v0 + a] == final_heading[v0 + a]; },
+                   co->N_per_set, spec->n_obs, pairs[b])) return -1;
+    for (int a = 0; a < p.V; ++a) nt += (long long)p.n_chk[a] * 24;
   }
   double *dtab = nullptr, *dtube = nullptr;
   ARENA_ALLOC(w->arena, dtab, tab.size() * 8); ARENA_ALLOC(w->arena, dtube, (size_t)nt * 8);
   HIP_OK(hipMemcpyAsync(dtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(dtube, tube, (size_t)nt * 8, hipMemcpyHostToDevice, st));
-  std::vector<cfzc::CSpec> specs(B);
-  std::vector<long long> xoff(B), soff(B);
+  std::vector<long long> off((size_t)2 * B);  // per problem: where its unknowns and its workspace begin
+  long long *xoff = off.data(), *soff = xoff + B;
   std::vector<int32_t> kbs(B);
   long long nx = 0, ns = 0, to = 0;
   int v0 = 0;
   for (int b = 0; b < B; ++b) {
     cfzc::CSpec &p = specs[b];
-    memset(&p, 0, sizeof p);
-    p.V = nveh[b]; p.Nps = co->N_per_set; p.n_obs = spec->n_obs; p.n_pairs = (int)pairs[b].size();
     long long npts = 0;
     for (int a = 0; a < p.V; ++a) {
       const int v = v0 + a;
-      p.n_chk[a] = n_sets[v] - 1; p.N[a] = p.Nps * p.n_chk[a];
-      p.has_final[a] = final_heading && final_heading[v] == final_heading[v]; p.final_heading[a] = p.has_final[a] ? final_heading[v] : 0.0;
+      p.final_heading[a] = p.has_final[a] ? final_heading[v] : 0.0;
       for (int i = 0; i < 3; ++i) p.init_pose[a][i] = init_pose[v * 3 + i];
       p.tube[a] = dtube + to; to += (long long)p.n_chk[a] * 24;
       npts += (long long)p.N[a] * cfzc::kPts;
     }
-    for (int e = 0; e < p.n_pairs; ++e) {
-      p.pair_a[e] = pairs[b][e].first; p.pair_b[e] = pairs[b][e].second;
-      if (p.pair_a[e] < 0 || p.pair_b[e] >= p.V || p.pair_a[e] >= p.pair_b[e]) return fail("bad vehicle pair");
-    }
-    p.max_iter = co->max_iter; p.max_backtrack = 25; p.filter_cap = 16;
+    set_ip_constants(p);
+    p.max_iter = co->max_iter;
     p.wb = spec->wb; p.dmin = spec->dmin; p.shrink = co->shrink_tube; p.dt0 = dt0[b];
     memcpy(p.bounds, spec->bounds, sizeof p.bounds); memcpy(p.g, spec->g, sizeof p.g);
     radau5_tables(p.A, p.B);
-    p.tol = co->tol; p.constr_viol_tol = co->constr_viol_tol; p.dual_inf_tol = 1.0; p.compl_inf_tol = 1e-4; p.mu_init = co->mu_init;
-    p.kappa_eps = 10.0; p.kappa_mu = 0.2; p.theta_mu = 1.5; p.tau_min = 0.99; p.bound_push = 1e-2; p.bound_frac = 1e-2; p.s_max = 100.0;
-    p.kappa_sigma = 1e10; p.eta_phi = 1e-8; p.gamma_theta = 1e-5; p.gamma_phi = 1e-8; p.delta_sw = 1.0; p.s_theta = 1.1; p.s_phi = 2.3;
+    p.tol = co->tol; p.constr_viol_tol = co->constr_viol_tol; p.mu_init = co->mu_init;
     // delta_c = 1e-7 of proximal type (cfz_colloc.inl): while a vehicle stands still with its heading along an axis, the
     // six ODE rows of x (or y) of an interval only see the rank-5 derivative matrix and their multipliers are not
     // determined.  Measured on the synthetic strategy: IPOPT's form of delta_c needs 288 iterations at 1e-9, 38 at 1e-7
     // and 30 at 3e-6 for the vehicle that waits, and leaves three of the four joint test problems unconverged at any
     // value; the proximal form solves all of them in 26-38 iterations at 1e-7, where the rows are met to ~2e-4 and the
     // cost is 0.65 % below the delta_c = 1e-9 value (constr_viol_tol is 1e-2, vehicle.py:651).
-    p.reg_primal = 1e-8; p.reg_dual = co->exact_rows ? 1e-9 : 1e-7; p.no_prox = (co->exact_rows ? 1 : 0) | (co->one_pivot ? 2 : 0) | ((co->structured && !co->one_pivot) ? 4 : 0);
-    // (the structured elimination packs a vehicle's interval count into eight bits: a longer plan goes through the band elimination,
-    // decided here, where the slab is sized, not discovered on the device -- ADVICE r5)
-    for (int a = 0; a < p.V; ++a) if (p.N[a] > 255) p.no_prox &= ~4;
+    p.reg_dual = co->exact_rows ? 1e-9 : 1e-7; p.no_prox = (co->exact_rows ? 1 : 0) | (co->one_pivot ? 2 : 0) | structured_bit(co->structured, co->one_pivot, p);
     p.vv_rows = co->vv_rows ? 1 : 0; p.curv_kappa = co->curv_kappa;
     p.obs_tab = dtab;
-    {  // half-bandwidth of this problem's ordering (51 for one vehicle)
-      const cfzc::CDims d = cfzc::cdims(p);
-      std::vector<int> pos((size_t)d.n + d.m);
-      if (cfzc::build_order(p, pos.data(), pos.data() + d.n) != d.nk) return fail("internal: ordering does not cover the band system");
-      kbs[b] = cfzc::half_bandwidth(p, pos.data(), pos.data() + d.n);
-    }
+    if ((kbs[b] = half_bandwidth_of(p)) < 0) return -1;
     xoff[b] = nx; nx += 7 * npts + 1;
     soff[b] = ns; ns += (long long)cfzc::work_doubles(p, kbs[b]);
     v0 += p.V;
@@ -398,8 +447,7 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
   ARENA_ALLOC(w->arena, dkb, (size_t)B * 4);
   HIP_OK(hipMemcpyAsync(dspec, specs.data(), sizeof(cfzc::CSpec) * B, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(dX, X.data(), (size_t)nx * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(doff, xoff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
-  HIP_OK(hipMemcpyAsync(doff + B, soff.data(), (size_t)B * 8, hipMemcpyHostToDevice, st));
+  HIP_OK(hipMemcpyAsync(doff, off.data(), (size_t)B * 2 * 8, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemcpyAsync(dkb, kbs.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
   HIP_OK(hipMemsetAsync(dslab, 0, (size_t)ns * 8, st));
   // One kernel: 512 threads per plan, band in global memory, panel elimination (`one_pivot`: one pivot at a time, the check of the
@@ -417,12 +465,8 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
     for (int b = 0; b < B; ++b) { nk_max = std::max(nk_max, cfzc::cdims(specs[b]).nk); kb_max = std::max(kb_max, (int)kbs[b]); }
     hipFuncAttributes fa;
     HIP_OK(hipFuncGetAttributes(&fa, (const void *)colloc_kernel));
-    HIP_OK(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, w->device));
-    {  // gfx950: a workgroup may own the whole LDS of its CU (160 KB); some runtimes report the smaller legacy figure per block
-      int per_cu = 0;
-      if (hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, w->device) == hipSuccess) lds_max = std::max(lds_max, per_cu);
-    }
-    if (std::getenv("CFZ_COLLOC_PROFILE")) fprintf(stderr, "cfz_colloc: LDS per workgroup %d B, static %zu B\n", lds_max, (size_t)fa.sharedSizeBytes);
+    if (lds_per_workgroup(w->device, &lds_max)) return -1;
+    if (profile) fprintf(stderr, "cfz_colloc: LDS per workgroup %d B, static %zu B\n", lds_max, (size_t)fa.sharedSizeBytes);
     const long long avail = ((long long)lds_max - (long long)fa.sharedSizeBytes) / 8;
     const long long pl = kb_max <= cfzc::kWideMaxKb ? (long long)CFZ_PANEL * (kb_max + CFZ_PANEL) : 0;
     const int lds_rhs = nk_max <= avail ? nk_max : 0;
@@ -458,7 +502,7 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
     if (status) status[b] = oi[2 * b + 1];
     if (iters) iters[b] = oi[2 * b];
     if (cost) cost[b] = od[(size_t)cfzc::kOutD * b];
-    if (std::getenv("CFZ_COLLOC_PROFILE")) {  // milliseconds per phase (100 MHz device clock)
+    if (profile) {  // milliseconds per phase (100 MHz device clock)
       const double *t = od.data() + (size_t)cfzc::kOutD * b + 3;
       fprintf(stderr, "cfz_colloc[%d]: %d vehicle(s), half-bandwidth %d, %d iterations, evaluate %.2f assemble %.2f factor %.2f substitute %.2f line search %.2f total %.2f ms (factor: panel / pivot search %.2f test / swap %.2f trailing columns / update %.2f)\n",
               b, specs[b].V, kbs[b], oi[2 * b], t[0] * 1e-5, t[1] * 1e-5, t[2] * 1e-5, t[3] * 1e-5, t[4] * 1e-5, t[5] * 1e-5, t[6] * 1e-5, t[7] * 1e-5, t[8] * 1e-5);
@@ -483,7 +527,7 @@ int cfz_colloc_w(cfz_plan_ws *w, int B, const cfz_spec *spec, const cfz_colloc_o
                  const double *dt0, double *traj, double *dt, int32_t *status, int32_t *iters, double *cost) {
   if (B < 1 || !spec || !co || !n_sets || !init_pose || !tube || !guess || !dt0 || !traj || !dt) return fail("bad argument");
   std::vector<int32_t> one((size_t)B, 1);
-  std::vector<std::vector<std::pair<int, int>>> none((size_t)B);
+  std::vector<PairList> none((size_t)B);
   return colloc_run(w, B, one.data(), none, spec, co, n_sets, init_pose, final_heading, tube, guess, dt0, traj, dt, status, iters, cost);
 }
 
@@ -499,14 +543,9 @@ int cfz_joint_colloc_w(cfz_plan_ws *w, int B, int V, const cfz_spec *spec, const
                        const double *init_pose, const double *final_heading, const double *tube, const double *guess, const double *dt0,
                        int n_pairs, const int32_t *pairs, double *traj, double *dt, int32_t *status, int32_t *iters, double *cost) {
   if (B < 1 || V < 1 || !spec || !co || !n_sets || !init_pose || !tube || !guess || !dt0 || !traj || !dt || n_pairs < 0) return fail("bad argument");
-  std::vector<std::pair<int, int>> pr;
-  if (pairs && V < 2) return fail("vehicle pairs need at least two vehicles");
-  if (pairs) for (int e = 0; e < n_pairs; ++e) {
-    if (pairs[2 * e] < 0 || pairs[2 * e] >= pairs[2 * e + 1] || pairs[2 * e + 1] >= V) return fail("bad vehicle pair");  // as colloc_run: 0 <= a < b < V
-    pr.push_back({pairs[2 * e], pairs[2 * e + 1]});
-  }
-  else for (int a = 0; a < V; ++a) for (int b = a + 1; b < V; ++b) pr.push_back({a, b});  // :56-58 all pairs
-  std::vector<std::vector<std::pair<int, int>>> all((size_t)B, pr);
+  PairList pr;
+  if (parse_pairs(V, n_pairs, pairs, pr)) return -1;
+  std::vector<PairList> all((size_t)B, pr);
   std::vector<int32_t> nv((size_t)B, V);
   return colloc_run(w, B, nv.data(), all, spec, co, n_sets, init_pose, final_heading, tube, guess, dt0, traj, dt, status, iters, cost);
 }
@@ -514,71 +553,29 @@ int cfz_joint_colloc_w(cfz_plan_ws *w, int B, int V, const cfz_spec *spec, const
 int cfz_colloc_band_info(int V, const int32_t *n_sets, const int32_t *has_final, int N_per_set, int n_obs, int n_pairs,
                          const int32_t *pairs, int32_t *nk, int32_t *kb, int64_t *band_bytes) {
   if (V < 1 || V > cfzc::kMaxVeh || !n_sets || N_per_set < 1 || n_obs < 0 || n_obs > cfzc::kMaxObs || n_pairs < 0) return fail("bad argument");
-  cfzc::CSpec p;
-  memset(&p, 0, sizeof p);
-  p.V = V; p.Nps = N_per_set; p.n_obs = n_obs;
-  for (int a = 0; a < V; ++a) {
-    if (n_sets[a] < 2) return fail("a plan needs at least two strategy steps");
-    p.n_chk[a] = n_sets[a] - 1; p.N[a] = N_per_set * p.n_chk[a]; p.has_final[a] = has_final ? (has_final[a] != 0) : 1;
-  }
-  std::vector<std::pair<int, int>> pr;
-  if (pairs && V < 2) return fail("vehicle pairs need at least two vehicles");
-  if (pairs) for (int e = 0; e < n_pairs; ++e) {
-    if (pairs[2 * e] < 0 || pairs[2 * e] >= pairs[2 * e + 1] || pairs[2 * e + 1] >= V) return fail("bad vehicle pair");  // as colloc_run: 0 <= a < b < V
-    pr.push_back({pairs[2 * e], pairs[2 * e + 1]});
-  }
-  else for (int a = 0; a < V; ++a) for (int b = a + 1; b < V; ++b) pr.push_back({a, b});
-  if ((int)pr.size() > cfzc::kMaxPairs) return fail("problem size outside compiled limits");
-  p.n_pairs = (int)pr.size();
-  for (int e = 0; e < p.n_pairs; ++e) { p.pair_a[e] = pr[e].first; p.pair_b[e] = pr[e].second; }
-  const cfzc::CDims d = cfzc::cdims(p);
-  std::vector<int> pos((size_t)d.n + d.m);
-  if (cfzc::build_order(p, pos.data(), pos.data() + d.n) != d.nk) return fail("internal: ordering does not cover the band system");
-  const int hb = cfzc::half_bandwidth(p, pos.data(), pos.data() + d.n);
-  if (nk) *nk = d.nk;
-  if (kb) *kb = hb;
-  if (band_bytes) *band_bytes = (int64_t)d.nk * (3 * hb + 1) * 8;
-  return 0;
+  return cfz_colloc_elimination_info(V, n_sets, has_final, N_per_set, n_obs, n_pairs, pairs, 0, nk, kb, band_bytes, nullptr, nullptr);
 }
 
 int cfz_colloc_elimination_info(int V, const int32_t *n_sets, const int32_t *has_final, int N_per_set, int n_obs, int n_pairs, const int32_t *pairs,
                                 int structured, int32_t *nk, int32_t *kb, int64_t *band_bytes, int64_t *alg_bytes, int64_t *workspace_bytes) {
   if (V < 1 || V > cfzc::kMaxVeh || !n_sets || N_per_set < 1 || n_obs < 0 || n_obs > cfzc::kMaxObs || n_pairs < 0) return fail("bad argument");
   if (structured != 0 && structured != 1) return fail("structured must be 0 (band) or 1 (cfz_jstruct.inl)");
+  PairList pr;
   cfzc::CSpec p;
   memset(&p, 0, sizeof p);
-  p.V = V; p.Nps = N_per_set; p.n_obs = n_obs; p.no_prox = structured ? 4 : 0;
-  for (int a = 0; a < V; ++a) {
-    if (n_sets[a] < 2) return fail("a plan needs at least two strategy steps");
-    p.n_chk[a] = n_sets[a] - 1; p.N[a] = N_per_set * p.n_chk[a]; p.has_final[a] = has_final ? (has_final[a] != 0) : 1;
-  }
-  for (int a = 0; a < V; ++a) if (p.N[a] > 255) p.no_prox &= ~4;  // (as colloc_run: such a plan goes through the band elimination)
-  std::vector<std::pair<int, int>> pr;
-  if (pairs && V < 2) return fail("vehicle pairs need at least two vehicles");
-  if (pairs) for (int e = 0; e < n_pairs; ++e) {
-    if (pairs[2 * e] < 0 || pairs[2 * e] >= pairs[2 * e + 1] || pairs[2 * e + 1] >= V) return fail("bad vehicle pair");
-    pr.push_back({pairs[2 * e], pairs[2 * e + 1]});
-  }
-  else for (int a = 0; a < V; ++a) for (int b = a + 1; b < V; ++b) pr.push_back({a, b});
-  if ((int)pr.size() > cfzc::kMaxPairs) return fail("problem size outside compiled limits");
-  p.n_pairs = (int)pr.size();
-  for (int e = 0; e < p.n_pairs; ++e) { p.pair_a[e] = pr[e].first; p.pair_b[e] = pr[e].second; }
+  if (parse_pairs(V, n_pairs, pairs, pr) || fill_shape(p, V, n_sets, [&](int a) { return has_final ? has_final[a] != 0 : true; }, N_per_set, n_obs, pr)) return -1;
+  p.no_prox = structured_bit(structured, 0, p);
+  const int hb = half_bandwidth_of(p);
+  if (hb < 0) return -1;
   const cfzc::CDims d = cfzc::cdims(p);
-  std::vector<int> pos((size_t)d.n + d.m);
-  if (cfzc::build_order(p, pos.data(), pos.data() + d.n) != d.nk) return fail("internal: ordering does not cover the band system");
-  const int hb = cfzc::half_bandwidth(p, pos.data(), pos.data() + d.n);
   const bool compact = cfzc::jstruct_mode(p);  // (as solve_colloc: no room for fill where nothing is factored in place)
   const size_t ld = compact ? 2 * (size_t)hb + 1 : 3 * (size_t)hb + 1;
   if (nk) *nk = d.nk;
   if (kb) *kb = hb;
   if (band_bytes) *band_bytes = (int64_t)d.nk * (int64_t)ld * 8;
-  if (alg_bytes) {
-    // per Newton system: the band elimination clears and assembles the band, then reads and writes it once while it eliminates;
-    // the structured elimination: jstruct_alg_doubles
-    size_t dbl = 3 * (size_t)d.nk * ld;
-    if (cfzc::jstruct_mode(p)) dbl = cfzc::jstruct_alg_doubles(p, d.nk, ld, d.npp);
-    *alg_bytes = (int64_t)dbl * 8;
-  }
+  // per Newton system: the band elimination clears and assembles the band, then reads and writes it once while it eliminates;
+  // the structured elimination: jstruct_alg_doubles
+  if (alg_bytes) *alg_bytes = (int64_t)(compact ? cfzc::jstruct_alg_doubles(p, d.nk, ld, d.npp) : 3 * (size_t)d.nk * ld) * 8;
   if (workspace_bytes) *workspace_bytes = (int64_t)cfzc::work_doubles(p, hb) * 8;
   return 0;
 }

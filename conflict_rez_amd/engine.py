@@ -40,6 +40,13 @@ class _CPlanOptions(C.Structure):
         ("tol", C.c_double), ("constr_viol_tol", C.c_double), ("mu_init", C.c_double), ("curv_kappa", C.c_double)]
 
 
+class _CCollocOptions(C.Structure):
+    _fields_ = [("N_per_set", C.c_int32), ("max_iter", C.c_int32), ("exact_rows", C.c_int32), ("one_pivot", C.c_int32), ("vv_rows", C.c_int32), ("kernel", C.c_int32),
+                ("shrink_tube", C.c_double),
+                ("tol", C.c_double), ("constr_viol_tol", C.c_double), ("mu_init", C.c_double), ("curv_kappa", C.c_double),
+                ("structured", C.c_int32), ("reserved1", C.c_int32)]
+
+
 class _COptions(C.Structure):
     _fields_ = [(k, C.c_int32) for k in _OPT_INTS] + [(k, C.c_double) for k in _OPT_DBLS]
 
@@ -119,6 +126,9 @@ def load_library(path=None):
     if not hasattr(lib, "cfz_abi_version") or lib.cfz_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: struct layout version {lib.cfz_abi_version() if hasattr(lib, 'cfz_abi_version') else 'none'}, this binding is written against {ABI_VERSION}: rebuild the library")
     lib.cfz_last_error.restype = C.c_char_p
+    lib.cfz_source_hash.restype = C.c_char_p
+    lib.cfz_colloc_band_info.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.cfz_colloc_elimination_info.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int] + [vp] * 5
     lib.cfz_default_spec.argtypes = [C.POINTER(_CSpec)]
     lib.cfz_default_options.argtypes = [C.POINTER(_COptions)]
     lib.cfz_create.argtypes = [C.POINTER(_CSpec), C.POINTER(_COptions), C.c_int, C.c_int, C.POINTER(vp)]
@@ -190,15 +200,23 @@ EXPORTS = (
 ARRIVE_TOL = dict(pos_tol=0.3, psi_tol=0.1, v_tol=0.1)
 
 
-def default_options(**overrides):
-    lib = load_library()
-    o = _COptions()
-    lib.cfz_default_options(C.byref(o))
-    for k, v in overrides.items():
+def _options(struct_type, default_fn_name, what, options):
+    """The library's defaults of one of its option structs with the overrides `options` applied (an array field element by element);
+    a name the struct does not have is refused, not dropped."""
+    o = struct_type()
+    getattr(load_library(), default_fn_name)(C.byref(o))
+    for k, v in options.items():
         if not hasattr(o, k):
-            raise TypeError(f"unknown solver option {k!r}")
-        setattr(o, k, v)
+            raise TypeError(f"unknown {what} option {k!r}")
+        if isinstance(getattr(o, k), C.Array):
+            getattr(o, k)[:] = [float(x) for x in v]
+        else:
+            setattr(o, k, v)
     return o
+
+
+def default_options(**overrides):
+    return _options(_COptions, "cfz_default_options", "solver", overrides)
 
 
 def problem_check(base, spec, base_options=None, **options):
@@ -258,12 +276,31 @@ def _f64(a, shape):
     return a
 
 
+def _ck(rc, name):
+    if rc != 0:
+        raise RuntimeError(f"{name}: " + load_library().cfz_last_error().decode())
+
+
+def _pack_tubes(tubes):
+    """Per vehicle a list over strategy steps 1.. of ((A_back, b_back), (A_front, b_front)) -> the 24 doubles per step the library reads."""
+    return np.ascontiguousarray(np.concatenate([np.concatenate([np.asarray(A, float).ravel(), np.asarray(b, float).ravel()])
+                                                for t in tubes for cellpair in t for (A, b) in cellpair]))
+
+
+def _headings(final_headings, n):
+    """Terminal headings [n], NaN where a vehicle has none (None, or no list at all)."""
+    return np.array([np.nan if (final_headings is None or final_headings[b] is None) else float(final_headings[b]) for b in range(n)])
+
+
+def _pairs(pairs):
+    """Vehicle pairs as int32 [n, 2]; None (every pair) stays None."""
+    return None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+
+
 def trim_default_workspaces():
     """`cfz_plan_ws_trim(NULL)`: release the device memory of the calling thread's own workspaces behind `state_ws`, `colloc`,
     `joint_colloc` called without `ws=` (a 256-plan joint launch leaves 25 GB there)."""
-    lib = load_library()
-    if lib.cfz_plan_ws_trim(None) != 0:
-        raise RuntimeError("cfz_plan_ws_trim: " + lib.cfz_last_error().decode())
+    _ck(load_library().cfz_plan_ws_trim(None), "cfz_plan_ws_trim")
 
 
 class PlanWorkspace:
@@ -273,13 +310,11 @@ class PlanWorkspace:
     def __init__(self, device: int = 0):
         self.lib = load_library()
         self._w = C.c_void_p()
-        if self.lib.cfz_plan_ws_create(int(device), C.byref(self._w)) != 0:
-            raise RuntimeError("cfz_plan_ws_create: " + self.lib.cfz_last_error().decode())
+        _ck(self.lib.cfz_plan_ws_create(int(device), C.byref(self._w)), "cfz_plan_ws_create")
 
     def trim(self):
         """`cfz_plan_ws_trim`: give the device memory held between calls back now (the next call allocates again)."""
-        if self.lib.cfz_plan_ws_trim(self._w) != 0:
-            raise RuntimeError("cfz_plan_ws_trim: " + self.lib.cfz_last_error().decode())
+        _ck(self.lib.cfz_plan_ws_trim(self._w), "cfz_plan_ws_trim")
 
     def close(self):
         if getattr(self, "_w", None):
@@ -298,12 +333,11 @@ def state_ws_default_guess(init_pose, tube, final_heading=None, N=30):
     (host arithmetic, no GPU).  tube as for `state_ws` (one vehicle); returns [N (n_sets - 1) + 1, 3]."""
     lib = load_library()
     n_sets = len(tube) + 1
-    t = np.ascontiguousarray(np.concatenate([np.concatenate([np.asarray(A, float).ravel(), np.asarray(b, float).ravel()]) for cellpair in tube for (A, b) in cellpair]))
+    t = _pack_tubes([tube])
     g = np.zeros((N * (n_sets - 1) + 1, 3))
     p0 = _f64(np.asarray(init_pose, float)[:3], (3,))
-    rc = lib.cfz_state_ws_default_guess(n_sets, N, _ptr(p0), float("nan") if final_heading is None else float(final_heading), _ptr(t), _ptr(g))
-    if rc != 0:
-        raise RuntimeError("cfz_state_ws_default_guess: " + lib.cfz_last_error().decode())
+    _ck(lib.cfz_state_ws_default_guess(n_sets, N, _ptr(p0), float("nan") if final_heading is None else float(final_heading), _ptr(t), _ptr(g)),
+        "cfz_state_ws_default_guess")
     return g
 
 
@@ -315,20 +349,13 @@ def state_ws(init_poses, tubes, guesses=None, final_headings=None, device=0, ws=
     options: fields of `cfz_plan_options` (N, dt, wb, shrink_tube, bounded_input, max_iter, tol, ...).
     Returns a list of dict(traj [T+1,7], status, iters, cost)."""
     lib = load_library()
-    po = _CPlanOptions()
-    lib.cfz_default_plan_options(C.byref(po))
-    for k, v in options.items():
-        if k == "bounds":
-            po.bounds[:] = [float(x) for x in v]
-        else:
-            setattr(po, k, v)
+    po = _options(_CPlanOptions, "cfz_default_plan_options", "plan", options)
     B = len(tubes)
     n_sets = np.array([len(t) + 1 for t in tubes], dtype=np.int32)
     T = po.N * (n_sets - 1)
-    tube = np.concatenate([np.concatenate([np.concatenate([np.asarray(A, float).ravel(), np.asarray(b, float).ravel()])
-                                           for cellpair in t for (A, b) in cellpair]) for t in tubes])
+    tube = _pack_tubes(tubes)
     init = _f64(np.asarray(init_poses, float), (B, 3))
-    fh = np.array([np.nan if (final_headings is None or final_headings[b] is None) else float(final_headings[b]) for b in range(B)])
+    fh = _headings(final_headings, B)
     guess = None
     if guesses is not None and any(g is not None for g in guesses):
         # a mixed batch (the reference's own `spline_ws_config`: vehicle_0 without a spline guess, the others with one): the vehicles
@@ -339,23 +366,13 @@ def state_ws(init_poses, tubes, guesses=None, final_headings=None, device=0, ws=
         assert guess.shape[0] == int((T + 1).sum())
     traj = np.zeros((int((T + 1).sum()), 7))
     status, iters, cost = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
-    args = (B, C.byref(po), _ptr(n_sets), _ptr(init), _ptr(fh), _ptr(np.ascontiguousarray(tube)), _ptr(guess),
-            _ptr(traj), _ptr(status), _ptr(iters), _ptr(cost))
-    rc = lib.cfz_state_ws(int(device), *args) if ws is None else lib.cfz_state_ws_w(ws._w, *args)
-    if rc != 0:
-        raise RuntimeError("cfz_state_ws: " + lib.cfz_last_error().decode())
+    args = (B, C.byref(po), _ptr(n_sets), _ptr(init), _ptr(fh), _ptr(tube), _ptr(guess), _ptr(traj), _ptr(status), _ptr(iters), _ptr(cost))
+    _ck(lib.cfz_state_ws(int(device), *args) if ws is None else lib.cfz_state_ws_w(ws._w, *args), "cfz_state_ws")
     out, o = [], 0
     for b in range(B):
         out.append(dict(traj=traj[o : o + T[b] + 1].copy(), status=int(status[b]), iters=int(iters[b]), cost=float(cost[b])))
         o += T[b] + 1
     return out
-
-
-class _CCollocOptions(C.Structure):
-    _fields_ = [("N_per_set", C.c_int32), ("max_iter", C.c_int32), ("exact_rows", C.c_int32), ("one_pivot", C.c_int32), ("vv_rows", C.c_int32), ("kernel", C.c_int32),
-                ("shrink_tube", C.c_double),
-                ("tol", C.c_double), ("constr_viol_tol", C.c_double), ("mu_init", C.c_double), ("curv_kappa", C.c_double),
-                ("structured", C.c_int32), ("reserved1", C.c_int32)]
 
 
 def colloc(spec, init_poses, tubes, guesses, dt0s, final_headings=None, device=0, ws=None, **options):
@@ -365,19 +382,13 @@ def colloc(spec, init_poses, tubes, guesses, dt0s, final_headings=None, device=0
     options: fields of `cfz_colloc_options` (N_per_set, max_iter, shrink_tube, tol, constr_viol_tol, ...).
     Returns a list of dict(traj [N, 6, 7], dt, status, iters, cost)."""
     lib = load_library()
-    co = _CCollocOptions()
-    lib.cfz_default_colloc_options(C.byref(co))
-    for k, v in options.items():
-        if not hasattr(co, k):
-            raise TypeError(f"unknown collocation option {k!r}")
-        setattr(co, k, v)
+    co = _options(_CCollocOptions, "cfz_default_colloc_options", "collocation", options)
     B = len(tubes)
     n_sets = np.array([len(t) + 1 for t in tubes], dtype=np.int32)
     Np = co.N_per_set * (n_sets - 1) * 6
-    tube = np.ascontiguousarray(np.concatenate([np.concatenate([np.concatenate([np.asarray(A, float).ravel(), np.asarray(b, float).ravel()])
-                                                                for cellpair in t for (A, b) in cellpair]) for t in tubes]))
+    tube = _pack_tubes(tubes)
     init = _f64(np.asarray(init_poses, float), (B, 3))
-    fh = np.array([np.nan if (final_headings is None or final_headings[b] is None) else float(final_headings[b]) for b in range(B)])
+    fh = _headings(final_headings, B)
     guess = np.ascontiguousarray(np.concatenate([_f64(np.asarray(g, float), (int(Np[b]), 7)) for b, g in enumerate(guesses)]))
     dt0 = _f64(np.asarray(dt0s, float), (B,))
     traj, dt = np.zeros((int(Np.sum()), 7)), np.zeros(B)
@@ -385,9 +396,7 @@ def colloc(spec, init_poses, tubes, guesses, dt0s, final_headings=None, device=0
     cs = spec.to_c()
     args = (B, C.byref(cs), C.byref(co), _ptr(n_sets), _ptr(init), _ptr(fh), _ptr(tube), _ptr(guess), _ptr(dt0),
             _ptr(traj), _ptr(dt), _ptr(status), _ptr(iters), _ptr(cost))
-    rc = lib.cfz_colloc(int(device), *args) if ws is None else lib.cfz_colloc_w(ws._w, *args)
-    if rc != 0:
-        raise RuntimeError("cfz_colloc: " + lib.cfz_last_error().decode())
+    _ck(lib.cfz_colloc(int(device), *args) if ws is None else lib.cfz_colloc_w(ws._w, *args), "cfz_colloc")
     out, o = [], 0
     for b in range(B):
         out.append(dict(traj=traj[o : o + Np[b]].reshape(-1, 6, 7).copy(), dt=float(dt[b]), status=int(status[b]), iters=int(iters[b]), cost=float(cost[b])))
@@ -398,7 +407,6 @@ def colloc(spec, init_poses, tubes, guesses, dt0s, final_headings=None, device=0
 def source_hash():
     """`cfz_source_hash`: which kernel sources the loaded library was built from (16 hex digits, or "unknown")."""
     lib = load_library()
-    lib.cfz_source_hash.restype = C.c_char_p
     return lib.cfz_source_hash().decode()
 
 
@@ -408,13 +416,10 @@ def colloc_band_info(n_sets, N_per_set=5, n_obs=6, pairs=None, has_final=None):
     lib = load_library()
     ns = np.ascontiguousarray(np.asarray(n_sets, np.int32))
     hf = None if has_final is None else np.ascontiguousarray(np.asarray(has_final, np.int32))
-    pr = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    pr = _pairs(pairs)
     nk, kb, bb = C.c_int32(), C.c_int32(), C.c_int64()
-    lib.cfz_colloc_band_info.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    rc = lib.cfz_colloc_band_info(len(ns), _ptr(ns), _ptr(hf), int(N_per_set), int(n_obs), 0 if pr is None else len(pr), _ptr(pr),
-                                  C.addressof(nk), C.addressof(kb), C.addressof(bb))
-    if rc != 0:
-        raise RuntimeError("cfz_colloc_band_info: " + lib.cfz_last_error().decode())
+    _ck(lib.cfz_colloc_band_info(len(ns), _ptr(ns), _ptr(hf), int(N_per_set), int(n_obs), 0 if pr is None else len(pr), _ptr(pr),
+                                 C.addressof(nk), C.addressof(kb), C.addressof(bb)), "cfz_colloc_band_info")
     return int(nk.value), int(kb.value), int(bb.value)
 
 
@@ -424,13 +429,10 @@ def colloc_elimination_info(n_sets, N_per_set=5, n_obs=6, pairs=None, has_final=
     lib = load_library()
     ns = np.ascontiguousarray(np.asarray(n_sets, np.int32))
     hf = None if has_final is None else np.ascontiguousarray(np.asarray(has_final, np.int32))
-    pr = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    pr = _pairs(pairs)
     nk, kb, bb, ab, wb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
-    lib.cfz_colloc_elimination_info.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-    rc = lib.cfz_colloc_elimination_info(len(ns), _ptr(ns), _ptr(hf), int(N_per_set), int(n_obs), 0 if pr is None else len(pr), _ptr(pr), int(structured),
-                                         C.addressof(nk), C.addressof(kb), C.addressof(bb), C.addressof(ab), C.addressof(wb))
-    if rc != 0:
-        raise RuntimeError("cfz_colloc_elimination_info: " + lib.cfz_last_error().decode())
+    _ck(lib.cfz_colloc_elimination_info(len(ns), _ptr(ns), _ptr(hf), int(N_per_set), int(n_obs), 0 if pr is None else len(pr), _ptr(pr), int(structured),
+                                        C.addressof(nk), C.addressof(kb), C.addressof(bb), C.addressof(ab), C.addressof(wb)), "cfz_colloc_elimination_info")
     return dict(nk=int(nk.value), kb=int(kb.value), band_bytes=int(bb.value), alg_bytes=int(ab.value), workspace_bytes=int(wb.value))
 
 
@@ -440,34 +442,25 @@ def joint_colloc_batch(spec, scenarios, pairs=None, device=0, ws=None, **options
     final_headings) with per-vehicle entries as in `colloc`, the same V in every scenario; pairs: list of (a, b) vehicle
     index pairs, default all.  Returns a list of dict(traj: per vehicle [N_a, 6, 7], dt, status, iters, cost)."""
     lib = load_library()
-    co = _CCollocOptions()
-    lib.cfz_default_colloc_options(C.byref(co))
-    for k, v in options.items():
-        if not hasattr(co, k):
-            raise TypeError(f"unknown collocation option {k!r}")
-        setattr(co, k, v)
+    co = _options(_CCollocOptions, "cfz_default_colloc_options", "collocation", options)
     B, V = len(scenarios), len(scenarios[0]["tubes"])
     assert all(len(sc["tubes"]) == V for sc in scenarios)
     tubes = [t for sc in scenarios for t in sc["tubes"]]
     n_sets = np.array([len(t) + 1 for t in tubes], dtype=np.int32)
     Np = co.N_per_set * (n_sets - 1) * 6
-    tube = np.ascontiguousarray(np.concatenate([np.concatenate([np.concatenate([np.asarray(A, float).ravel(), np.asarray(b, float).ravel()])
-                                                                for cellpair in t for (A, b) in cellpair]) for t in tubes]))
+    tube = _pack_tubes(tubes)
     init = _f64(np.concatenate([np.asarray(sc["init_poses"], float).reshape(V, 3) for sc in scenarios]), (B * V, 3))
-    fhs = [fh for sc in scenarios for fh in (sc.get("final_headings") or [None] * V)]
-    fh = np.array([np.nan if f is None else float(f) for f in fhs])
+    fh = _headings([f for sc in scenarios for f in (sc.get("final_headings") or [None] * V)], B * V)
     guesses = [g for sc in scenarios for g in sc["guesses"]]
     guess = np.ascontiguousarray(np.concatenate([_f64(np.asarray(g, float), (int(Np[b]), 7)) for b, g in enumerate(guesses)]))
     dt0 = _f64(np.array([float(sc["dt0"]) for sc in scenarios]), (B,))
-    pr = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    pr = _pairs(pairs)
     traj, dt = np.zeros((int(Np.sum()), 7)), np.zeros(B)
     status, iters, cost = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
     cs = spec.to_c()
     args = (B, V, C.byref(cs), C.byref(co), _ptr(n_sets), _ptr(init), _ptr(fh), _ptr(tube), _ptr(guess), _ptr(dt0),
             0 if pr is None else len(pr), _ptr(pr), _ptr(traj), _ptr(dt), _ptr(status), _ptr(iters), _ptr(cost))
-    rc = lib.cfz_joint_colloc(int(device), *args) if ws is None else lib.cfz_joint_colloc_w(ws._w, *args)
-    if rc != 0:
-        raise RuntimeError("cfz_joint_colloc: " + lib.cfz_last_error().decode())
+    _ck(lib.cfz_joint_colloc(int(device), *args) if ws is None else lib.cfz_joint_colloc_w(ws._w, *args), "cfz_joint_colloc")
     out, o = [], 0
     for b in range(B):
         tr = []
@@ -497,8 +490,7 @@ class Engine:
         self._S = self._V = 0  # scenarios and vehicles of the closed loop; 0 until loop_init (the library refuses loop calls before it)
         self._rec_cap = self._rec_used = 0
         cs, co = spec.to_c(), default_options(**options)
-        if self.lib.cfz_create(C.byref(cs), C.byref(co), int(device), self.max_batch, C.byref(self._h)) != 0:
-            raise RuntimeError("cfz_create: " + self.lib.cfz_last_error().decode())
+        _ck(self.lib.cfz_create(C.byref(cs), C.byref(co), int(device), self.max_batch, C.byref(self._h)), "cfz_create")
 
     def close(self):
         if getattr(self, "_h", None):
@@ -511,9 +503,7 @@ class Engine:
         except Exception:
             pass
 
-    def _ck(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what}: " + self.lib.cfz_last_error().decode())
+    _ck = staticmethod(_ck)
 
     # ---- host-buffer path ------------------------------------------------------------------
     def solve(self, x0, ref, nbr, zu, want_duals=True, carry=None, slots=None):

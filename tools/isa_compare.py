@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 code of cfz_engine.hip between two source trees, function by function (no GPU needed).
+"""Compare the gfx950 code of one translation unit (--unit, default cfz_engine.hip) between two source trees, function by function
+(no GPU needed).
 
     python tools/isa_compare.py                      # the checked-in HEAD (a temporary git worktree) against the working tree
     python tools/isa_compare.py --base-ref HEAD~1    # ... the parent of a commit already made
     python tools/isa_compare.py OLD NEW [-k NAME ...]  # two trees (conflict_rez_amd/csrc with include/ beside it), or two .s listings
+    python tools/isa_compare.py --unit cfz_planning.hip --base-ref HEAD~1   # the planning kernels
 
-Each tree's cfz_engine.hip is compiled with the flags of __graft_entry__.build plus `-S --cuda-device-only` (about a minute on one
+Each tree's unit is compiled with the flags of __graft_entry__.build plus `-S --cuda-device-only` (about a minute on one
 core; the two run side by side).  The listing is split at the function labels, comments are dropped and the `.L...` labels are
 renumbered by first appearance inside each function, so that a function whose code did not change compares equal even when
 functions were added or removed around it.  Per function: the instruction count on either side, `same` or `different`, and the
 figures DESIGN.md tabulates for the kernels (.vgpr_count, .vgpr_spill_count, .sgpr_spill_count, .private_segment_fixed_size).
-The exit status is 1 when a function named with -k (default: the twelve solver kernels) differs, is missing, or changed its figures.
+The exit status is 1 when a function named with -k differs, is missing, or changed its figures (default: the twelve solver kernels
+of cfz_engine.hip; EVERY function of cfz_planning.hip -- both state_ws_kernel instantiations, colloc_kernel and the out-of-line device
+functions -- in either listing).
 It compares text and searches for no particular instruction.  `--markdown` prints the kernels' rows as a table for DESIGN.md."""
 import argparse
 import os
@@ -28,8 +32,11 @@ SOLVER_KERNELS = ("solve_kernel", "solve_kernel_pool", "loop_kernel", "loop_kern
 META = (".vgpr_count", ".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size")
 
 
-def start_compile(tree, out):
-    src = os.path.join(tree, "conflict_rez_amd", "csrc", "cfz_engine.hip")
+UNITS = ("cfz_engine.hip", "cfz_planning.hip")
+
+
+def start_compile(tree, out, unit):
+    src = os.path.join(tree, "conflict_rez_amd", "csrc", unit)
     if not os.path.exists(src):
         sys.exit(f"{src}: no such file")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -51,7 +58,8 @@ def short_name(sym):
         i += n.end()
         last = sym[i:i + int(n.group())]
         i += int(n.group())
-    return last or sym
+    b = re.match(r"ILb([01])E", sym[i:])  # a kernel instantiated on one bool: state_ws_kernel<true>
+    return (last + ("<true>" if b.group(1) == "1" else "<false>") if b else last) if last else sym
 
 
 def parse(listing):
@@ -110,13 +118,14 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("trees", nargs="*", help="OLD NEW: source trees or .s listings (default: --base-ref and the working tree)")
     ap.add_argument("--base-ref", default="HEAD", help="the commit the working tree is compared with when no trees are given")
-    ap.add_argument("-k", "--kernel", action="append", help="a function that must be the same (default: the twelve solver kernels)")
+    ap.add_argument("--unit", choices=UNITS, default=UNITS[0], help="the translation unit to compile in either tree")
+    ap.add_argument("-k", "--kernel", action="append", help="a function that must be the same (default: see above)")
     ap.add_argument("--keep", metavar="DIR", help="keep the two listings as DIR/old.s and DIR/new.s")
     ap.add_argument("--markdown", action="store_true", help="print the named functions as a markdown table")
     a = ap.parse_args()
     if len(a.trees) not in (0, 2):
         ap.error("give two trees or none")
-    must = tuple(a.kernel) if a.kernel else SOLVER_KERNELS
+    must = tuple(a.kernel) if a.kernel else SOLVER_KERNELS if a.unit == UNITS[0] else None  # None: every function
     with tempfile.TemporaryDirectory() as tmp:
         out = a.keep or tmp
         os.makedirs(out, exist_ok=True)
@@ -132,7 +141,7 @@ def main():
                     listings.append(tree)
                 else:
                     listings.append(os.path.join(out, name))
-                    procs.append(start_compile(os.path.abspath(tree), listings[-1]))
+                    procs.append(start_compile(os.path.abspath(tree), listings[-1], a.unit))
             if any([p.wait() != 0 for p in procs]):
                 sys.exit("hipcc failed")
         finally:
@@ -140,6 +149,8 @@ def main():
                 subprocess.call(["git", "-C", ROOT, "worktree", "remove", "--force", worktree])
         (fa, ma), (fb, mb) = parse(listings[0]), parse(listings[1])
     bad, rows = [], []
+    if must is None:
+        must = tuple(dict.fromkeys(short_name(s) for s in list(fa) + list(fb)))
     for sym in list(fa) + [s for s in fb if s not in fa]:
         name = short_name(sym)
         if sym not in fa or sym not in fb:
@@ -158,7 +169,7 @@ def main():
         print("|---|---|---|---|---|---|---|")
         for name, na, nb, verdict, figs in rows:
             if name in must:
-                print(f"| `{name}` | {na} / {nb} | " + " | ".join(figs) + f" | {verdict} |")
+                print(f"| `{name}` | {na} / {nb} | " + " | ".join(figs or ["-"] * len(META)) + f" | {verdict} |")
     else:
         print(f"{'function':34s} {'instructions':>17s}  {'':10s} " + " ".join(f"{k:>15s}" for k in ("vgpr", "vgpr_spill", "sgpr_spill", "scratch")) + "   (old / new)")
         for name, na, nb, verdict, figs in rows:
