@@ -255,10 +255,19 @@ __global__ __launch_bounds__(1024) void order_by_iters(int B, const int32_t *ite
 // (release), device-scope atomic; consumer: atomic load of the slot, __threadfence() (acquire), payload loads.
 // The pop has no lane-divergent control flow (all lanes issue the same loads; atomics add 1 from lane 0 and 0 from
 // the others): a value defined under `if (lane == 0)` and broadcast afterwards was miscompiled by hipcc 7.2.
+// CFZ_LOOP_TRACE (diagnostic builds, tools/build_variant.sh): CFZ_MARK leaves every workgroup's last phase for the watchdog;
+// CFZ_ITEM_STAMP writes item (t, b)'s record of kLoopTraceWords 64-bit words: the constant 100 MHz clock after the pop [0], at the start [1]
+// and the end [2] of the solve and after the release [3], and 1 + whether the item ran prioritised [4] (0: the item never ran).
+// tools/loop_priority_trace.py reads them through cfz_loop_trace_read.  Neither exists in the product build.
 #ifdef CFZ_LOOP_TRACE
+constexpr int kLoopTraceWords = 5;
+__device__ long long *cfz_loop_trace_buf;
 #define CFZ_MARK(c) do { if (threadIdx.x == 0) __hip_atomic_store(&ctrl[4 + blockIdx.x], (c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while (0)
+#define CFZ_ITEM_STAMP(w, flag) do { if (threadIdx.x == 0) { long long *cfz_r = cfz_loop_trace_buf + ((size_t)t * B + b) * kLoopTraceWords;      \
+                                                        cfz_r[w] = (long long)wall_clock64(); if ((w) == 0) cfz_r[4] = 1 + (flag); } } while (0)
 #else
 #define CFZ_MARK(c) do { } while (0)
+#define CFZ_ITEM_STAMP(w, flag) do { } while (0)
 #endif
 //   ref_table[P][V][T][7], table_of[S]: the pool of plan sets and the one each scenario follows (as loop_prep)
 //   rec[K][S][V][7], rec_si[K][2][S][V]: the record of this launch's iterations (NULL: none; as loop_post)
@@ -278,7 +287,7 @@ __global__ __launch_bounds__(1024) void order_by_iters(int B, const int32_t *ite
 #define CFZ_LOOP_ARGS const KArgs *__restrict__ ka, int S, int V, int K, int T, const double *ref_table, const int32_t *table_of,        \
                       const int32_t *kidx0, int t_base, double *pred, double *state, double *scratch, int32_t *qbuf, int32_t *ctrl,       \
                       int32_t *done, int32_t *status, int32_t *iters, double *stats, int32_t *iter_sum, double *wst, int wst_stride,     \
-                      int prio_lag, double *rec, int32_t *rec_si
+                      int prio_lag, int prio_tail, double *rec, int32_t *rec_si
 __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(CFZ_LOOP_ARGS) {
   constexpr bool kSeq = false, kDist = false, kComm = false, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
@@ -376,6 +385,12 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
 
 // The ten persistent kernels, stated once: what each was compiled with (dist: kDist, and so on).  create_fill, the occupancy query and
 // the launch of cfz_loop_run all go through this table; a new kernel is one more row here and one more line in cfz_loop_run's chain.
+// The built-in priority setting of cfz_loop_run, chosen by measurement (docs/notebook.md "Issue priority on the critical path"): the items
+// of the oldest open iteration, and no rank condition (a divisor d > 0 would add one: the last B / d positions of an iteration's queue)
+constexpr int kLoopPrioLag = 0, kLoopPrioTailDiv = 0;
+#ifdef CFZ_LOOP_TRACE
+long long *g_loop_trace_dev = nullptr; size_t g_loop_trace_items = 0; int g_loop_trace_grid = 0;
+#endif
 struct LoopVariant { const void *fn; bool seq, dist, comm, pool; };
 const LoopVariant kLoopVariants[10] = {
     {(const void *)loop_kernel, false, false, false, false},          {(const void *)loop_kernel_seq, true, false, false, false},
@@ -1597,7 +1612,25 @@ int cfz_loop_run(cfz_handle *h, int K) {
   HIP_OK(hipEventRecord(h->ev0, h->stream));
   double *rec; int32_t *rec_si;
   record_slice(h, rec, rec_si);
-  const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : 0;
+  // Issue priority for the items on the launch's critical path (cfz_loop_body.inl).  CFZ_LOOP_PRIO_LAG: an item of iteration t
+  // qualifies while t <= lowest open iteration + lag (negative: no item is ever prioritised).  CFZ_LOOP_PRIO_TAIL: from iteration 1 on
+  // it must also hold one of the last `tail` positions of its iteration's queue (0: the iteration alone decides; unset: the built-in
+  // setting, kLoopPrioTailDiv).  Overrides for experiments, read at every call; the results do not depend on either.
+  const int prio_lag = std::getenv("CFZ_LOOP_PRIO_LAG") ? std::atoi(std::getenv("CFZ_LOOP_PRIO_LAG")) : kLoopPrioLag;
+  const int prio_tail = std::getenv("CFZ_LOOP_PRIO_TAIL") ? std::max(0, std::atoi(std::getenv("CFZ_LOOP_PRIO_TAIL")))
+                                                          : (kLoopPrioTailDiv > 0 ? std::max(V, B / kLoopPrioTailDiv) : 0);
+#ifdef CFZ_LOOP_TRACE
+  {
+    static long long *trace_dev = nullptr; static size_t trace_cap = 0;
+    if (trace_cap < total) {
+      if (trace_dev) (void)hipFree(trace_dev);
+      HIP_OK(hipMalloc(&trace_dev, total * kLoopTraceWords * 8)); trace_cap = total;
+      HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(cfz_loop_trace_buf), &trace_dev, sizeof trace_dev));
+    }
+    HIP_OK(hipMemsetAsync(trace_dev, 0, total * kLoopTraceWords * 8, h->stream));
+    g_loop_trace_dev = trace_dev; g_loop_trace_items = total; g_loop_trace_grid = grid;
+  }
+#endif
   // The ten kernels share their arguments up to the record; what follows is the tail groups of the settings a kernel was compiled
   // with, in this order.  One line per row of kLoopVariants, in its order; `launch` refuses a line that names another kernel than its row.
   const auto xo = std::make_tuple((const int32_t *)h->lp.xperm, (const int32_t *)h->lp.xrank);
@@ -1609,7 +1642,7 @@ int cfz_loop_run(cfz_handle *h, int K) {
     std::apply([&](auto... tail) {
       hipLaunchKernelGGL(kernel, dim3(grid), dim3(cfz::kNL), h->lds_bytes, h->stream, h->kargs, S, V, K, h->lp.T, h->lp.ref_table, h->lp.table_of,
                          h->lp.kidx, 0, h->lp.pred2, h->lp.state, h->lp.scratch, h->lp.queue, h->lp.ctrl, h->lp.done, h->status, h->iters, h->stats,
-                         h->lp.iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, rec, rec_si, tail...);
+                         h->lp.iter_sum, h->carry_duals ? h->wst : nullptr, h->wst_stride, prio_lag, prio_tail, rec, rec_si, tail...);
     }, std::tuple_cat(groups...));
     return 0;
   };
@@ -1672,6 +1705,16 @@ int cfz_loop_run(cfz_handle *h, int K) {
   if (ctrl[2]) return fail("persistent loop kernel timed out waiting for a work item");
   return 0;
 }
+
+#ifdef CFZ_LOOP_TRACE
+// diagnostic build only: the trace of the last cfz_loop_run, out[K * B][kLoopTraceWords] in item order (t, b); returns the grid of
+// that launch (the resident workgroups), -1 when n is not K * B
+extern "C" int cfz_loop_trace_read(long long *out, long n) {
+  if (!out || !g_loop_trace_dev || (size_t)n != g_loop_trace_items) return fail("cfz_loop_trace_read: no trace of that many items");
+  HIP_OK(hipMemcpy(out, g_loop_trace_dev, g_loop_trace_items * kLoopTraceWords * 8, hipMemcpyDeviceToHost));
+  return g_loop_trace_grid;
+}
+#endif
 
 long cfz_loop_last_iterations(const cfz_handle *h) { return h ? h->last_iter_sum : -1; }
 long cfz_loop_last_converged(const cfz_handle *h) { return h ? h->last_converged : -1; }

@@ -14,22 +14,21 @@
   double *ref = my + 5;  // (the record keeps the layout x0 | ref | nbr | zu of the stepwise path; only ref is used here)
   double *dn = ref + 3 * N;  // kDist: d[5:12] of the item in hand, kept from the parameter phase to the plant in the idle nbr | zu slots
   int32_t *head = qbuf, *tail = qbuf + K, *slots = qbuf + 2 * K;
-  // what wavefront 0 popped, for wavefront 1: {iteration t (-1: leave), instance b}.  Lives in the reduction exchange
-  // area of the workspace, which is idle between two solves.
+  // what wavefront 0 popped, for wavefront 1: {iteration t (-1: leave), instance b, whether the item runs at raised issue priority}.
+  // Lives in the reduction exchange area of the workspace, which is idle between two solves.
   volatile int32_t *cmd = reinterpret_cast<volatile int32_t *>(smem + L.xw);
 #define CFZ_LD(p) __builtin_amdgcn_readfirstlane(__hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
   int idle = 0;
   while (true) {
     if (wave == 0) {
       // ---- pop (wavefront 0 only): lowest iteration first -----------------------------------------------
-      int t = -1, b = -1;
+      int t = -1, b = -1, idx = 0;
       while (true) {
         int t0 = CFZ_LD(&ctrl[0]);
         const int hint = t0;
         while (t0 < K && CFZ_LD(&head[t0]) >= B) ++t0;
         if (t0 > hint && lane == 0) atomicMax(&ctrl[0], t0);
         if (t0 >= K) break;  // every item of every iteration has been handed out
-        int idx = 0;
         for (int tt = t0; tt < K; ++tt) {
           const int hd = CFZ_LD(&head[tt]), tl = CFZ_LD(&tail[tt]);
           if (tl == 0) break;  // no scenario has reached iteration tt yet, hence none is further either
@@ -55,18 +54,27 @@
       // (invalidates this CU's L1), completed before the barrier that releases the other wavefront's loads.
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) { cmd[0] = t; cmd[1] = b; }
+      // The launch ends with its slowest scenario (a chain of K dependent iterations).  An item of the oldest open iteration
+      // (prio_lag >= 0: t <= ctrl[0] + prio_lag) that also sits among the last prio_tail positions of its iteration's queue
+      // (prio_tail > 0, t >= 1) belongs to a scenario that is behind: items are published in the order in which their scenarios
+      // finished the iteration before, under either exchange rule.  Iteration 0 was queued by the host in index order, which says
+      // nothing, so there the iteration decides alone; B < prio_tail: every position qualifies.  Decided here, by the wavefront that
+      // holds the position, from scalars only.
+      int pr = 0;
+      if (prio_lag >= 0 && t >= 0) pr = (t <= CFZ_LD(&ctrl[0]) + prio_lag && (prio_tail <= 0 || t == 0 || idx >= B - prio_tail)) ? 1 : 0;
+      if (lane == 0) { cmd[0] = t; cmd[1] = b; cmd[2] = pr; }
     }
     __syncthreads();
-    const int t = cmd[0], b = cmd[1];
+    // the item through readfirstlane: the same in every lane, and known to the compiler as such.  s_setprio ignores EXEC; under a
+    // condition read from (volatile) LDS the raise sat in an EXEC-masked region and ran in every wavefront, followed by the lowering.
+    const int t = __builtin_amdgcn_readfirstlane(cmd[0]), b = __builtin_amdgcn_readfirstlane(cmd[1]);
     if (t < 0) break;
+    const int pr = __builtin_amdgcn_readfirstlane(cmd[2]);
     CFZ_MARK(2);
-    // The launch ends with its slowest scenario (a chain of K dependent iterations).  A workgroup serving the oldest open
-    // iteration is on that critical path: its two wavefronts take issue priority over the wavefronts they share their
-    // SIMDs with (VALU issue is arbitrated by priority, then age), the others give way.
-    if (prio_lag >= 0) {
-      if (t <= CFZ_LD(&ctrl[0]) + prio_lag) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-    }
+    CFZ_ITEM_STAMP(0, pr);
+    // Both wavefronts of a prioritised item take issue priority over the wavefronts they share their SIMDs with (VALU issue is
+    // arbitrated by priority, then age), the others give way.  Lowered again below, after the release.
+    if (pr) __builtin_amdgcn_s_setprio(3);
     const int s = b / V, v = b - s * V;
     // kPool: the constants of the scenario's problem, pool[problem_of[s]], in place of the handle's block; the index is the same in
     // every lane of both wavefronts, so the block is still read through scalar loads.  N, n_nbr and the layout L stay the handle's.
@@ -128,11 +136,13 @@
     }
     __syncthreads();
     CFZ_MARK(3);
+    CFZ_ITEM_STAMP(1, 0);
     int oi[2]; double od[3];
     cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     cfz::solve_instance(spi, dvi, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
     __syncthreads();
     CFZ_MARK(4);
+    CFZ_ITEM_STAMP(2, 0);
     // ---- read-back (the solution is still in the workspace) or shift fallback (:484-524), plant (:528-543) ------------
     for (int i = tid; i < 7 * N; i += cfz::kNL) {
       const int c = i / N, k = i - c * N;
@@ -195,6 +205,9 @@
       }
       atomicAdd(&ctrl[1], 1);
     }
+    // the priority ends with the item: neither the pop loop of wavefront 0 nor wavefront 1's wait at the barrier holds it
+    if (pr) __builtin_amdgcn_s_setprio(0);
+    CFZ_ITEM_STAMP(3, 0);
     CFZ_MARK(8);
   }
   CFZ_MARK(9);
