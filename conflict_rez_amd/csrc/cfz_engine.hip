@@ -13,6 +13,8 @@
 //   loop_kernel_pool, loop_kernel_seq_pool, loop_kernel_pool_comm, loop_kernel_seq_pool_comm  the disturbed and the lossy pairs with the
 //                  per-scenario problem constants of cfz_loop_set_problems: an item reads the KArgs block of its scenario's problem
 //   solve_kernel_pool  solve_kernel with the same selection, for the stepwise closed loop while a pool is set
+//                  The per-scenario obstacle maps of cfz_loop_set_maps run through the same pool kernels: the host composes one KArgs
+//                  block per (problem, map) pair in use, whose obs_tab points at that map's table (compose_pool)
 //   loop_prep      stepwise closed loop (cfz_loop_step): parameters and shifted warm start of every vehicle from the
 //                  previous predictions (reference vehicle_follower.py:432-476, 636-637), the measurement under a disturbance
 //   loop_post      stepwise closed loop: read-back or shift fallback, plant integration, clock
@@ -20,7 +22,7 @@
 //   vs_prep        loop_prep for the vehicle-sharded loop (cfz_vsl_step, which ends with loop_post): table, clock and neighbours
 //                  from the caller; the two share the __device__ function prep_stage
 //   audit_kernel   signed distances, first contact and arrivals along a recorded trajectory (cfz_audit.inl), one
-//                  wavefront per scenario
+//                  wavefront per scenario, each against the obstacles of its own map
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
@@ -39,8 +41,10 @@
 #include <cstdlib>
 #include <unistd.h>
 #include <cmath>
+#include <map>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/confrez_hip.h"
@@ -400,14 +404,15 @@ const LoopVariant kLoopVariants[10] = {
     {(const void *)loop_kernel_pool_comm, false, true, true, true},   {(const void *)loop_kernel_seq_pool_comm, true, true, true, true}};
 
 // The row that runs the setting in force.  The comm and the pool kernels exist only with kDist (no full cross product): while no
-// disturbance is set they take the zero-noise block (disturb_args), so every one of the 16 settings has exactly one row.
-int loop_variant(bool seq, bool dz_on, bool cm_on, bool pb_on) {
-  const bool dist = dz_on || cm_on || pb_on;
+// disturbance is set they take the zero-noise block (disturb_args), so every one of the 32 settings has exactly one row.  A map pool
+// (mp_on) runs on the pool rows, as a problem pool does: the two are composed into one set of blocks on the host (compose_pool).
+int loop_variant(bool seq, bool dz_on, bool cm_on, bool pb_on, bool mp_on) {
+  const bool pool = pb_on || mp_on, dist = dz_on || cm_on || pool;
   for (int i = 0; i < 10; ++i) {
     const LoopVariant &v = kLoopVariants[i];
-    if (v.seq == seq && v.dist == dist && v.comm == cm_on && v.pool == pb_on) return i;
+    if (v.seq == seq && v.dist == dist && v.comm == cm_on && v.pool == pool) return i;
   }
-  return -1;  // (not reached: the ten rows cover the 16 settings)
+  return -1;  // (not reached: the ten rows cover the 32 settings)
 }
 
 // delivered[K][S][V][V]: the delivery bits of messages [tau0, tau0 + K) (cfz_loop_comm), receiver before sender, diagonal 1; one thread
@@ -594,9 +599,10 @@ __global__ void loop_goals(int S, int V, int T, const double *ref_table, const i
 // ---- audit of a recorded closed loop (cfz_audit.inl) ------------------------------------------------------------------
 // One wavefront per scenario; its lanes deal out the (step, item) pairs round-robin and keep the running minima in registers,
 // then a butterfly over the wavefront merges them (a minimum under a total order: the same result on every run).  traj[K][S][V][7]
-// from the window's first step, goal[S][V][3]; obs_in[n_obs] the obstacles with their normals and inverse edge lengths, il the
-// body's (both formed on the host: the loop has no sqrt and no division); clear[S][2] as audit_signed_key (the host takes the root),
-// where[S][6], first_contact[S], arrive[S][V].  Plain stores, no atomics.
+// from the window's first step, goal[S][V][3]; obs_in[M][n_obs] the obstacles of M maps with their normals and inverse edge lengths, il
+// the body's (both formed on the host: the loop has no sqrt and no division); map_of[S] the map of every scenario (NULL: map 0), which
+// its wavefront stages in LDS; clear[S][2] as audit_signed_key (the host takes the root), where[S][6] (the obstacle's index within the
+// scenario's map), first_contact[S], arrive[S][V].  Plain stores, no atomics.
 // cs[n][2]: cos and sin of the n = K S V headings of traj[n][7], one thread each (the audit loop itself has no transcendental)
 __global__ void audit_headings(long n, const double *traj, double *cs) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -607,13 +613,14 @@ __global__ void audit_headings(long n, const double *traj, double *cs) {
 }
 
 __global__ __launch_bounds__(64) void audit_kernel(const KArgs *__restrict__ ka, int K, int S, int V, const double *traj,
-                                                   const double *cs, const double *goal, const cfz::AuditPoly *obs_in, double il0, double il1,
-                                                   double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
-                                                   int32_t *first_contact, int32_t *arrive) {
+                                                   const double *cs, const double *goal, const cfz::AuditPoly *obs_in,
+                                                   const int32_t *map_of, double il0, double il1, double pos_tol, double psi_tol,
+                                                   double v_tol, double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive) {
   __shared__ cfz::AuditPoly obs[cfz::kMaxObs];
   const int s = blockIdx.x, lane = threadIdx.x;
   const int no = ka->sp.n_obs;
-  if (lane < no) obs[lane] = obs_in[lane];
+  const cfz::AuditPoly *mine = obs_in + (size_t)(map_of ? map_of[s] : 0) * no;
+  if (lane < no) obs[lane] = mine[lane];
   double g[4];
   for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
   const double il[2] = {il0, il1};
@@ -691,12 +698,24 @@ struct cfz_handle {
     uint64_t cm_seed = 0;
     int cm_max_age = 0, cm_compensate = 0, cm_tau_on = 0, cm_ring_slots = 0;
     bool cm_on = false;
-    // problem pool (cfz_loop_set_problems; pb_on false: none): pb_pool[pb_cap] the KArgs block {ks_p, derive(ks_p), lay} of every problem
-    // (obs_tab the handle's), pb_of[S] the problem of each scenario
+    // problem pool (cfz_loop_set_problems; pb_on false: none) as the user gave it: pb_user[P] the block {ks_p, derive(ks_p), lay} of every
+    // problem (obs_tab the handle's), pb_user_of[S] the problem of each scenario
+    std::vector<KArgs> pb_user;
+    std::vector<int32_t> pb_user_of;
+    bool pb_on = false;
+    // map pool (cfz_loop_set_maps; mp_on false: none): mp_tab[mp_M][n_obs][20] the maps' tables in the layout of cfz_handle::obs_tab,
+    // mp_poly[mp_M][n_obs] their polygons as the audit reads them, mp_of[S] the map of each scenario (device), mp_user_of the same (host)
+    double *mp_tab = nullptr;
+    cfz::AuditPoly *mp_poly = nullptr;
+    int32_t *mp_of = nullptr;
+    std::vector<int32_t> mp_user_of;
+    int mp_M = 0;
+    bool mp_on = false;
+    // what the pool kernels take while either setting is on (compose_pool): pb_pool[pb_cap] one block per (problem, map) pair that some
+    // scenario uses, its obs_tab that map's table; pb_of[S] the block of each scenario
     KArgs *pb_pool = nullptr;
     int32_t *pb_of = nullptr;
     int pb_cap = 0;
-    bool pb_on = false;
     // persistent loop
     double *pred2 = nullptr, *scratch = nullptr;
     int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
@@ -721,7 +740,7 @@ int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, cons
     hipLaunchKernelGGL(kernel, dim3(grid ? grid : B), dim3(cfz::kNL), h->lds_bytes, st, h->kargs, B, x0, ref, nbr, zu, status, iters, stats, du,
                        order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all, h->slots_set ? h->slots : nullptr, tail...);
   };
-  if (pool)  // the stepwise closed loop under cfz_loop_set_problems: instance b solves the problem of scenario b / V
+  if (pool)  // the stepwise closed loop under cfz_loop_set_problems / cfz_loop_set_maps: instance b solves the block of scenario b / V
     launch(solve_kernel_pool, h->lp.pb_pool, h->lp.pb_of, h->ks.n_nbr + 1);
   else
     launch(solve_kernel);
@@ -747,6 +766,27 @@ int spec_shape_ok(const cfz_spec *spec) {
 int options_ok(const cfz_options *opt) {
   if (opt->filter_cap < 1 || opt->filter_cap > 32) return fail("filter_cap must be in 1..32");
   if (opt->restoration < 0 || !(opt->reg_dual_rows >= 0.0) || !(opt->resto_first >= 0.0)) return fail("restoration, reg_dual_rows, resto_first must not be negative");
+  return 0;
+}
+
+// one obstacle's 20 doubles of KSpec::obs_tab: A[4][2], b[4], V[4][2]
+void obs_tab_entry(double *o, const double A[4][2], const double b[4], const double V[4][2]) {
+  for (int i = 0; i < 4; ++i) { o[2 * i] = A[i][0]; o[2 * i + 1] = A[i][1]; o[8 + i] = b[i];
+                                o[12 + 2 * i] = V[i][0]; o[13 + 2 * i] = V[i][1]; }
+}
+
+// the vertices V[n_obs][4][2] of a map A[n_obs][4][2], b[n_obs][4], as cfz_create forms them (quad_vertices); refused, naming the
+// obstacle: an entry that is not finite, an obstacle that is no bounded quadrilateral (cfz_map_check)
+int map_vertices(int n_obs, const double *A, const double *b, double (*V)[4][2]) {
+  for (int j = 0; j < n_obs; ++j) {
+    const double *Aj = A + (size_t)j * 8, *bj = b + (size_t)j * 4;
+    bool finite = true;
+    for (int i = 0; i < 8; ++i) finite = finite && std::isfinite(Aj[i]);
+    for (int i = 0; i < 4; ++i) finite = finite && std::isfinite(bj[i]);
+    if (!finite) return fail(("obstacle " + std::to_string(j) + " has an entry that is not finite").c_str());
+    if (!quad_vertices(reinterpret_cast<const double(*)[2]>(Aj), bj, V[j]))
+      return fail(("obstacle " + std::to_string(j) + " is not a bounded quadrilateral").c_str());
+  }
   return 0;
 }
 
@@ -865,11 +905,7 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
   HIP_OK(hipStreamCreate(&h->stream));
   {
     std::vector<double> tab((size_t)std::max(k.n_obs, 1) * 20, 0.0);
-    for (int j = 0; j < k.n_obs; ++j) {
-      double *o = tab.data() + (size_t)j * 20;
-      for (int i = 0; i < 4; ++i) { o[2 * i] = k.A_obs[j][i][0]; o[2 * i + 1] = k.A_obs[j][i][1]; o[8 + i] = k.b_obs[j][i];
-                                    o[12 + 2 * i] = k.V_obs[j][i][0]; o[13 + 2 * i] = k.V_obs[j][i][1]; }
-    }
+    for (int j = 0; j < k.n_obs; ++j) obs_tab_entry(tab.data() + (size_t)j * 20, k.A_obs[j], k.b_obs[j], k.V_obs[j]);
     HIP_OK(hipMalloc(&h->obs_tab, tab.size() * 8));
     HIP_OK(hipMemcpy(h->obs_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
     h->ks.obs_tab = h->obs_tab;
@@ -1138,13 +1174,23 @@ void comm_free(cfz_handle *h) {
 
 void problems_free(cfz_handle *h) {
   dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
+  h->lp.pb_user.clear(); h->lp.pb_user_of.clear();
   h->lp.pb_on = false; h->lp.pb_cap = 0;
 }
 
-// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance and comm setting, problem pool and the
-// persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
+void maps_free(cfz_handle *h) {
+  dev_free(h->lp.mp_tab); dev_free(h->lp.mp_poly); dev_free(h->lp.mp_of);
+  h->lp.mp_user_of.clear();
+  h->lp.mp_on = false; h->lp.mp_M = 0;
+}
+
+// the pool kernels run (solve_kernel_pool, the pool rows of kLoopVariants, loop_post on the pool) whenever either setting is on
+bool pool_on(const cfz_handle *h) { return h->lp.pb_on || h->lp.mp_on; }
+
+// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance and comm setting, problem pool, map pool
+// and the persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
 void loop_release(cfz_handle *h) {
-  record_free(h); exchange_free(h); disturb_free(h); comm_free(h); problems_free(h);
+  record_free(h); exchange_free(h); disturb_free(h); comm_free(h); problems_free(h); maps_free(h);
   dev_free(h->lp.dz_zero);
   dev_free(h->lp.ref_table); dev_free(h->lp.table_of); dev_free(h->lp.pred); dev_free(h->lp.state); dev_free(h->lp.kidx); dev_free(h->lp.order);
   dev_free(h->lp.pred2); dev_free(h->lp.scratch); dev_free(h->lp.queue); dev_free(h->lp.ctrl); dev_free(h->lp.done); dev_free(h->lp.iter_sum);
@@ -1204,7 +1250,7 @@ void record_slice(const cfz_handle *h, double *&rec, int32_t *&rec_si) {
   rec_si = h->lp.rec ? h->lp.rec_si + (size_t)h->lp.rec_used * 2 * B : nullptr;
 }
 
-// One round of a stepwise iteration (cfz_loop_step): loop_prep, solve_kernel (solve_kernel_pool while a problem pool is set), loop_post for n_inst instances.  Jacobi: all B of them,
+// One round of a stepwise iteration (cfz_loop_step): loop_prep, solve_kernel (solve_kernel_pool while a problem pool or a map pool is set), loop_post for n_inst instances.  Jacobi: all B of them,
 // xperm and xrank NULL; round r of the sequential exchange: the S vehicles of rank r.  dispatch (NULL: index order) lists the instance
 // ids in the order the solve's workgroups take them; the carry slot of instance b is b either way.
 int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const int32_t *xperm, const int32_t *xrank) {
@@ -1217,7 +1263,7 @@ int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const 
   hipLaunchKernelGGL(loop_prep, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, h->lp.T, h->lp.ref_table,
                      h->lp.table_of, h->lp.kidx, h->lp.pred, h->lp.state, h->x0, h->ref, h->nbr, h->zu, r, xperm, xrank, dz, h->lp.steps_done, cm);
   HIP_OK(hipGetLastError());
-  const bool pool = h->lp.pb_on;  // the scenario's own problem: solve_kernel_pool, and its input box in loop_post
+  const bool pool = pool_on(h);  // the scenario's own problem on its own map: solve_kernel_pool, and its input box in loop_post
   if (launch_solve(h, S * V, h->x0, h->ref, h->nbr, h->zu, h->status, h->iters, h->stats, false, h->stream, dispatch, 1, n_inst, pool)) return -1;
   hipLaunchKernelGGL(loop_post, dim3((unsigned)((n_inst + 63) / 64)), dim3(64), 0, h->stream, S, V, N, h->kargs, h->status, h->iters, h->zu,
                      h->lp.pred, h->lp.state, h->lp.kidx, rec, rec_si, r, xperm, dz, h->lp.steps_done, nullptr,
@@ -1226,29 +1272,40 @@ int loop_round(cfz_handle *h, int r, int n_inst, const int32_t *dispatch, const 
   return 0;
 }
 
-int audit_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const double *d_goal, double pos_tol, double psi_tol,
-                 double v_tol, double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive) {
-  // the obstacles with their face normals and inverse edge lengths, and the body's edge lengths, formed here (audit_kernel)
-  const int no = h->ks.n_obs;
-  std::vector<cfz::AuditPoly> ob((size_t)std::max(no, 1));
+// the obstacles of one map (vertices V[n_obs][4][2], counter-clockwise as quad_vertices leaves them) with their face normals and
+// inverse edge lengths, as audit_kernel reads them
+void audit_polys(int no, const double (*V)[4][2], cfz::AuditPoly *ob) {
   for (int j = 0; j < no; ++j) {
-    memcpy(ob[j].v, h->ks.V_obs[j], sizeof ob[j].v);
+    memcpy(ob[j].v, V[j], sizeof ob[j].v);
     cfz::audit_poly_prepare(ob[j]);
   }
-  const double *g = h->ks.g;
+}
+
+// d_obs[M][n_obs] the prepared polygons of the maps and d_map_of[S] (device; both NULL: every scenario against the handle's map, whose
+// polygons are formed here); d_map_of NULL with d_obs set: every scenario against map 0 of d_obs
+int audit_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const double *d_goal, const cfz::AuditPoly *d_obs,
+                 const int32_t *d_map_of, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
+                 int32_t *first_contact, int32_t *arrive) {
+  const int no = h->ks.n_obs;
+  std::vector<cfz::AuditPoly> ob((size_t)std::max(no, 1));
+  const double *g = h->ks.g;  // the body's edge lengths are formed here as well
   double *dc = nullptr, *dcs = nullptr;
   int32_t *di = nullptr;
-  cfz::AuditPoly *dob = nullptr;
   const long n = (long)K * S * V;
   ARENA_ALLOC(h->arena, dc, (size_t)S * 2 * 8); ARENA_ALLOC(h->arena, di, (size_t)S * (7 + V) * 4);
   ARENA_ALLOC(h->arena, dcs, (size_t)n * 2 * 8);
-  ARENA_ALLOC(h->arena, dob, ob.size() * sizeof(cfz::AuditPoly));
-  HIP_OK(hipMemcpyAsync(dob, ob.data(), ob.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice, h->stream));
+  if (!d_obs) {
+    cfz::AuditPoly *dob = nullptr;
+    audit_polys(no, h->ks.V_obs, ob.data());
+    ARENA_ALLOC(h->arena, dob, ob.size() * sizeof(cfz::AuditPoly));
+    HIP_OK(hipMemcpyAsync(dob, ob.data(), ob.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice, h->stream));
+    d_obs = dob;
+  }
   int32_t *dw = di, *df = di + (size_t)S * 6, *da = di + (size_t)S * 7;
   hipLaunchKernelGGL(audit_headings, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, d_traj, dcs);
   HIP_OK(hipGetLastError());
-  hipLaunchKernelGGL(audit_kernel, dim3(S), dim3(64), 0, h->stream, h->kargs, K, S, V, d_traj, dcs, d_goal, dob, 1.0 / (g[0] + g[2]),
-                     1.0 / (g[1] + g[3]), pos_tol, psi_tol, v_tol, dc, dw, df, da);
+  hipLaunchKernelGGL(audit_kernel, dim3(S), dim3(64), 0, h->stream, h->kargs, K, S, V, d_traj, dcs, d_goal, d_obs, d_map_of,
+                     1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), pos_tol, psi_tol, v_tol, dc, dw, df, da);
   HIP_OK(hipGetLastError());
   if (clear) HIP_OK(hipMemcpyAsync(clear, dc, (size_t)S * 2 * 8, hipMemcpyDeviceToHost, h->stream));
   if (where) HIP_OK(hipMemcpyAsync(where, dw, (size_t)S * 6 * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1258,6 +1315,48 @@ int audit_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const
   if (clear)
     for (int i = 0; i < 2 * S; ++i) clear[i] = cfz::audit_key_distance(clear[i]);
   return 0;
+}
+
+// What the pool kernels take, composed from the two per-scenario settings: one KArgs block per (problem, map) pair that some scenario
+// uses, in the order of first use, and the block of every scenario.  probs[P], problem_of[S] as cfz_loop_set_problems fills them (probs
+// NULL: the handle's problem for every scenario); map_tab[M][n_obs][20] (device), map_of[S] as cfz_loop_set_maps does (map_tab NULL: the
+// handle's map).  A block is its problem's {sp, dv, L} with sp.obs_tab pointing at its map's table; dv and L do not depend on the
+// obstacles, and the obstacle arrays inside sp stay the handle's (no loop kernel reads them).  The blocks are device allocations of
+// their own, handed back in pool, of, cap (both settings off: none): the caller swaps them in (pool_swap) once its call can no longer
+// fail, so that a refused or failed call leaves the setting in force as it was.
+int compose_pool(const cfz_handle *h, const std::vector<KArgs> *probs, const int32_t *problem_of, const double *map_tab, const int32_t *map_of,
+                 KArgs *&pool, int32_t *&of, int &cap) {
+  pool = nullptr; of = nullptr; cap = 0;
+  if (!probs && !map_tab) return 0;
+  const int S = h->lp.S;
+  const size_t tab = (size_t)std::max(h->ks.n_obs, 1) * 20;
+  const KArgs own = {h->ks, cfz::derive(h->ks), h->lay};  // (what cfz_create wrote to h->kargs)
+  std::vector<KArgs> blocks;
+  std::vector<int32_t> block_of((size_t)S);
+  std::map<std::pair<int, int>, int> seen;
+  for (int s = 0; s < S; ++s) {
+    const std::pair<int, int> key(probs ? problem_of[s] : 0, map_tab ? map_of[s] : 0);
+    auto it = seen.find(key);
+    if (it == seen.end()) {
+      KArgs b = probs ? (*probs)[key.first] : own;
+      b.sp.obs_tab = map_tab ? map_tab + (size_t)key.second * tab : h->obs_tab;
+      it = seen.emplace(key, (int)blocks.size()).first;
+      blocks.push_back(b);
+    }
+    block_of[s] = it->second;
+  }
+  hipError_t e = hipMalloc(&pool, blocks.size() * sizeof(KArgs));
+  if (e == hipSuccess) e = hipMalloc(&of, (size_t)S * 4);
+  if (e == hipSuccess) e = hipMemcpy(pool, blocks.data(), blocks.size() * sizeof(KArgs), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(of, block_of.data(), (size_t)S * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { dev_free(pool); dev_free(of); return fail("device copy of the composed pool", e); }
+  cap = (int)blocks.size();
+  return 0;
+}
+
+void pool_swap(cfz_handle *h, KArgs *pool, int32_t *of, int cap) {
+  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
+  h->lp.pb_pool = pool; h->lp.pb_of = of; h->lp.pb_cap = cap;
 }
 }  // namespace
 
@@ -1346,22 +1445,52 @@ int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol,
   ARENA_ALLOC(h->arena, dg, B * 3 * 8);
   hipLaunchKernelGGL(loop_goals, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, S, V, h->lp.T, h->lp.ref_table, h->lp.table_of, dg);
   HIP_OK(hipGetLastError());
-  return audit_launch(h, K, S, V, h->lp.rec + (size_t)t0 * B * 7, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
+  // every scenario against its own map under the mapping in force now (cfz_loop_set_maps)
+  return audit_launch(h, K, S, V, h->lp.rec + (size_t)t0 * B * 7, dg, h->lp.mp_on ? h->lp.mp_poly : nullptr, h->lp.mp_on ? h->lp.mp_of : nullptr,
+                      pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
 }
 
 int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, double pos_tol, double psi_tol, double v_tol,
               double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive) {
+  return cfz_audit_maps(h, K, S, V, traj, goal, 0, nullptr, nullptr, nullptr, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
+}
+
+int cfz_audit_maps(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, int M, const double *A_obs,
+                   const double *b_obs, const int32_t *map_of, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
+                   int32_t *first_contact, int32_t *arrive) {
   if (!h) return fail("null handle");
   if (K < 1 || S < 1 || V < 1 || V > CFZ_MAX_NBR + 1) return fail("K, S must be positive and V in 1..CFZ_MAX_NBR+1");
   if (!traj || !goal) return fail("null trajectory or goal");
   if ((size_t)K * S * V * 7 > ((size_t)1 << 31)) return fail("trajectory too large");
+  if (M < 0) return fail("M must not be negative");
+  const bool maps = M > 0 && A_obs;  // else: the handle's map for every scenario
+  const int no = h->ks.n_obs;
+  std::vector<cfz::AuditPoly> poly;
+  if (maps) {
+    if (!b_obs || !map_of) return fail("null b_obs or map_of");
+    for (int s = 0; s < S; ++s)
+      if (map_of[s] < 0 || map_of[s] >= M) return fail("map_of[s] outside [0, M)");
+    poly.resize(std::max((size_t)M * no, (size_t)1));
+    for (int m = 0; m < M; ++m) {
+      double Vx[CFZ_MAX_OBS][4][2];
+      if (map_vertices(no, A_obs + (size_t)m * no * 8, b_obs + (size_t)m * no * 4, Vx)) { cfz_g_err = "map " + std::to_string(m) + ": " + cfz_g_err; return -1; }
+      audit_polys(no, Vx, poly.data() + (size_t)m * no);
+    }
+  }
   HIP_OK(hipSetDevice(h->device));
   if (arena_reset(h->arena)) return -1;
   double *dt_ = nullptr, *dg = nullptr;
+  cfz::AuditPoly *dpoly = nullptr;
+  int32_t *dof = nullptr;
   ARENA_ALLOC(h->arena, dt_, (size_t)K * S * V * 7 * 8); ARENA_ALLOC(h->arena, dg, (size_t)S * V * 3 * 8);
   HIP_OK(hipMemcpyAsync(dt_, traj, (size_t)K * S * V * 7 * 8, hipMemcpyHostToDevice, h->stream));
   HIP_OK(hipMemcpyAsync(dg, goal, (size_t)S * V * 3 * 8, hipMemcpyHostToDevice, h->stream));
-  return audit_launch(h, K, S, V, dt_, dg, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);
+  if (maps) {
+    ARENA_ALLOC(h->arena, dpoly, poly.size() * sizeof(cfz::AuditPoly)); ARENA_ALLOC(h->arena, dof, (size_t)S * 4);
+    HIP_OK(hipMemcpyAsync(dpoly, poly.data(), poly.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice, h->stream));
+    HIP_OK(hipMemcpyAsync(dof, map_of, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
+  }
+  return audit_launch(h, K, S, V, dt_, dg, dpoly, dof, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);  // (ends synchronised: `poly` outlives its copy)
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
@@ -1478,30 +1607,92 @@ int cfz_problem_check(const cfz_spec *base, const cfz_options *base_opt, const c
 int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz_options *opts, const int32_t *problem_of) {
   if (loop_ready(h, true)) return -1;
   if (P < 0) return fail("P must not be negative");
-  if (P == 0 || !specs) { h->lp.pb_on = false; return 0; }  // off: the kernels without it
-  if (!problem_of) return fail("null problem_of");
+  const bool off = P == 0 || !specs;  // off: the kernels without it (the map pool's, if one is set)
   const int S = h->lp.S;
-  for (int s = 0; s < S; ++s)
-    if (problem_of[s] < 0 || problem_of[s] >= P) return fail("problem_of[s] outside [0, P)");
-  std::vector<KArgs> pool((size_t)P);
-  for (int p = 0; p < P; ++p) {
-    const cfz_options *o = opts ? &opts[p] : &h->opt0;
-    if (cfz_problem_check(&h->spec0, &h->opt0, &specs[p], o)) { cfz_g_err = "problem " + std::to_string(p) + ": " + cfz_g_err; return -1; }
-    if (fill_kspec(pool[p].sp, &specs[p], o)) return -1;
-    pool[p].sp.obs_tab = h->obs_tab;
-    pool[p].dv = cfz::derive(pool[p].sp); pool[p].L = h->lay;
+  std::vector<KArgs> pool;
+  std::vector<int32_t> pool_of;
+  if (!off) {
+    if (!problem_of) return fail("null problem_of");
+    for (int s = 0; s < S; ++s)
+      if (problem_of[s] < 0 || problem_of[s] >= P) return fail("problem_of[s] outside [0, P)");
+    pool.resize((size_t)P);
+    pool_of.assign(problem_of, problem_of + S);
+    for (int p = 0; p < P; ++p) {
+      const cfz_options *o = opts ? &opts[p] : &h->opt0;
+      if (cfz_problem_check(&h->spec0, &h->opt0, &specs[p], o)) { cfz_g_err = "problem " + std::to_string(p) + ": " + cfz_g_err; return -1; }
+      if (fill_kspec(pool[p].sp, &specs[p], o)) return -1;
+      pool[p].sp.obs_tab = h->obs_tab;
+      pool[p].dv = cfz::derive(pool[p].sp); pool[p].L = h->lay;
+    }
   }
-  // the new setting is written into blocks of its own and swapped in once it is complete: a failure leaves the one in force as it was
+  // the new setting, composed with the map pool in force, is written into blocks of its own and swapped in once it is complete: a
+  // failure leaves the one in force as it was
   KArgs *d = nullptr;
   int32_t *of = nullptr;
-  hipError_t e = hipMalloc(&d, (size_t)P * sizeof(KArgs));
-  if (e == hipSuccess) e = hipMalloc(&of, (size_t)S * 4);
-  if (e == hipSuccess) e = hipMemcpy(d, pool.data(), (size_t)P * sizeof(KArgs), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(of, problem_of, (size_t)S * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { dev_free(d); dev_free(of); return fail("cfz_loop_set_problems: device copy of the pool", e); }
-  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
-  h->lp.pb_pool = d; h->lp.pb_of = of; h->lp.pb_cap = P;
-  h->lp.pb_on = true;
+  int cap = 0;
+  if (compose_pool(h, off ? nullptr : &pool, pool_of.data(), h->lp.mp_on ? h->lp.mp_tab : nullptr, h->lp.mp_user_of.data(), d, of, cap)) return -1;
+  pool_swap(h, d, of, cap);
+  h->lp.pb_user.swap(pool); h->lp.pb_user_of.swap(pool_of);
+  h->lp.pb_on = !off;
+  return 0;
+}
+
+int cfz_map_check(const cfz_spec *base, const double *A_obs, const double *b_obs) {
+  if (!base) return fail("null argument");
+  if (spec_shape_ok(base)) return -1;
+  if (base->n_obs > 0 && (!A_obs || !b_obs)) return fail("null A_obs or b_obs");
+  double V[CFZ_MAX_OBS][4][2];
+  return map_vertices(base->n_obs, A_obs, b_obs, V);
+}
+
+int cfz_loop_set_maps(cfz_handle *h, int M, const double *A_obs, const double *b_obs, const int32_t *map_of) {
+  if (loop_ready(h, true)) return -1;
+  if (M < 0) return fail("M must not be negative");
+  const int S = h->lp.S, no = h->ks.n_obs;
+  const std::vector<KArgs> *probs = h->lp.pb_on ? &h->lp.pb_user : nullptr;
+  KArgs *d = nullptr;
+  int32_t *of = nullptr;
+  int cap = 0;
+  if (M == 0 || !A_obs) {  // off: the kernels without it (the problem pool's, if one is set)
+    if (compose_pool(h, probs, h->lp.pb_user_of.data(), nullptr, nullptr, d, of, cap)) return -1;
+    pool_swap(h, d, of, cap);
+    maps_free(h);
+    return 0;
+  }
+  if (!b_obs || !map_of) return fail("null b_obs or map_of");
+  for (int s = 0; s < S; ++s)
+    if (map_of[s] < 0 || map_of[s] >= M) return fail("map_of[s] outside [0, M)");
+  const size_t stride = (size_t)std::max(no, 1) * 20;
+  std::vector<double> tab((size_t)M * stride, 0.0);
+  std::vector<cfz::AuditPoly> poly(std::max((size_t)M * no, (size_t)1));
+  for (int m = 0; m < M; ++m) {
+    const double *A = A_obs + (size_t)m * no * 8, *b = b_obs + (size_t)m * no * 4;
+    double V[CFZ_MAX_OBS][4][2];
+    if (map_vertices(no, A, b, V)) { cfz_g_err = "map " + std::to_string(m) + ": " + cfz_g_err; return -1; }
+    for (int j = 0; j < no; ++j)
+      obs_tab_entry(tab.data() + (size_t)m * stride + (size_t)j * 20, reinterpret_cast<const double(*)[2]>(A + (size_t)j * 8), b + (size_t)j * 4, V[j]);
+    audit_polys(no, V, poly.data() + (size_t)m * no);
+  }
+  // as in cfz_loop_set_problems: blocks of its own, swapped in once the new setting is complete
+  double *dtab = nullptr;
+  cfz::AuditPoly *dpoly = nullptr;
+  int32_t *dof = nullptr;
+  hipError_t e = hipMalloc(&dtab, tab.size() * 8);
+  if (e == hipSuccess) e = hipMalloc(&dpoly, poly.size() * sizeof(cfz::AuditPoly));
+  if (e == hipSuccess) e = hipMalloc(&dof, (size_t)S * 4);
+  if (e == hipSuccess) e = hipMemcpy(dtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dpoly, poly.data(), poly.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dof, map_of, (size_t)S * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) fail("cfz_loop_set_maps: device copy of the maps", e);
+  if (e != hipSuccess || compose_pool(h, probs, h->lp.pb_user_of.data(), dtab, map_of, d, of, cap)) {
+    dev_free(dtab); dev_free(dpoly); dev_free(dof);
+    return -1;
+  }
+  pool_swap(h, d, of, cap);
+  maps_free(h);
+  h->lp.mp_tab = dtab; h->lp.mp_poly = dpoly; h->lp.mp_of = dof; h->lp.mp_M = M;
+  h->lp.mp_user_of.assign(map_of, map_of + S);
+  h->lp.mp_on = true;
   return 0;
 }
 
@@ -1566,7 +1757,7 @@ int cfz_loop_run(cfz_handle *h, int K) {
   HIP_OK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
   int per_cu = 0;
   const bool seq = h->lp.xperm != nullptr, comm = h->lp.cm_on;
-  const int variant = loop_variant(seq, h->lp.dz_on, comm, h->lp.pb_on);
+  const int variant = loop_variant(seq, h->lp.dz_on, comm, h->lp.pb_on, h->lp.mp_on);
   if (variant < 0) return fail("no persistent kernel for this setting");
   const LoopVariant &var = kLoopVariants[variant];
   HIP_OK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, var.fn, cfz::kNL, h->lds_bytes));

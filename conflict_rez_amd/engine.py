@@ -180,6 +180,10 @@ def load_library(path=None):
     if hasattr(lib, "cfz_loop_set_problems"):
         lib.cfz_problem_check.argtypes = [C.POINTER(_CSpec), C.POINTER(_COptions), C.POINTER(_CSpec), C.POINTER(_COptions)]
         lib.cfz_loop_set_problems.argtypes = [vp, C.c_int, vp, vp, vp]
+    if hasattr(lib, "cfz_loop_set_maps"):
+        lib.cfz_map_check.argtypes = [C.POINTER(_CSpec), vp, vp]
+        lib.cfz_loop_set_maps.argtypes = [vp, C.c_int, vp, vp, vp]
+        lib.cfz_audit_maps.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.cfz_loop_record.argtypes = [vp, C.c_int]
     lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -193,7 +197,7 @@ EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
-    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems"
+    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -248,6 +252,40 @@ def pack_problems(problems, options=None):
         specs[p] = spec.to_c()
         opts[p] = default_options(**{**(options or {}), **over})
     return len(problems), specs, opts
+
+
+def pack_maps(spec, maps):
+    """The arrays `cfz_loop_set_maps` takes: maps is a sequence whose entries are each a list of obstacle objects (`.A` [4,2], `.b` [4], as
+    `ProblemSpec.from_objects` takes them), a pair of arrays (A [n_obs,4,2], b [n_obs,4]) or a ProblemSpec (its A_obs, b_obs) ->
+    (A [M,n_obs,4,2], b [M,n_obs,4]), n_obs that of `spec`.  An entry with another obstacle count is refused by name."""
+    no = spec.n_obs
+    A, b = np.zeros((len(maps), no, 4, 2)), np.zeros((len(maps), no, 4))
+    for m, item in enumerate(maps):
+        if isinstance(item, ProblemSpec):
+            Am, bm = item.A_obs, item.b_obs
+        elif isinstance(item, (tuple, list)) and len(item) == 2 and not hasattr(item[0], "A"):
+            Am, bm = item
+        elif isinstance(item, (tuple, list)) and all(hasattr(o, "A") and hasattr(o, "b") for o in item):
+            Am, bm = [o.A for o in item], [o.b for o in item]
+        else:
+            raise TypeError(f"maps[{m}] must be a list of obstacles (.A, .b), a pair of arrays (A, b) or a ProblemSpec")
+        Am = np.asarray(Am, dtype=np.float64).reshape(-1, 4, 2) if np.size(Am) else np.zeros((0, 4, 2))
+        bm = np.asarray(bm, dtype=np.float64) if np.size(bm) else np.zeros((0, 4))
+        if len(Am) != no or bm.shape != (len(Am), 4):
+            raise ValueError(f"maps[{m}] has {len(Am)} obstacles (b of shape {bm.shape}), the engine's spec has {no}")
+        A[m], b[m] = Am, bm
+    return A, b
+
+
+def map_check(spec, A, b):
+    """`cfz_map_check`: may the obstacles A [n_obs,4,2], b [n_obs,4] stand in a map pool (`Engine.loop_set_maps`) of an engine created
+    with `spec`?  Host arithmetic, needs no GPU.  Raises ValueError with the library's text, which names the obstacle that has an entry
+    that is not finite or is no bounded quadrilateral."""
+    lib = load_library()
+    A, b = _f64(A, (spec.n_obs, 4, 2)), _f64(b, (spec.n_obs, 4))
+    cs = spec.to_c()
+    if lib.cfz_map_check(C.byref(cs), _ptr(A), _ptr(b)) != 0:
+        raise ValueError("cfz_map_check: " + lib.cfz_last_error().decode())
 
 
 def _ptr(a):
@@ -727,6 +765,30 @@ class Engine:
         po = np.ascontiguousarray(po, dtype=np.int32)
         self._ck(self.lib.cfz_loop_set_problems(self._h, P, specs, opts, _ptr(po)), "cfz_loop_set_problems")
 
+    def _maps(self, maps, map_of, S):
+        """(M, A, b, map_of) as the library takes them; maps None or []: (0, None, None, None)."""
+        if maps is None or len(maps) == 0:
+            return 0, None, None, None
+        A, b = pack_maps(self.spec, maps)
+        if map_of is None:
+            raise ValueError("map_of is required with a pool of maps")
+        mo = np.asarray(map_of)
+        if mo.dtype.kind not in "iu" or mo.shape != (S,):
+            raise ValueError(f"map_of must hold {S} integers, got shape {mo.shape}, dtype {mo.dtype}")
+        return len(A), A, b, np.ascontiguousarray(mo, dtype=np.int32)
+
+    def loop_set_maps(self, maps, map_of=None):
+        """`cfz_loop_set_maps`: per-scenario obstacle maps on the later steps and runs of the closed loop (include/confrez_hip.h).  maps: a
+        sequence of maps as `pack_maps` takes them (lists of obstacles, (A, b) pairs or ProblemSpecs), each with this engine's obstacle
+        count; map_of [S]: the map of each scenario.  Every solve of scenario s then stands on that map, and `loop_audit` measures the
+        scenario against it.  Composes with `loop_set_problems` in either order.  None or []: off again, what `loop_init` restores."""
+        if not self._S and maps is not None and len(maps):  # (before loop_init the library refuses the call)
+            A, b = pack_maps(self.spec, maps)
+            self._ck(self.lib.cfz_loop_set_maps(self._h, len(A), _ptr(A), _ptr(b), None), "cfz_loop_set_maps")
+            return
+        M, A, b, mo = self._maps(maps, map_of, self._S)
+        self._ck(self.lib.cfz_loop_set_maps(self._h, M, _ptr(A), _ptr(b), _ptr(mo)), "cfz_loop_set_maps")
+
     def loop_step(self):
         self._ck(self.lib.cfz_loop_step(self._h), "cfz_loop_step")
         if self._rec_cap:
@@ -769,9 +831,10 @@ class Engine:
                                          _ptr(o["where"]), _ptr(o["first_contact"]), _ptr(o["arrive"])), "cfz_loop_audit")
         return o
 
-    def audit(self, traj, goal, pos_tol=ARRIVE_TOL["pos_tol"], psi_tol=ARRIVE_TOL["psi_tol"], v_tol=ARRIVE_TOL["v_tol"]):
-        """`cfz_audit` of a host trajectory traj [K,S,V,7] (x, y, psi, v, ...) with goals [S,V,3], against this engine's body and
-        obstacles -> the dict of `loop_audit`."""
+    def audit(self, traj, goal, maps=None, map_of=None, pos_tol=ARRIVE_TOL["pos_tol"], psi_tol=ARRIVE_TOL["psi_tol"], v_tol=ARRIVE_TOL["v_tol"]):
+        """`cfz_audit_maps` of a host trajectory traj [K,S,V,7] (x, y, psi, v, ...) with goals [S,V,3], against this engine's body and
+        obstacles, or, with maps (as `loop_set_maps` takes them) and map_of [S], scenario s against the obstacles of map map_of[s]
+        -> the dict of `loop_audit`."""
         traj = np.ascontiguousarray(traj, dtype=np.float64)
         if traj.ndim != 4 or traj.shape[3] < 4:
             raise ValueError(f"expected traj of shape [K, S, V, 7], got {traj.shape}")
@@ -780,8 +843,9 @@ class Engine:
             t7 = np.zeros((K, S, V, 7)); t7[..., : traj.shape[3]] = traj; traj = t7
         goal = _f64(goal, (S, V, 3))
         o = self._audit_out(S, V)
-        self._ck(self.lib.cfz_audit(self._h, K, S, V, _ptr(traj), _ptr(goal), float(pos_tol), float(psi_tol), float(v_tol),
-                                    _ptr(o["clear"]), _ptr(o["where"]), _ptr(o["first_contact"]), _ptr(o["arrive"])), "cfz_audit")
+        M, A, b, mo = self._maps(maps, map_of, S)
+        self._ck(self.lib.cfz_audit_maps(self._h, K, S, V, _ptr(traj), _ptr(goal), M, _ptr(A), _ptr(b), _ptr(mo), float(pos_tol), float(psi_tol),
+                                         float(v_tol), _ptr(o["clear"]), _ptr(o["where"]), _ptr(o["first_contact"]), _ptr(o["arrive"])), "cfz_audit_maps")
         return o
 
     def loop_last_converged(self):

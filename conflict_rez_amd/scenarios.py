@@ -37,6 +37,27 @@ def parking_lot_spec(n_nbr=3, N=30, dt=0.1, n_obs=6, dmin=0.05):
     return ProblemSpec.from_objects(obs, VehicleBody(), VehicleConfig(), GeofenceRegion(), n_nbr=n_nbr, N=N, dt=dt, dmin=dmin)
 
 
+def grow_obstacles(spec: ProblemSpec, margin):
+    """The obstacles of `spec` with every face moved outwards by `margin` metres (inwards if negative): (A, b + margin * |A rows|).
+    The reference map's rows are unit normals, so its b moves by the margin itself."""
+    A, b = np.array(spec.A_obs, float), np.array(spec.b_obs, float)
+    return A, b + float(margin) * np.linalg.norm(A, axis=-1)
+
+
+def shift_obstacles(spec: ProblemSpec, dx, dy):
+    """The obstacles of `spec` moved by (dx, dy): {p + d : A p <= b} = {q : A q <= b + A d} -> (A, b + A (dx, dy))."""
+    A, b = np.array(spec.A_obs, float), np.array(spec.b_obs, float)
+    return A, b + A @ np.array([float(dx), float(dy)])
+
+
+def map_spec(spec: ProblemSpec, A, b):
+    """The `ProblemSpec` of a plain engine that stands on the map (A, b) and is otherwise `spec`: what a scenario of
+    `Engine.loop_set_maps` on that map solves."""
+    import dataclasses
+
+    return dataclasses.replace(spec, A_obs=np.array(A, float), b_obs=np.array(b, float))
+
+
 def load_reference_table(path=None, kind="state_ws"):
     """[V, T, 7] planned trajectories (x,y,psi,v,delta,a,w) sampled every dt; held at the goal.  kind: "state_ws" or "planned"
     (module docstring); `path` overrides."""

@@ -19,11 +19,16 @@
    --dmin 0.05,0.1,0.2: every (strategy, start) (and noise level, and drop rate) runs once per clearance in the same launch, each replica
    solving the NLP with that dmin (`Engine.loop_set_problems`: a pool of one problem per value); the replicas of a start share its
    stream ids.  Contact-free starts and the smallest clearances are printed per value.
+   --obstacle-margins 0,0.1,0.2: every (strategy, start) (and noise level, drop rate and clearance) runs once per margin in the same
+   launch, each replica on a map whose obstacles are grown by that margin on every face (`Engine.loop_set_maps`: a pool of one map per
+   value, `scenarios.grow_obstacles`); the replicas of a start share its stream ids.  The plans stay those of the reference map: the
+   question is how much room those plans leave.  The audit measures every replica against its own map; contact-free starts and the
+   smallest clearances are printed per margin.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
                                               [--noise-levels L0,L1,...] [--noise-seed SEED]
                                               [--drop-rates P0,P1,...] [--max-age A] [--no-compensate] [--comm-seed SEED]
-                                              [--dmin D0,D1,...]
+                                              [--dmin D0,D1,...] [--obstacle-margins M0,M1,...]
 """
 import argparse
 import dataclasses
@@ -39,12 +44,14 @@ import numpy as np  # noqa: E402
 NOISE_SIGMA = dict(meas=(0.02, 0.02, 0.005, 0.02, 0.0), act=(0.05, 0.02), proc=(0.005, 0.005, 0.002, 0.01, 0.0))
 
 
-def replicate(k0, noise, tof, levels=None, rates=None, dmins=None):
-    """The batch of one launch: every scenario of (k0 [S0], noise [S0,V,5], tof [S0]) once per noise level, drop rate and clearance.
-    Blocks nest in that order: block l of the first S0 * L scenarios is every start at level l; block r of the first S0 * L * R is all of
-    those at rate r; block d is all of those under problem d.  Every replica of start i keeps stream id i, for the noise and for the
-    delivery alike, so that the values of each axis are compared on common random numbers.
-    -> dict(k0, noise, tof, level, stream, drop, problem_of), each [S] (level, drop, problem_of None where that axis is not given)."""
+def replicate(k0, noise, tof, levels=None, rates=None, dmins=None, margins=None):
+    """The batch of one launch: every scenario of (k0 [S0], noise [S0,V,5], tof [S0]) once per noise level, drop rate, clearance and
+    obstacle margin.  Blocks nest in that order: block l of the first S0 * L scenarios is every start at level l; block r of the first
+    S0 * L * R is all of those at rate r; block d is all of those under problem d; block m is all of those on map m.  Every replica of
+    start i keeps stream id i, for the noise and for the delivery alike, so that the values of each axis are compared on common random
+    numbers.
+    -> dict(k0, noise, tof, level, stream, drop, problem_of), each [S] (level, drop, problem_of None where that axis is not given), and,
+    with margins, map_of [S]."""
     S0 = len(k0)
     out = dict(k0=np.asarray(k0), noise=np.asarray(noise), tof=np.asarray(tof), level=None, stream=np.arange(S0, dtype=np.uint32), drop=None,
                problem_of=None)
@@ -55,7 +62,8 @@ def replicate(k0, noise, tof, levels=None, rates=None, dmins=None):
                 out[k] = np.tile(out[k], n)
         out["noise"] = np.tile(out["noise"], (n, 1, 1))
 
-    for name, values, dtype in (("level", levels, float), ("drop", rates, float), ("problem_of", None if not dmins else range(len(dmins)), np.int32)):
+    for name, values, dtype in (("level", levels, float), ("drop", rates, float), ("problem_of", None if not dmins else range(len(dmins)), np.int32),
+                                ("map_of", None if not margins else range(len(margins)), np.int32)):
         if values:
             S = len(out["k0"])
             tile(len(values))
@@ -81,6 +89,9 @@ def main():
     ap.add_argument("--comm-seed", type=int, default=2024, help="seed of the delivery streams")
     ap.add_argument("--dmin", type=lambda t: [float(x) for x in t.split(",")], default=None,
                     help="comma-separated clearances of the NLP, e.g. 0.05,0.1,0.2: one replica of every start per value, in one launch")
+    ap.add_argument("--obstacle-margins", type=lambda t: [float(x) for x in t.split(",")], default=None,
+                    help="comma-separated margins [m] by which every obstacle face is moved outwards, e.g. 0,0.1,0.2: one replica of every start per "
+                         "value, in one launch, on the plans of the reference map")
     a = ap.parse_args()
 
     import torch
@@ -110,9 +121,10 @@ def main():
         k0, nz = scenarios.sample_scenarios(M, plan["tables"][p], seed=a.seed + int(p), spec=spec)
         k0s.append(k0); noises.append(nz); tof.append(np.full(M, p, np.int32))
     k0, noise, tof = np.concatenate(k0s), np.concatenate(noises), np.concatenate(tof)
-    levels, rates, dmins = a.noise_levels, a.drop_rates, a.dmin
-    rep = replicate(k0, noise, tof, levels, rates, dmins)
+    levels, rates, dmins, margins = a.noise_levels, a.drop_rates, a.dmin, a.obstacle_margins
+    rep = replicate(k0, noise, tof, levels, rates, dmins, margins)
     k0, noise, tof, lvl, streams, drop, pof = (rep[k] for k in ("k0", "noise", "tof", "level", "stream", "drop", "problem_of"))
+    mof = rep.get("map_of")
     comm_streams = streams
     if levels:
         print(f"noise levels {levels} x sigma: meas {NOISE_SIGMA['meas']}, act {NOISE_SIGMA['act']}, proc {NOISE_SIGMA['proc']}; "
@@ -122,6 +134,8 @@ def main():
               f"one stream per start shared by its replicas")
     if dmins:
         print(f"clearances dmin {dmins}: one problem per value in the pool, every replica of a start on its streams")
+    if margins:
+        print(f"obstacle margins {margins} m: one map per value in the pool, every replica of a start on its streams and on the reference map's plans")
     S = len(k0)
     eng = engine.Engine(spec, max_batch=S * V, device=a.device)
     eng.loop_init(plan["tables"], k0, noise, table_of=tof)
@@ -133,6 +147,8 @@ def main():
         eng.loop_set_comm(a.comm_seed, drop, max_age=a.max_age, compensate=not a.no_compensate, stream=comm_streams)
     if dmins:
         eng.loop_set_problems([dataclasses.replace(spec, dmin=d) for d in dmins], pof)
+    if margins:
+        eng.loop_set_maps([scenarios.grow_obstacles(spec, m) for m in margins], mof)
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -158,7 +174,7 @@ def main():
         done = arr.min(1) >= 0  # every vehicle of the scenario arrived
         last = arr.max(1)[done]
         n_contact = int((aud["first_contact"][sel] >= 0).sum())
-        n_sel = int(sel.sum())  # M starts x noise levels x drop rates x clearances
+        n_sel = int(sel.sum())  # M starts x noise levels x drop rates x clearances x margins
         print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{n_sel:<2d} "
               f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
               + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or []))
@@ -174,7 +190,12 @@ def main():
         free = int((aud["first_contact"][sel] < 0).sum())
         print(f"dmin {d:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
               f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
-    print(f"strategies whose {M * len(levels or [1]) * len(rates or [1]) * len(dmins or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
+    for i, m in enumerate(margins or []):
+        sel = mof == i
+        free = int((aud["first_contact"][sel] < 0).sum())
+        print(f"obstacle margin {m:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
+              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
+    print(f"strategies whose {M * len(levels or [1]) * len(rates or [1]) * len(dmins or [1]) * len(margins or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms")
     eng.close()
 

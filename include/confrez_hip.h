@@ -497,6 +497,33 @@ int cfz_loop_comm(cfz_handle *h, int tau0, int K, int32_t *delivered /* [K][S][V
 int cfz_problem_check(const cfz_spec *base, const cfz_options *base_opt, const cfz_spec *spec, const cfz_options *opt);
 int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz_options *opts, const int32_t *problem_of);
 
+/* ---- per-scenario obstacle maps of the closed loop -----------------------------------------------------------------------------------
+ * Above, every scenario of a launch stands on the handle's obstacles.  A *map* is n_obs obstacles, A_obs[n_obs][4][2] and
+ * b_obs[n_obs][4] as in cfz_spec; n_obs is the handle's (the workspace layout, the LDS size and the carry records are built from it).
+ * With a pool of M maps and map_of[S], every solve of scenario s (cfz_loop_step and cfz_loop_run alike, under either exchange rule,
+ * with or without disturbances and lossy exchange) uses the obstacles of map map_of[s]: for its separation rows, its working set, the
+ * stage-0 feasibility test that yields status 4, and its restoration.  Nothing else about a step changes.
+ * The setting composes with cfz_loop_set_problems, in either call order: scenario s then solves problem problem_of[s] on map
+ * map_of[s].  A pool problem still carries the handle's obstacles (cfz_problem_check is unchanged); the map comes from here.  The
+ * same kernels run as under a problem pool; with maps alone every scenario solves the handle's problem, and the applied input is
+ * clipped only while a disturbance is set, as under a problem pool.
+ * The audit follows the map: cfz_loop_audit measures the vehicle-obstacle signed distance of scenario s against map map_of[s] under
+ * the mapping in force WHEN IT IS CALLED (not the one a recorded step was solved under), and where[s][5] is the obstacle's index
+ * within that map.  cfz_audit_maps is cfz_audit with the maps given by the caller (M = 0 or A_obs NULL: the handle's map, which is
+ * cfz_audit); it does not read the loop's setting.  The vehicle-vehicle column does not depend on the map.
+ * The setting holds until it is changed and may change between calls, at a step boundary; carried multipliers and working-set codes
+ * stay (a warm start, not a promise).  cfz_loop_init / cfz_loop_init_tables switch it off.  Off is the default, and with it off the
+ * kernels that ran before run again.  cfz_mpc_solve*, cfz_vsl_step, cfz_dual_ws and the planning entry points keep the handle's map.
+ * cfz_map_check: host arithmetic, no device.  0 if the base->n_obs obstacles may stand in a map pool of a handle created with `base`:
+ * every entry finite and every obstacle a bounded quadrilateral (the check cfz_create makes); else -1 and cfz_last_error names the
+ * obstacle ("obstacle j ...").
+ * cfz_loop_set_maps: A_obs[M][n_obs][4][2], b_obs[M][n_obs][4], map_of[S]; M = 0 or A_obs NULL: off.  Refused, the loop's state and the
+ * setting in force staying: a call before cfz_loop_init, M < 0, a map_of[s] outside [0, M), any map that cfz_map_check refuses (the
+ * text is then prefixed with "map m: "). */
+int cfz_map_check(const cfz_spec *base, const double *A_obs /* [n_obs][4][2] */, const double *b_obs /* [n_obs][4] */);
+int cfz_loop_set_maps(cfz_handle *h, int M, const double *A_obs /* [M][n_obs][4][2] */, const double *b_obs /* [M][n_obs][4] */,
+                      const int32_t *map_of /* [S] */);
+
 /* ---- closed loop over per-scenario plans -------------------------------------------------------
  * tables[P][V][T][7]: a pool of P plan sets (each what cfz_loop_init takes as ref_table); scenario s follows set table_of[s]
  * (NULL: set s, which needs P == S).  Otherwise exactly cfz_loop_init, which is this call with P = 1 and every scenario on set 0.
@@ -525,11 +552,16 @@ int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status
  * Ties go to the lowest step, then the lowest index.  One wavefront per scenario, deterministic.  Any output may be NULL.
  * cfz_loop_audit: the handle's record; goals = the last sample of the table each scenario follows.
  * cfz_audit: a host trajectory traj[K][S][V][7] (x, y, psi, v, ...: what cfz_loop_history returns, or a `_follower_final.pkl`
- * of the reference laid out so) with goal[S][V][3]; V in 1..CFZ_MAX_NBR+1 need not be the handle's. */
+ * of the reference laid out so) with goal[S][V][3]; V in 1..CFZ_MAX_NBR+1 need not be the handle's.
+ * cfz_loop_audit follows cfz_loop_set_maps (the mapping in force when it is called); cfz_audit_maps takes M maps and map_of[S] from
+ * the caller, see "per-scenario obstacle maps" above.  Refused there: M < 0, a map_of[s] outside [0, M), a map cfz_map_check refuses. */
 int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
                    int32_t *first_contact, int32_t *arrive);
 int cfz_audit(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, double pos_tol, double psi_tol, double v_tol,
               double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive);
+int cfz_audit_maps(cfz_handle *h, int K, int S, int V, const double *traj, const double *goal, int M, const double *A_obs /* [M][n_obs][4][2] */,
+                   const double *b_obs /* [M][n_obs][4] */, const int32_t *map_of /* [S] */, double pos_tol, double psi_tol, double v_tol,
+                   double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive);
 
 const char *cfz_last_error(void);
 /* First 16 hex digits of the SHA-256 over the kernel sources this library was built from (__graft_entry__.source_hash; "unknown" for

@@ -1,0 +1,211 @@
+"""The map pool of the closed loop (`cfz_map_check`, `engine.pack_maps`, `Engine.loop_set_maps`) without a GPU: the library loads
+without a device (tests/test_abi.py), the check is host arithmetic; the Python argument handling; the obstacle helpers of
+conflict_rez_amd/scenarios.py; the replica construction of examples/evaluate_strategies.py --obstacle-margins; and the two conditions
+under which the four test maps (tests/map_pool_binding.py) make the GPU comparison of tests/test_map_pool_gpu.py meaningful, asserted
+from the host replay itself."""
+import ctypes as C
+import dataclasses
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import map_pool_binding as mb  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def engine():
+    import __graft_entry__ as g
+
+    g.build()
+    from conflict_rez_amd import engine
+
+    engine.load_library()
+    return engine
+
+
+@pytest.fixture(scope="module")
+def spec():
+    from conflict_rez_amd import scenarios
+
+    return scenarios.parking_lot_spec()
+
+
+class _Obstacle:
+    def __init__(self, A, b):
+        self.A, self.b = A, b
+
+
+def test_pack_maps(engine, spec):
+    """A list of obstacle objects, a pair of arrays and a ProblemSpec give the same rows; a wrong obstacle count is refused by name."""
+    from conflict_rez_amd import scenarios
+
+    A1, b1 = scenarios.grow_obstacles(spec, 0.1)
+    objs = [_Obstacle(A1[j], b1[j]) for j in range(spec.n_obs)]
+    A, b = engine.pack_maps(spec, [spec, (A1, b1), objs, scenarios.map_spec(spec, A1, b1), [A1.tolist(), b1.tolist()]])
+    assert A.shape == (5, spec.n_obs, 4, 2) and b.shape == (5, spec.n_obs, 4) and A.dtype == np.float64 and b.dtype == np.float64
+    assert A.flags.c_contiguous and b.flags.c_contiguous
+    assert np.array_equal(A[0], spec.A_obs) and np.array_equal(b[0], spec.b_obs)
+    for m in (1, 2, 3, 4):
+        assert np.array_equal(A[m], A1) and np.array_equal(b[m], b1), m
+    A, b = engine.pack_maps(spec, [])
+    assert A.shape == (0, spec.n_obs, 4, 2) and b.shape == (0, spec.n_obs, 4)
+    with pytest.raises(ValueError, match=r"maps\[1\] has 5 obstacles"):
+        engine.pack_maps(spec, [spec, (A1[:5], b1[:5])])
+    with pytest.raises(ValueError, match=r"maps\[0\] has 4 obstacles"):
+        engine.pack_maps(spec, [objs[:4]])
+    with pytest.raises(ValueError, match=r"maps\[2\] has 6 obstacles \(b of shape \(5, 4\)\)"):
+        engine.pack_maps(spec, [spec, spec, (A1, b1[:5])])
+    with pytest.raises(ValueError, match=r"maps\[0\] has 0 obstacles"):
+        engine.pack_maps(spec, [dataclasses.replace(spec, A_obs=np.zeros((0, 4, 2)), b_obs=np.zeros((0, 4)))])
+    with pytest.raises(TypeError, match=r"maps\[1\]"):
+        engine.pack_maps(spec, [spec, "B"])
+    # a spec without obstacles takes maps without obstacles
+    empty = dataclasses.replace(spec, A_obs=np.zeros((0, 4, 2)), b_obs=np.zeros((0, 4)))
+    A, b = engine.pack_maps(empty, [empty, []])
+    assert A.shape == (2, 0, 4, 2) and b.shape == (2, 0, 4)
+
+
+def test_map_check(engine, spec):
+    """The four test maps are accepted; an unbounded obstacle (two parallel rows repeated) and a NaN are refused, naming the obstacle."""
+    for A, b in mb.maps(spec):
+        engine.map_check(spec, A, b)
+    A, b = (np.array(x) for x in mb.maps(spec)[0])
+    A2, b2 = A.copy(), b.copy()
+    A2[3, 2], b2[3, 2] = A2[3, 0], b2[3, 0]  # row 0 three times and its opposite, 1 m behind it: a strip, open along its length
+    A2[3, 3], b2[3, 3] = A2[3, 0], b2[3, 0]
+    A2[3, 1], b2[3, 1] = -A2[3, 0], 1.0 - b2[3, 0]
+    with pytest.raises(ValueError, match="obstacle 3 is not a bounded quadrilateral"):
+        engine.map_check(spec, A2, b2)
+    for where in ("A", "b"):
+        A3, b3 = A.copy(), b.copy()
+        (A3 if where == "A" else b3)[4, 1] = np.nan
+        with pytest.raises(ValueError, match="obstacle 4 has an entry that is not finite"):
+            engine.map_check(spec, A3, b3)
+    b4 = b.copy(); b4[1, 0] = np.inf
+    with pytest.raises(ValueError, match="obstacle 1 has an entry that is not finite"):
+        engine.map_check(spec, A, b4)
+    with pytest.raises(ValueError, match="shape"):
+        engine.map_check(spec, A[:5], b[:5])
+    lib, cs = engine.load_library(), spec.to_c()
+    assert lib.cfz_map_check(C.byref(cs), None, None) != 0 and b"null" in lib.cfz_last_error()
+    assert lib.cfz_map_check(None, None, None) != 0
+    bad = dataclasses.replace(spec, N=1).to_c()
+    assert lib.cfz_map_check(C.byref(bad), A.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)) != 0 and b"N out of range" in lib.cfz_last_error()
+
+
+def test_obstacle_helpers(spec):
+    """grow_obstacles moves every face by the margin and shift_obstacles every vertex by (dx, dy), checked on the vertices; map_spec is the
+    spec of a plain engine on that map.  The reference map's rows are unit normals."""
+    from conflict_rez_amd import scenarios
+
+    A0, b0 = np.array(spec.A_obs, float), np.array(spec.b_obs, float)
+    assert np.abs(np.linalg.norm(A0, axis=-1) - 1.0).max() < 1e-12
+    V0 = mb.vertices(A0, b0)
+    for margin in (0.10, 0.20, -0.05):
+        A, b = scenarios.grow_obstacles(spec, margin)
+        assert np.array_equal(A, A0) and A is not spec.A_obs
+        V = mb.vertices(A, b)
+        # the support of the polygon along every face normal, max over the vertices of n . v, is where the face stands
+        face0 = np.einsum("jik,jvk->jiv", A0, V0).max(-1)
+        face = np.einsum("jik,jvk->jiv", A, V).max(-1)
+        assert np.abs(face0 - b0).max() < 1e-9 and np.abs(face - b).max() < 1e-9
+        assert np.abs((face - face0) - margin).max() < 1e-9, margin
+    # rows that are no unit normals: the face still moves by the margin
+    scaled = dataclasses.replace(spec, A_obs=A0 * 2.0, b_obs=b0 * 2.0)
+    A, b = scenarios.grow_obstacles(scaled, 0.1)
+    assert np.abs(mb.vertices(A, b) - mb.vertices(*scenarios.grow_obstacles(spec, 0.1))).max() < 1e-9
+    for d in ((0.15, -0.15), (-1.0, 2.5)):
+        A, b = scenarios.shift_obstacles(spec, *d)
+        assert np.array_equal(A, A0)
+        assert np.abs(mb.vertices(A, b) - (V0 + np.asarray(d))).max() < 1e-9, d
+    assert np.array_equal(spec.A_obs, A0) and np.array_equal(spec.b_obs, b0)  # the spec is left as it was
+    A, b = scenarios.shift_obstacles(spec, 0.15, -0.15)
+    ms = scenarios.map_spec(spec, A, b)
+    assert np.array_equal(ms.A_obs, A) and np.array_equal(ms.b_obs, b) and ms.n_obs == spec.n_obs
+    for f in dataclasses.fields(spec):
+        if f.name not in ("A_obs", "b_obs"):
+            assert np.array_equal(getattr(ms, f.name), getattr(spec, f.name)), f.name
+    # the four maps differ pairwise
+    M = mb.maps(spec)
+    for i in range(4):
+        for j in range(i + 1, 4):
+            assert not np.array_equal(M[i][1], M[j][1]), (i, j)
+
+
+def test_loop_set_maps_arguments(engine, spec):
+    """What `Engine.loop_set_maps` / `Engine.audit` refuse on the Python side, before the library is called (no handle is needed)."""
+    e = object.__new__(engine.Engine)
+    e.spec = spec
+    M = mb.maps(spec)
+    assert e._maps(None, None, 8) == (0, None, None, None) and e._maps([], None, 8) == (0, None, None, None)
+    n, A, b, mo = e._maps(M, np.arange(8) % 4, 8)
+    assert n == 4 and A.shape == (4, 6, 4, 2) and b.shape == (4, 6, 4) and mo.dtype == np.int32 and mo.tolist() == [0, 1, 2, 3] * 2
+    with pytest.raises(ValueError, match="map_of is required"):
+        e._maps(M, None, 8)
+    with pytest.raises(ValueError, match="map_of must hold 8 integers"):
+        e._maps(M, np.arange(7) % 4, 8)
+    with pytest.raises(ValueError, match="map_of must hold 8 integers"):
+        e._maps(M, np.zeros(8), 8)
+
+
+def test_replicas_of_the_strategy_example():
+    """examples/evaluate_strategies.py --obstacle-margins: the margin is the outermost block, after noise level, drop rate and clearance;
+    every replica keeps its start's stream id; without margins the batch is what it was."""
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from evaluate_strategies import replicate
+
+    S0, V = 5, 4
+    k0 = np.arange(10, 10 + S0, dtype=np.int32)
+    noise = np.random.default_rng(0).normal(size=(S0, V, 5))
+    tof = np.array([0, 0, 1, 1, 2], np.int32)
+    levels, rates, dmins, margins = [0.0, 1.0], [0.0, 0.3], [0.05, 0.1, 0.2], [0.0, 0.1, 0.2, 0.3]
+    r = replicate(k0, noise, tof, levels, rates, dmins, margins)
+    L, R, D, G = len(levels), len(rates), len(dmins), len(margins)
+    S = S0 * L * R * D * G
+    assert all(len(r[k]) == S for k in r)
+    i = np.arange(S)
+    assert np.array_equal(r["stream"], i % S0) and np.array_equal(r["k0"], k0[i % S0]) and np.array_equal(r["noise"], noise[i % S0])
+    assert np.array_equal(r["level"], np.asarray(levels)[(i // S0) % L]) and np.array_equal(r["drop"], np.asarray(rates)[(i // (S0 * L)) % R])
+    assert np.array_equal(r["problem_of"], (i // (S0 * L * R)) % D)
+    assert np.array_equal(r["map_of"], i // (S0 * L * R * D)) and r["map_of"].dtype == np.int32
+    assert len(set(zip(r["stream"].tolist(), r["level"].tolist(), r["drop"].tolist(), r["problem_of"].tolist(), r["map_of"].tolist()))) == S
+    r = replicate(k0, noise, tof, margins=margins)
+    assert r["level"] is None and r["drop"] is None and r["problem_of"] is None
+    assert np.array_equal(r["map_of"], np.arange(S0 * G) // S0) and np.array_equal(r["stream"], np.arange(S0 * G) % S0)
+    assert "map_of" not in replicate(k0, noise, tof, levels, rates, dmins)
+
+
+def test_the_maps_move_the_outcome_and_every_map_converges(spec, ospec):
+    """The two conditions the GPU comparison rests on, from the host replay (S = 8, K = 8, Jacobi, map_of[s] = s % 4, the batch of
+    test_map_pool_gpu.py::test_against_the_host_replay): every scenario on map B, C or D ends in final states that differ from its
+    replay on map A bit for bit and by more than 1e-6 in some component of a final state, and every map has at least one converged solve in the batch.
+    A later change of the workload then cannot quietly make the GPU comparison vacuous."""
+    import __graft_entry__ as g
+
+    g.build()
+    from conflict_rez_amd import scenarios
+
+    S, K = 8, 8
+    table, _ = scenarios.load_reference_table(kind="planned")
+    k0, noise = scenarios.sample_scenarios(S, table, seed=2024, spec=spec)
+    M = mb.maps(spec)
+    map_of = np.arange(S) % 4
+    mixed = mb.replay_mixed(ospec, M, map_of, table, k0, noise, K, spec.dt, spec.wb)
+    other = np.flatnonzero(map_of > 0)
+    base = mb.replay_mixed(ospec, M, np.zeros(S, int), table, k0, noise, K, spec.dt, spec.wb, scenarios_=other)
+    status = np.stack([st for _, st, _ in mixed])  # [K, S, V]
+    end, end0 = mixed[-1][0], base[-1][0]
+    for s in other:
+        gap = float(np.abs(end[s] - end0[s]).max())  # over the state (x, y, psi, v, delta) of the four vehicles
+        print(f"scenario {s} on map {mb.NAMES[map_of[s]]}: final states differ from map A's by {gap:.2e} (positions by "
+              f"{float(np.abs(end[s, :, :2] - end0[s, :, :2]).max()):.2e} m)")
+        assert not np.array_equal(end[s], end0[s]), s
+        assert gap > 1e-6, (s, gap)
+    for m in range(4):
+        conv = int((status[:, map_of == m] == 0).sum())
+        print(f"map {mb.NAMES[m]}: {conv} of {status[:, map_of == m].size} solves converged")
+        assert conv >= 1, mb.NAMES[m]

@@ -4,7 +4,9 @@ steps; 3 `loop_step`s, Jacobi and under seeded orders; a sequential persistent r
 tests/disturbance_binding.SIGMA); a lossy exchange (p_drop 0.3), Jacobi and sequential, run of 4; the pool of the four problems of
 tests/problem_pool_binding.py under noise, run of 4 and stepped 3 times; and runs of 4 through the remaining persistent kernels
 (sequential + noise, sequential + pool, pool + loss, sequential + pool + loss), so that all ten and both stepwise solve kernels are
-compared.  Every loop is compared at its end point and over its record; the exit status is 1 when anything differs.
+compared; and, where both builds have cfz_loop_set_maps, the four maps of tests/map_pool_binding.py under noise, run of 4 and stepped 3
+times, and together with the problems, the sequential order and loss, each with its audit.  Every loop is compared at its end point and
+over its record; the exit status is 1 when anything differs.  A key that only the second build has is listed, not compared.
 usage: python tools/gpu_lib_compare.py <libA.so> <libB.so> [scenarios]     (each library runs in a process of its own)"""
 import os, subprocess, sys, tempfile
 import numpy as np
@@ -15,6 +17,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     from conflict_rez_amd import engine, scenarios
     from disturbance_binding import SIGMA
     from problem_pool_binding import problems
+    from map_pool_binding import maps as test_maps
     lib, S, out = sys.argv[2], int(sys.argv[3]), sys.argv[4]
     engine._lib = engine.load_library(lib)
     spec = scenarios.parking_lot_spec()
@@ -45,7 +48,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     loop("dist", lambda: e.loop_set_disturbance(2024, **SIGMA), lambda: e.loop_run(4))
     probs, pof = problems(spec), np.arange(S) % 4
 
-    def setting(seq=False, noise=False, comm=False, pool=False):
+    def setting(seq=False, noise=False, comm=False, pool=False, maps=False):
         def setup():
             if seq:
                 e.loop_set_order(order)
@@ -55,6 +58,8 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
                 e.loop_set_comm(2024, 0.3, max_age=3)
             if pool:
                 e.loop_set_problems(probs, pof)
+            if maps:
+                e.loop_set_maps(test_maps(spec), (np.arange(S) // 4) % 4)
         return setup
 
     loop("comm", setting(comm=True), lambda: e.loop_run(4))
@@ -65,6 +70,13 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     loop("seqpool", setting(seq=True, pool=True), lambda: e.loop_run(4))
     loop("poolcomm", setting(comm=True, pool=True), lambda: e.loop_run(4))
     loop("seqpoolcomm", setting(seq=True, comm=True, pool=True), lambda: e.loop_run(4))
+    res.update({"audit_" + k: v for k, v in e.loop_audit().items()})  # audit_kernel, on the handle's map
+    if hasattr(e.lib, "cfz_loop_set_maps"):
+        loop("maps", setting(noise=True, maps=True), lambda: e.loop_run(4))
+        res.update({"maps_audit_" + k: v for k, v in e.loop_audit().items()})
+        loop("mapsstep", setting(noise=True, maps=True), three_steps)
+        loop("seqpoolmapscomm", setting(seq=True, comm=True, pool=True, maps=True), lambda: e.loop_run(4))
+        res.update({"seqpoolmapscomm_audit_" + k: v for k, v in e.loop_audit().items()})
     np.savez(out, **res)
     sys.exit(0)
 S = int(sys.argv[3]) if len(sys.argv) > 3 else 256
@@ -87,6 +99,9 @@ for k in a:
     if k.endswith("_its"):
         print(f"{k[:-4]}: IPM iterations {int(a[k])} / {int(b[k])}")
         differ += int(a[k]) != int(b[k])
+only_b = sorted(k for k in b if k not in a)
+if only_b:
+    print(f"only in the second build, not compared: {len(only_b)} keys ({', '.join(sorted({k.split('_')[0] for k in only_b}))})")
 print("closed loop iterations", int(a["loop_its"]), int(b["loop_its"]))
 print("ALL EQUAL" if not differ else f"{differ} DIFFERENCES")
 sys.exit(1 if differ else 0)

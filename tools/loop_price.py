@@ -10,8 +10,11 @@ of alternated launches in one process, their medians, the ratios and the spread 
   --setting pool         every problem the handle's own: loop_kernel_pool / loop_kernel_seq_pool, once with a pool of P = 1 problem that
                          every scenario reads, once with P = S copies at distinct addresses, one per scenario (the resident instances of
                          a CU then read different 2 KB blocks through one scalar cache)
+  --setting maps         every map the handle's own: the same pool kernels, once with M = 1 map that every scenario reads, once with M = S
+                         copies at distinct addresses, one per scenario (S blocks as under P = S, and S distinct 960-byte obstacle tables
+                         read through vector loads where the plain kernels read one shared table)
 
-usage: python tools/loop_price.py --setting disturbance|comm|pool [--scenarios 1024,8192] [--steps 25] [--repeats 5]
+usage: python tools/loop_price.py --setting disturbance|comm|pool|maps [--scenarios 1024,8192] [--steps 25] [--repeats 5]
                                   [--sigma] [--max-age 3] [--rates 0.1,0.3]"""
 import argparse
 import os
@@ -26,7 +29,7 @@ SIGMA = dict(meas=(0.02, 0.02, 0.005, 0.02, 0.0), act=(0.05, 0.02), proc=(0.005,
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--setting", required=True, choices=("disturbance", "comm", "pool"))
+    ap.add_argument("--setting", required=True, choices=("disturbance", "comm", "pool", "maps"))
     ap.add_argument("--scenarios", default="1024,8192")
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--repeats", type=int, default=5)
@@ -51,7 +54,10 @@ def main():
             "comm": ({"zero": lambda e: e.loop_set_comm(2024, 0.0, max_age=a.max_age)}, "p_drop = 0 must reproduce the lossless loop"),
             "pool": ({"P=1": lambda e: e.loop_set_problems([spec], np.zeros(S, np.int32)),
                       "P=S": lambda e: e.loop_set_problems([spec] * S, np.arange(S, dtype=np.int32))},
-                     "a pool of the handle's own problem must reproduce the plain loop")}[a.setting]
+                     "a pool of the handle's own problem must reproduce the plain loop"),
+            "maps": ({"M=1": lambda e: e.loop_set_maps([spec], np.zeros(S, np.int32)),
+                      "M=S": lambda e: e.loop_set_maps([spec] * S, np.arange(S, dtype=np.int32))},
+                     "a pool of the handle's own map must reproduce the plain loop")}[a.setting]
         forms = {"plain": None, **neutral}
 
         def launch(seq, setup):
@@ -91,7 +97,7 @@ def main():
                         print(f"    p_drop {rate:g} compensate {int(comp)}: {t:8.2f} ms (x {t / mp:.3f} of plain), {n / (S * V * K):.2f} IPM iterations per solve, "
                               f"{conv} of {S * V * K} solves converged", flush=True)
             else:
-                print(head + spread + "; " + "; ".join(f"pool {k} {med[k]:8.2f} ms {rng[k]}, ratio {med[k] / mp:.4f}" for k in ("P=1", "P=S"))
+                print(head + spread + "; " + "; ".join(f"{a.setting} {k} {med[k]:8.2f} ms {rng[k]}, ratio {med[k] / mp:.4f}" for k in neutral)
                       + f"; {its / (S * V * K):.2f} IPM iterations per solve", flush=True)
         eng.close()
 
