@@ -55,6 +55,8 @@ def step_inputs(table, k, state, pred, v, new_pred=None, before=(), read=None):
 def replay(ospec: MpcSpec, table, k0, noise, steps, dt=0.1, wb=2.5, carry_duals=True, opt=None, *, order=None, d=None, box=None,
            table_of=None, comm=None, ages=None):
     """Generator: after every iteration yields (state [S,V,5], pred [S,V,7,N], status [S,V], iters [S,V]).
+    ospec, opt: one MpcSpec and one IpmOptions (or None) for the batch, or a sequence of S of either: scenario s is solved with its own
+    entry (the device's problem and map pools); specs that differ in N or n_nbr are refused, as the device refuses them.
     order [S,V]: the sequential exchange, scenario s steps its vehicles in the order order[s] (None: Jacobi).  d [K,S,V,12]: the device's
     disturbances (`Engine.loop_disturbance`) with box [2,2], the bounds of (a, w): the solver sees state + d[0:5], the plant takes
     clip(input + d[5:7]) from the true state, d[7:12] is added to what it returns.  table_of [S]: `table` is a pool [P,V,T,7].
@@ -63,11 +65,16 @@ def replay(ospec: MpcSpec, table, k0, noise, steps, dt=0.1, wb=2.5, carry_duals=
     vehicles ranked later in it) and asks the setting one question per neighbour, `read(t, s, v, u, earlier, N) -> (tau, rows [N])`:
     the message vehicle v takes of neighbour u and the rows it reads of it; lossless, that is (t - 1, advanced), or (t, as it stands)
     of a neighbour ranked `earlier`.  ages (a list, or None) receives (t, s, v, u, age) of every such read."""
-    S, V, N = len(k0), table.shape[-3], ospec.N
+    S, V = len(k0), table.shape[-3]
+    specs = [ospec] * S if isinstance(ospec, MpcSpec) else list(ospec)
+    opts = list(opt) if isinstance(opt, (list, tuple)) else [opt] * S
+    N = specs[0].N
+    if len(specs) != S or len(opts) != S or any((sp.N, sp.n_nbr) != (N, specs[0].n_nbr) for sp in specs):
+        raise ValueError(f"replay: {S} scenarios take one spec and one options entry each, the specs equal in N and n_nbr")
     state, pred = seed(table, k0, noise, N, table_of)
     hist = {-1: pred}
     carry = [[None] * V for _ in range(S)]
-    kw = {} if opt is None else {"opt": opt}
+    kws = [{} if o is None else {"opt": o} for o in opts]
     for t in range(steps):
         cm = None if comm is None else comm(t)
         newp = hist[t] = pred.copy()
@@ -85,7 +92,7 @@ def replay(ospec: MpcSpec, table, k0, noise, steps, dt=0.1, wb=2.5, carry_duals=
                         return hist[tau][s, u], rows
                 x0, ref, nb, w = step_inputs(tab, k0[s] + t, state[s], pred[s], v, newp[s], done, read)
                 dd = None if d is None else d[t, s, v]
-                r = port.solve(ospec, x0 if dd is None else x0 + dd[:5], ref, nb, w.T.copy(), **kw, carry=carry[s][v] if carry_duals else None)
+                r = port.solve(specs[s], x0 if dd is None else x0 + dd[:5], ref, nb, w.T.copy(), **kws[s], carry=carry[s][v] if carry_duals else None)
                 carry[s][v] = r["carry"]
                 newp[s, v] = r["p"].T if r["status"] == 0 else w
                 u = newp[s, v][5:7, 0] if dd is None else np.clip(newp[s, v][5:7, 0] + dd[5:7], box[:, 0], box[:, 1])

@@ -3,9 +3,10 @@
 definitions (vertex-edge distances, separating-axis overlaps) that both the CPU build and the GPU kernel are checked against."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from emu_build import build_shared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(ROOT, "tests", "_build", "libcfz_audit_emu.so")
@@ -14,12 +15,7 @@ _lib = None
 
 def build(force=False):
     srcs = [os.path.join(ROOT, "tests", "emu", "cfz_audit_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_audit.inl")]
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(s) for s in srcs):
-        os.makedirs(os.path.dirname(_LIB), exist_ok=True)
-        tmp = _LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, srcs[0]])
-        os.replace(tmp, _LIB)
-    return _LIB
+    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 
 def lib():

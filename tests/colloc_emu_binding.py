@@ -1,9 +1,10 @@
 """ctypes binding of the test-only CPU build of the collocation solver source (tests/emu/cfz_colloc_emu.cpp)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from emu_build import build_shared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(ROOT, "tests", "_build", "libcfz_colloc_emu.so")
@@ -25,12 +26,7 @@ class CSpec(C.Structure):
 def build(force=False):
     srcs = [os.path.join(ROOT, "tests", "emu", "cfz_colloc_emu.cpp")] + [os.path.join(ROOT, "conflict_rez_amd", "csrc", f)
                                                                          for f in ("cfz_colloc.inl", "cfz_struct.inl", "cfz_jstruct.inl", "cfz_plan.inl", "cfz_solver.inl")]
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(s) for s in srcs):
-        os.makedirs(os.path.dirname(_LIB), exist_ok=True)
-        tmp = _LIB + ".%d.tmp" % os.getpid()  # built aside and renamed: parallel test workers never see a half-written library
-        subprocess.check_call(["g++", "-O2", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized", "-fPIC", "-shared", "-o", tmp, srcs[0]])
-        os.replace(tmp, _LIB)
-    return _LIB
+    return build_shared(_LIB, srcs, ["-O2", "-Wno-unknown-pragmas", "-Wno-maybe-uninitialized"], force)
 
 
 _lib = None

@@ -4,13 +4,13 @@ of the delivery bits on top of `disturbance_binding.philox4x32_10`, and the age 
 replay (`oracle.closed_loop.replay(comm=...)`, which keeps the message history) asks which message and which rows a vehicle reads."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from disturbance_binding import philox4x32_10  # noqa: E402
+from emu_build import build_shared  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(ROOT, "tests", "_build", "libcfz_comm_emu.so")
@@ -21,12 +21,7 @@ MAX_AGE = 6  # CFZ_MAX_AGE
 def build(force=False):
     csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
     srcs = [os.path.join(ROOT, "tests", "emu", "cfz_comm_emu.cpp"), os.path.join(csrc, "cfz_comm.inl"), os.path.join(csrc, "cfz_disturb.inl")]
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(s) for s in srcs):
-        os.makedirs(os.path.dirname(_LIB), exist_ok=True)
-        tmp = _LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-o", tmp, srcs[0]])
-        os.replace(tmp, _LIB)
-    return _LIB
+    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 
 def lib():

@@ -1,5 +1,5 @@
 """Shared by the map-pool tests (tests/test_map_pool_gpu.py, tests/test_map_pool_host.py): the four test maps of `cfz_loop_set_maps`
-over the `parking_lot_spec()` handle and the host replay (oracle/closed_loop.replay) of a batch whose scenarios stand on different maps.
+over the `parking_lot_spec()` handle and their form for the host replay (oracle/closed_loop.replay, which takes one MpcSpec per scenario).
 
   A  the handle's own obstacles
   B  every face moved outwards by 0.10 m (`scenarios.grow_obstacles`)
@@ -30,18 +30,7 @@ def vertices(A, b):
     return np.stack([ab.obstacle_vertices(A[j], b[j]) for j in range(len(A))])
 
 
-def replay_mixed(ospec, maps_, map_of, table, k0, noise, steps, dt, wb, order=None, scenarios_=None):
-    """The host replay of a batch on mixed maps, scenario by scenario with the scenario's own obstacles in the MpcSpec (scenarios do not
-    interact); scenarios_ (default: all) are the ones replayed, the others stay zero.
-    -> per step (state [S,V,5], status [S,V], iters [S,V])."""
-    from oracle.closed_loop import replay
-
-    S, V = len(k0), table.shape[0]
-    out = [(np.zeros((S, V, 5)), np.zeros((S, V), int), np.zeros((S, V), int)) for _ in range(steps)]
-    for s in (range(S) if scenarios_ is None else scenarios_):
-        A, b = maps_[map_of[s]]
-        osp = dataclasses.replace(ospec, A_obs=np.array(A, float), b_obs=np.array(b, float))
-        gen = replay(osp, table, k0[s : s + 1], noise[s : s + 1], steps, dt=dt, wb=wb, order=None if order is None else order[s : s + 1])
-        for t, (state, _, status, iters) in enumerate(gen):
-            out[t][0][s], out[t][1][s], out[t][2][s] = state[0], status[0], iters[0]
-    return out
+def oracle_spec(ospec, m):
+    """The MpcSpec of the handle's problem on the map m = (A_obs, b_obs), for the host replay."""
+    A, b = m
+    return dataclasses.replace(ospec, A_obs=np.array(A, float), b_obs=np.array(b, float))

@@ -1,9 +1,10 @@
 """ctypes binding of the test-only CPU build of the planning solver source (tests/emu/cfz_plan_emu.cpp)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from emu_build import build_shared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _LIB = os.path.join(ROOT, "tests", "_build", "libcfz_plan_emu.so")
@@ -20,12 +21,7 @@ class PSpec(C.Structure):
 
 def build(force=False):
     srcs = [os.path.join(ROOT, "tests", "emu", "cfz_plan_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_plan.inl")]
-    if force or not os.path.exists(_LIB) or os.path.getmtime(_LIB) < max(os.path.getmtime(s) for s in srcs):
-        os.makedirs(os.path.dirname(_LIB), exist_ok=True)
-        tmp = _LIB + ".%d.tmp" % os.getpid()  # built aside and renamed: parallel test workers never see a half-written library
-        subprocess.check_call(["g++", "-O2", "-Wno-unknown-pragmas", "-fPIC", "-shared", "-o", tmp, srcs[0]])
-        os.replace(tmp, _LIB)
-    return _LIB
+    return build_shared(_LIB, srcs, ["-O2", "-Wno-unknown-pragmas"], force)
 
 
 def make_spec(nlp, opt):

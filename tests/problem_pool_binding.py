@@ -42,18 +42,3 @@ def oracle_problem(ospec, item):
     return (dataclasses.replace(ospec, dmin=sp.dmin, bounds=np.array(sp.bounds, float), weights=np.array(sp.weights, float)),
             IpmOptions(**options_of(item)))
 
-
-def replay_mixed(ospec, probs, problem_of, table, k0, noise, steps, dt, wb, order=None):
-    """The host replay of a mixed batch, scenario by scenario with the scenario's own MpcSpec and options (scenarios do not interact).
-    -> per step (state [S,V,5], status [S,V], iters [S,V])."""
-    from oracle.closed_loop import replay
-
-    S, V = len(k0), table.shape[0]
-    out = [(np.zeros((S, V, 5)), np.zeros((S, V), int), np.zeros((S, V), int)) for _ in range(steps)]
-    for s in range(S):
-        osp, opt = oracle_problem(ospec, probs[problem_of[s]])
-        gen = replay(osp, table, k0[s : s + 1], noise[s : s + 1], steps, dt=dt, wb=wb, opt=opt,
-                     order=None if order is None else order[s : s + 1])
-        for t, (state, _, status, iters) in enumerate(gen):
-            out[t][0][s], out[t][1][s], out[t][2][s] = state[0], status[0], iters[0]
-    return out

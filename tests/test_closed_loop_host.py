@@ -1,5 +1,6 @@
 """oracle/closed_loop.py without a GPU: `replay`'s options against its plain form, and `replay` against `step_inputs`, the one host
-statement of what a solve of the closed loop is fed.  2 scenarios x 3 steps of the planned table, feasible starts."""
+statement of what a solve of the closed loop is fed (2 scenarios x 3 steps of the planned table, feasible starts); and `replay` with one
+problem per scenario against the one-scenario replays (3 scenarios on the test maps and problems of the pool modules)."""
 import numpy as np
 import pytest
 
@@ -69,3 +70,58 @@ def test_replay_feeds_every_solve_what_step_inputs_returns(case, monkeypatch):
                 n_unshifted += sum(u in order[s][:r] for u in others)
         state, pred = state1, pred1
     assert n_unshifted == STEPS * S * V * (V - 1) // 2
+
+
+
+def _pool_case(case, which):
+    """(table, k0, noise, specs, options) of three scenarios (seed 2024) of the planned table on the maps [A, B, D] of map_pool_binding or
+    the problems [A, D, B] of problem_pool_binding; specs[0] is the handle's own."""
+    import map_pool_binding as mb
+    import problem_pool_binding as pb
+    from conflict_rez_amd import scenarios
+
+    spec, ospec, table = case[:3]
+    k0, noise = scenarios.sample_scenarios(3, table, seed=2024, spec=spec)
+    if which == "maps":
+        return table, k0, noise, [mb.oracle_spec(ospec, mb.maps(spec)[m]) for m in (0, 1, 3)], [None] * 3
+    specs, opts = zip(*(pb.oracle_problem(ospec, pb.problems(spec)[p]) for p in (0, 3, 1)))
+    return table, k0, noise, specs, opts
+
+
+def _same_bits(a, b, what, s=None):
+    """The replays a and b are equal bit for bit at every step; s: scenario s of a against b, a replay of that scenario alone."""
+    assert len(a) == len(b) == STEPS
+    for t, (x, y) in enumerate(zip(a, b)):
+        for name, p, q in zip(("state", "pred", "status", "iters"), x, y):
+            assert np.array_equal(p if s is None else p[s : s + 1], q), (what, s, t, name)
+
+
+@pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
+@pytest.mark.parametrize("which", ["maps", "problems"])
+def test_per_scenario_problems_are_the_separate_replays(case, which, exchange):
+    """replay with one MpcSpec (and IpmOptions) per scenario equals, bit for bit in state, prediction, status and iterations, the three
+    one-scenario replays with those specs, under Jacobi and under a sequential order.  Not vacuous: scenarios 1 and 2 end in other
+    states than under the handle's own problem, scenario 0 (on it) does not."""
+    table, k0, noise, specs, opts = _pool_case(case, which)
+    order = np.array([[2, 0, 3, 1], [3, 2, 1, 0], [1, 3, 0, 2]]) if exchange == "sequential" else None
+    kw = dict(dt=case[0].dt, wb=case[0].wb)
+    joint = list(closed_loop.replay(specs, table, k0, noise, STEPS, opt=opts, order=order, **kw))
+    for s in range(3):
+        one = slice(s, s + 1)
+        _same_bits(joint, list(closed_loop.replay(specs[s], table, k0[one], noise[one], STEPS, opt=opts[s], order=None if order is None else order[one], **kw)), which, s)
+    under_a = list(closed_loop.replay(specs[0], table, k0, noise, STEPS, opt=opts[0], order=order, **kw))
+    assert [not np.array_equal(joint[-1][0][s], under_a[-1][0][s]) for s in range(3)] == [False, True, True]
+
+
+def test_one_problem_is_the_same_problem_for_every_scenario(case):
+    """A single MpcSpec and the same spec repeated per scenario give equal bits; a wrong count and specs that differ in N are refused."""
+    import dataclasses
+
+    ospec = case[1]
+    table, k0, noise, _, _ = _pool_case(case, "maps")
+    kw = dict(dt=case[0].dt, wb=case[0].wb)
+    one = list(closed_loop.replay(ospec, table, k0, noise, STEPS, **kw))
+    _same_bits(one, list(closed_loop.replay([ospec] * 3, table, k0, noise, STEPS, opt=[None] * 3, **kw)), "the spec three times")
+    for bad in ([ospec, dataclasses.replace(ospec, N=ospec.N - 2), ospec], [ospec] * 2):
+        with pytest.raises(ValueError, match="N and n_nbr"):
+            next(closed_loop.replay(bad, table, k0, noise, STEPS, **kw))

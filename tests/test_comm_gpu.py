@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import comm_binding as cb  # noqa: E402
 import disturbance_binding as db  # noqa: E402
-from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
+from loop_cases import against_replay, orders as _orders, planned as _planned, run as _run, same as _same, stepwise  # noqa: E402
 from oracle.closed_loop import replay  # noqa: E402
 
 SIG = db.SIGMA
@@ -122,12 +122,8 @@ def test_everything_dropped(eng, ospec, exchange, A):
                 eng.loop_step()
         else:
             eng.loop_run(K)
-        h = eng.loop_history()
-        worst = 0.0
-        for t in range(K):
-            assert np.array_equal(h["status"][t], ref[t][2]) and np.array_equal(h["iters"][t], ref[t][3]), (how, t)
-            worst = max(worst, float(np.abs(h["traj"][t][..., :5] - ref[t][0]).max()))
-        print(f"{exchange}, A = {A}, {how}: max |state - replay| {worst:.2e}; {sum(int((r[2] == 0).sum()) for r in ref)} of {K * S * V} converge")
+        worst, n_conv = against_replay(eng.loop_history(), ref, how)
+        print(f"{exchange}, A = {A}, {how}: max |state - replay| {worst:.2e}; {n_conv} of {K * S * V} converge")
         assert worst < 1e-6
 
 
@@ -187,16 +183,10 @@ def test_against_the_host_replay(eng, ospec, S, exchange, compensate):
         eng.loop_set_order(order)
     eng.loop_set_comm(SEED, 0.3, max_age=3, compensate=compensate)
     setting = cb.Setting(3, compensate, -1, bits=eng.loop_comm(0, steps))
-    got = []
-    for _ in range(steps):
-        eng.loop_step()
-        got.append(eng.loop_get())
-    ages, n_conv, worst = [], 0, 0.0
-    for t, (state, _, status, iters) in enumerate(replay(ospec, table, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, order=order,
-                                                         comm=lambda t: setting, ages=ages)):
-        assert np.array_equal(got[t]["status"], status) and np.array_equal(got[t]["iters"], iters), t
-        worst = max(worst, float(np.abs(got[t]["state"] - state).max()))
-        n_conv += int((status == 0).sum())
+    got = stepwise(eng, steps)
+    ages = []
+    worst, n_conv = against_replay(got, replay(ospec, table, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, order=order,
+                                               comm=lambda t: setting, ages=ages))
     old = sum(a >= 2 for *_, a in ages)
     print(f"{exchange}: {n_conv} of {S * V * steps} replayed solves converge; {old} of {len(ages)} neighbour reads have age >= 2; "
           f"max |state - replay| {worst:.2e}")
@@ -222,10 +212,7 @@ def test_setting_at_a_step_boundary(eng, ospec):
     h = eng.loop_history()
     ages = []
     comm = lambda t: None if t < cuts[0] else (first if t < cuts[1] else second)
-    worst = 0.0
-    for t, (state, _, status, iters) in enumerate(replay(ospec, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, comm=comm, ages=ages)):
-        assert np.array_equal(h["status"][t], status) and np.array_equal(h["iters"][t], iters), t
-        worst = max(worst, float(np.abs(h["traj"][t][..., :5] - state).max()))
+    worst, _ = against_replay(h, replay(ospec, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, comm=comm, ages=ages))
     by_t = {t: max(a for tt, *_, a in ages if tt == t) for t in range(cuts[0], K)}
     print(f"max |state - replay| {worst:.2e}; largest age per iteration {by_t}")
     assert worst < 1e-6

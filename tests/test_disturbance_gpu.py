@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import disturbance_binding as db  # noqa: E402
-from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
+from loop_cases import against_replay, orders as _orders, planned as _planned, run as _run, same as _same, stepwise  # noqa: E402
 
 SIG = db.SIGMA
 SEED = 2024
@@ -228,16 +228,9 @@ def test_against_the_host_replay(eng, ospec, S, exchange):
         eng.loop_set_order(order)
     eng.loop_set_disturbance(SEED, **SIG)
     d = eng.loop_disturbance(0, steps)
-    got = []
-    for _ in range(steps):
-        eng.loop_step()
-        got.append(eng.loop_get())
+    got = stepwise(eng, steps)
     plain = _run(eng, ((table, k0, noise), {}), steps, "step", order, record=False)
-    n_conv, worst = 0, 0.0
-    for t, (state, _, status, iters) in enumerate(replay(ospec, table, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, order=order, d=d, box=box)):
-        assert np.array_equal(got[t]["status"], status) and np.array_equal(got[t]["iters"], iters), t
-        worst = max(worst, float(np.abs(got[t]["state"] - state).max()))
-        n_conv += int((status == 0).sum())
+    worst, n_conv = against_replay(got, replay(ospec, table, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, order=order, d=d, box=box))
     moved = float(np.abs(got[-1]["state"] - plain["state"]).max())
     print(f"{exchange}: {n_conv} of {S * V * steps} replayed solves converge; max |state - replay| {worst:.2e}; final states moved by up to "
           f"{moved:.2f} against the undisturbed loop")

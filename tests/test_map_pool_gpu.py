@@ -8,6 +8,8 @@ The four test maps (tests/map_pool_binding.py) over the `parking_lot_spec()` han
 tests/test_map_pool_host.py asserts from the host replay that the map moves the outcome of every scenario of the batch of
 test_against_the_host_replay and that every map has converged solves there.  A plain engine created on a map
 (`scenarios.map_spec`) is the parent's code path for that map: the mixed batch must equal it bit for bit.
+
+What every per-scenario pool has is tests/loop_cases.py's, written against `POOL`; here: the numbered statement, that call, what is special.
 """
 import os
 import sys
@@ -22,12 +24,23 @@ import audit_binding as ab  # noqa: E402
 import disturbance_binding as db  # noqa: E402
 import map_pool_binding as mb  # noqa: E402
 import problem_pool_binding as pb  # noqa: E402
+import loop_cases as lc  # noqa: E402
 from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
 
 SIG = db.SIGMA
 SEED = 2024
 S16, K6 = 16, 6
 TOL = dict(pos_tol=0.3, psi_tol=0.1, v_tol=0.1)
+
+
+def _plain(spec, m, max_batch):
+    from conflict_rez_amd import engine, scenarios
+
+    return engine.Engine(scenarios.map_spec(spec, *m), max_batch=max_batch)
+
+
+POOL = lc.Pool(set=lambda e, maps, map_of: e.loop_set_maps(maps, map_of), off=lambda e: e.loop_set_maps(None), own=lambda e: e.spec,
+               entries=mb.maps, plain=_plain, names=mb.NAMES)
 
 
 @pytest.fixture(scope="module")
@@ -50,20 +63,10 @@ def maps(eng):
 @pytest.fixture(scope="module")
 def plain_engines(eng, maps):
     """One plain engine per map, created with the handle's spec on that map: the parent's code path."""
-    from conflict_rez_amd import engine, scenarios
-
-    es = [engine.Engine(scenarios.map_spec(eng.spec, A, b), max_batch=S16 * 4) for A, b in maps]
+    es = [POOL.plain(eng.spec, m, S16 * 4) for m in maps]
     yield es
     for e in es:
         e.close()
-
-
-def _rows(a, rows):
-    return {k: (v[:, rows] if k.startswith("rec_") else v[rows]) for k, v in a.items()}
-
-
-def _goals(table, S):
-    return np.broadcast_to(table[:, -1, :3], (S,) + table[:, -1, :3].shape).copy()
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
@@ -74,18 +77,8 @@ def test_off_is_off(eng, how, exchange):
     S, K, V = S16, K6, eng.spec.n_nbr + 1
     init = _planned(eng, S)
     order = _orders(S, V, 11) if exchange == "sequential" else None
-    mof3 = np.random.default_rng(4).integers(0, 3, S)
-    assert len(set(mof3)) == 3
-
-    def set_unset(e):
-        e.loop_set_maps(mb.maps(e.spec), np.arange(S) % 4)
-        e.loop_set_maps(None)
-
-    plain = _run(eng, init, K, how, order)
+    plain = lc.off_is_off(POOL, eng, init, K, how, order)
     assert (plain["rec_status"] == 0).mean() > 0.5
-    _same(plain, _run(eng, init, K, how, order, lambda e: e.loop_set_maps([e.spec], np.zeros(S, int))), "M = 1, the handle's own")
-    _same(plain, _run(eng, init, K, how, order, lambda e: e.loop_set_maps([e.spec] * 3, mof3)), "M = 3 identical copies")
-    _same(plain, _run(eng, init, K, how, order, set_unset), "set, then unset")
     _same(plain, _run(eng, init, K, how, order, lambda e: e.loop_set_maps([])), "an empty pool is off")
 
 
@@ -99,24 +92,8 @@ def test_off_is_off_under_a_lossy_exchange(eng, how, exchange):
     S, K, V = S16, K6, eng.spec.n_nbr + 1
     init = _planned(eng, S)
     order = _orders(S, V, 11) if exchange == "sequential" else None
-    mof3 = np.random.default_rng(4).integers(0, 3, S)
-
-    def comm(then=None):
-        def f(e):
-            e.loop_set_comm(SEED + 1, 0.3, max_age=3, compensate=True)
-            if then is not None:
-                then(e)
-        return f
-
-    def set_unset(e):
-        e.loop_set_maps(mb.maps(e.spec), np.arange(S) % 4)
-        e.loop_set_maps(None)
-
-    plain = _run(eng, init, K, how, order, comm())
+    plain = lc.off_is_off(POOL, eng, init, K, how, order, under=lambda e: e.loop_set_comm(SEED + 1, 0.3, max_age=3, compensate=True))
     assert not np.array_equal(plain["state"], _run(eng, init, K, how, order)["state"])  # the loss is felt
-    _same(plain, _run(eng, init, K, how, order, comm(lambda e: e.loop_set_maps([e.spec], np.zeros(S, int)))), "M = 1, the handle's own")
-    _same(plain, _run(eng, init, K, how, order, comm(lambda e: e.loop_set_maps([e.spec] * 3, mof3))), "M = 3 identical copies")
-    _same(plain, _run(eng, init, K, how, order, comm(set_unset)), "set, then unset")
 
 
 @pytest.mark.parametrize("disturbed", [False, True], ids=["exact", "noise+loss"])
@@ -127,37 +104,22 @@ def test_mixed_batch_equals_separate_handles(eng, maps, plain_engines, exchange,
     sub-batch on the stream ids of its rows.  The rows of D differ from what the plain engine on map A gives for the same scenarios."""
     S, K, V = S16, K6, eng.spec.n_nbr + 1
     table, k0, noise = _planned(eng, S)
-    mof = np.arange(S) % 4
     order = _orders(S, V, 11) if exchange == "sequential" else None
-
-    def settings(stream):
-        def f(e):
-            if disturbed:
-                e.loop_set_disturbance(SEED, stream=stream, **SIG)
-                e.loop_set_comm(SEED + 1, 0.3, max_age=3, compensate=True, stream=stream)
-        return f
-
-    def mixed_setup(e):
-        settings(np.arange(S))(e)
-        e.loop_set_maps(maps, mof)
-
-    for how in ("step", "run", (3, K - 3)):
-        mixed = _run(eng, (table, k0, noise), K, how, order, mixed_setup)
-        for m, pe in enumerate(plain_engines):
-            sel = np.flatnonzero(mof == m)
-            alone = _run(pe, (table, k0[sel], noise[sel]), K, how, None if order is None else order[sel], settings(sel))
-            _same(_rows(mixed, sel), alone, (how, mb.NAMES[m]))
-        sel = np.flatnonzero(mof == 3)
+    settings = lambda stream: lc.noise_and_loss(SIG, stream, SEED) if disturbed else None
+    sel = np.flatnonzero(np.arange(S) % 4 == 3)
+    for how, mixed in lc.mixed_batch_equals_separate_handles(POOL, eng, maps, plain_engines, (table, k0, noise), K, order, settings).items():
         on_a = _run(plain_engines[0], (table, k0[sel], noise[sel]), K, how, None if order is None else order[sel], settings(sel))
         assert not np.array_equal(mixed["state"][sel], on_a["state"]), (how, "the D rows equal the A engine's")
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
 def test_against_the_host_replay(eng, ospec, maps, exchange):
-    """3. S = 8, two scenarios per map (map_of[s] = s % 4), K = 8: the port replayed scenario by scenario with the scenario's own obstacles
+    """3. S = 8, two scenarios per map (map_of[s] = s % 4), K = 8: the port replayed with every scenario's own obstacles in its MpcSpec
     gives equal status and iterations solve for solve and states within 1e-6 (the tolerance of
     test_problem_pool_gpu.py::test_against_the_host_replay and test_disturbance_gpu.py::test_against_the_host_replay); at least one solve
     on map C ends with status 4 (the measured state inside the grown obstacles' clearance)."""
+    from oracle.closed_loop import replay
+
     S, K, V = 8, 8, eng.spec.n_nbr + 1
     table, k0, noise = _planned(eng, S)
     mof = np.arange(S) % 4
@@ -166,20 +128,13 @@ def test_against_the_host_replay(eng, ospec, maps, exchange):
     if order is not None:
         eng.loop_set_order(order)
     eng.loop_set_maps(maps, mof)
-    got = []
-    for _ in range(K):
-        eng.loop_step()
-        got.append(eng.loop_get())
-    ref = mb.replay_mixed(ospec, maps, mof, table, k0, noise, K, eng.spec.dt, eng.spec.wb, order=order)
-    worst = 0.0
+    got = lc.stepwise(eng, K)
+    osp = [mb.oracle_spec(ospec, maps[m]) for m in mof]
+    worst, _ = lc.against_replay(got, replay(osp, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, order=order))
     status = np.stack([g["status"] for g in got])
-    for t, (state, st, it) in enumerate(ref):
-        worst = max(worst, float(np.abs(got[t]["state"] - state).max()))
     conv = {mb.NAMES[m]: int((status[:, mof == m] == 0).sum()) for m in range(4)}
     print(f"{exchange}: max |state - replay| {worst:.2e}; converged solves of 64 per map {conv}; "
           f"map C: {int((status[:, mof == 2] == 4).sum())} solves with status 4")
-    for t, (state, st, it) in enumerate(ref):
-        assert np.array_equal(got[t]["status"], st) and np.array_equal(got[t]["iters"], it), t
     assert worst < 1e-6
     assert (status[:, mof == 2] == 4).any()
 
@@ -211,7 +166,7 @@ def test_maps_and_problems_together(eng, maps):
         pe = engine.Engine(scenarios.map_spec(pb.spec_of(p), *m), max_batch=4, **pb.options_of(p))
         alone = _run(pe, (table, k0[s : s + 1], noise[s : s + 1]), K, "run")
         pe.close()
-        _same(_rows(both, [s]), alone, (pb.NAMES[pof[s]], mb.NAMES[mof[s]]))
+        _same(lc.rows(both, [s]), alone, (pb.NAMES[pof[s]], mb.NAMES[mof[s]]))
     only_maps = _run(eng, (table, k0, noise), K, "run", None, lambda e: e.loop_set_maps(maps, mof))
     only_probs = _run(eng, (table, k0, noise), K, "run", None, lambda e: e.loop_set_problems(probs, pof))
     assert not np.array_equal(only_maps["state"], both["state"]) and not np.array_equal(only_probs["state"], both["state"])
@@ -231,25 +186,8 @@ def test_maps_and_problems_together(eng, maps):
 def test_mapping_changes_between_calls(eng, maps, exchange):
     """5. loop_run(3), another map_of, loop_run(3) equals the same sequence stepped, bit for bit; the change matters."""
     S, K, V = S16, K6, eng.spec.n_nbr + 1
-    init = _planned(eng, S)
     order = _orders(S, V, 11) if exchange == "sequential" else None
-    mof0, mof1 = np.arange(S) % 4, (np.arange(S) + 1) % 4
-    first = lambda e: e.loop_set_maps(maps, mof0)
-    ran = _run(eng, init, K, (3, 3), order, first, lambda e: e.loop_set_maps(maps, mof1))
-    eng.loop_init(*init)
-    if order is not None:
-        eng.loop_set_order(order)
-    first(eng)
-    eng.loop_record(K)
-    for t in range(K):
-        if t == 3:
-            eng.loop_set_maps(maps, mof1)
-        eng.loop_step()
-    stepped = eng.loop_get()
-    stepped.update({"rec_" + k: v for k, v in eng.loop_history().items()})
-    _same(ran, stepped, "run / remap / run against the same sequence stepped")
-    kept = _run(eng, init, K, (3, 3), order, first)
-    assert np.array_equal(kept["rec_traj"][:3], ran["rec_traj"][:3]) and not np.array_equal(kept["state"], ran["state"])
+    lc.mapping_changes_between_calls(POOL, eng, maps, _planned(eng, S), K, order)
 
 
 def test_audit_follows_the_map(eng, maps, plain_engines):
@@ -263,13 +201,13 @@ def test_audit_follows_the_map(eng, maps, plain_engines):
     mof = np.arange(S) % 4
     _run(eng, (table, k0, noise), K, "run", None, lambda e: e.loop_set_maps(maps, mof))
     traj = eng.loop_history()["traj"]
-    goals = _goals(table, S)
+    goals = lc.goals(table, S)
     a = eng.loop_audit(**TOL)
     assert np.isfinite(a["clear"]).all()
     _same(a, eng.audit(traj, goals, maps, mof, **TOL), "loop_audit against audit of the history on the same maps")
     for m, pe in enumerate(plain_engines):
         sel = np.flatnonzero(mof == m)
-        _same(_rows(a, sel), pe.audit(traj[:, sel], goals[sel], **TOL), ("the plain engine on map", mb.NAMES[m]))
+        _same(lc.rows(a, sel), pe.audit(traj[:, sel], goals[sel], **TOL), ("the plain engine on map", mb.NAMES[m]))
     for s in range(S):
         emu = ab.emu_audit(traj[:, s : s + 1], goals[s : s + 1], mb.vertices(*maps[mof[s]]), eng.spec.g, TOL["pos_tol"], TOL["psi_tol"], TOL["v_tol"])
         for k in ("where", "first_contact", "arrive"):
@@ -296,49 +234,31 @@ def test_refusals(eng, maps):
     from conflict_rez_amd import engine
 
     S, K = S16, 4
-    table, k0, noise = init = _planned(eng, S)
+    init = _planned(eng, S)
     mof = np.arange(S) % 4
     fresh = engine.Engine(eng.spec, max_batch=4)
     with pytest.raises(RuntimeError, match="cfz_loop_init has not been called"):
         fresh.loop_set_maps(maps, np.zeros(1, int))
     fresh.close()
-    eng.loop_init(*init)
-    eng.loop_set_maps(maps, mof)
-    eng.loop_run(2)
-    before = eng.loop_get()
     A, b = engine.pack_maps(eng.spec, maps)
     ptr = lambda x: x.ctypes.data_as(C.c_void_p)
-    assert eng.lib.cfz_loop_set_maps(eng._h, -1, ptr(A), ptr(b), ptr(mof.astype(np.int32))) != 0
-    assert b"M must not be negative" in eng.lib.cfz_last_error()
-    for bad in (np.where(mof == 3, 4, mof), np.where(mof == 0, -1, mof)):
+
+    def refused(eng):
+        assert eng.lib.cfz_loop_set_maps(eng._h, -1, ptr(A), ptr(b), ptr(mof.astype(np.int32))) != 0
+        assert b"M must not be negative" in eng.lib.cfz_last_error()
+        for bad in (np.where(mof == 3, 4, mof), np.where(mof == 0, -1, mof)):
+            with pytest.raises(RuntimeError, match="map_of"):
+                eng.loop_set_maps(maps, bad)
+        strip_A, strip_b = np.array(maps[1][0]), np.array(maps[1][1])
+        strip_A[2, 1:], strip_b[2, 1:] = strip_A[2, 0], strip_b[2, 0]  # obstacle 2: one row four times, a half-plane
+        nan_b = np.array(maps[2][1]); nan_b[5, 3] = np.nan
+        for pool, text in (([maps[0], (strip_A, strip_b)], "map 1: obstacle 2 is not a bounded quadrilateral"),
+                           ([maps[0], maps[1], (maps[2][0], nan_b)], "map 2: obstacle 5 has an entry that is not finite")):
+            with pytest.raises(RuntimeError, match=text):
+                eng.loop_set_maps(pool, np.zeros(S, int))
+            with pytest.raises(RuntimeError, match=text):
+                eng.audit(np.zeros((2, S, 4, 7)), np.zeros((S, 4, 3)), pool, np.zeros(S, int))
         with pytest.raises(RuntimeError, match="map_of"):
-            eng.loop_set_maps(maps, bad)
-    strip_A, strip_b = np.array(maps[1][0]), np.array(maps[1][1])
-    strip_A[2, 1:], strip_b[2, 1:] = strip_A[2, 0], strip_b[2, 0]  # obstacle 2: one row four times, a half-plane
-    nan_b = np.array(maps[2][1]); nan_b[5, 3] = np.nan
-    for pool, text in (([maps[0], (strip_A, strip_b)], "map 1: obstacle 2 is not a bounded quadrilateral"),
-                       ([maps[0], maps[1], (maps[2][0], nan_b)], "map 2: obstacle 5 has an entry that is not finite")):
-        with pytest.raises(RuntimeError, match=text):
-            eng.loop_set_maps(pool, np.zeros(S, int))
-        with pytest.raises(RuntimeError, match=text):
-            eng.audit(np.zeros((2, S, 4, 7)), np.zeros((S, 4, 3)), pool, np.zeros(S, int))
-    with pytest.raises(RuntimeError, match="map_of"):
-        eng.audit(np.zeros((2, S, 4, 7)), np.zeros((S, 4, 3)), maps, np.where(mof == 3, 4, mof))
-    after = eng.loop_get()
-    _same(before, after, "state after the refusals")
-    eng.loop_step()
-    eng.loop_run(K - 3)
-    end = eng.loop_get()
-    eng.loop_init(*init)
-    eng.loop_set_maps(maps, mof)
-    eng.loop_run(2)
-    eng.loop_step()
-    eng.loop_run(K - 3)
-    _same(end, eng.loop_get(), "the setting in force stayed")
-    # loop_init: off
-    eng.loop_init(*init)
-    eng.loop_run(K)
-    off = eng.loop_get()
-    assert not np.array_equal(off["state"], end["state"])
-    plain = _run(eng, init, K, "run")
-    _same(off, {k: plain[k] for k in off}, "loop_init switches the maps off")
+            eng.audit(np.zeros((2, S, 4, 7)), np.zeros((S, 4, 3)), maps, np.where(mof == 3, 4, mof))
+
+    lc.refusals_change_nothing(POOL, eng, maps, init, K, refused, rest=("step", K - 3))

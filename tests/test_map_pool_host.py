@@ -188,22 +188,22 @@ def test_the_maps_move_the_outcome_and_every_map_converges(spec, ospec):
 
     g.build()
     from conflict_rez_amd import scenarios
+    from oracle.closed_loop import replay
 
     S, K = 8, 8
     table, _ = scenarios.load_reference_table(kind="planned")
     k0, noise = scenarios.sample_scenarios(S, table, seed=2024, spec=spec)
     M = mb.maps(spec)
     map_of = np.arange(S) % 4
-    mixed = mb.replay_mixed(ospec, M, map_of, table, k0, noise, K, spec.dt, spec.wb)
+    mixed = list(replay([mb.oracle_spec(ospec, M[m]) for m in map_of], table, k0, noise, K, dt=spec.dt, wb=spec.wb))
     other = np.flatnonzero(map_of > 0)
-    base = mb.replay_mixed(ospec, M, np.zeros(S, int), table, k0, noise, K, spec.dt, spec.wb, scenarios_=other)
-    status = np.stack([st for _, st, _ in mixed])  # [K, S, V]
-    end, end0 = mixed[-1][0], base[-1][0]
-    for s in other:
-        gap = float(np.abs(end[s] - end0[s]).max())  # over the state (x, y, psi, v, delta) of the four vehicles
+    base = list(replay(mb.oracle_spec(ospec, M[0]), table, k0[other], noise[other], K, dt=spec.dt, wb=spec.wb))  # the others on map A
+    status = np.stack([st for _, _, st, _ in mixed])  # [K, S, V]
+    for s, e, e0 in zip(other, mixed[-1][0][other], base[-1][0]):  # final states [V, 5]
+        gap = float(np.abs(e - e0).max())  # over the state (x, y, psi, v, delta) of the four vehicles
         print(f"scenario {s} on map {mb.NAMES[map_of[s]]}: final states differ from map A's by {gap:.2e} (positions by "
-              f"{float(np.abs(end[s, :, :2] - end0[s, :, :2]).max()):.2e} m)")
-        assert not np.array_equal(end[s], end0[s]), s
+              f"{float(np.abs(e[:, :2] - e0[:, :2]).max()):.2e} m)")
+        assert not np.array_equal(e, e0), s
         assert gap > 1e-6, (s, gap)
     for m in range(4):
         conv = int((status[:, map_of == m] == 0).sum())

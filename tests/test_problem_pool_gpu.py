@@ -7,12 +7,14 @@ Geometry, time base and carry_duals stay the handle's.
 The four test problems (tests/problem_pool_binding.py) over the `parking_lot_spec()` handle, planned table, V = 4:
   A the handle's own | B dmin 0.2 | C v in [-1.8, 1.8], a in [-0.8, 0.8], w in [-0.5, 0.5] | D weights (20, 20, 50, 2, 2, 5), max_iter 5
 chosen under two conditions:
-  (i)  the problem moves the outcome: replayed on the host scenario by scenario (oracle/closed_loop.replay with the scenario's own MpcSpec
+  (i)  the problem moves the outcome: replayed on the host (oracle/closed_loop.replay with every scenario's own MpcSpec
        and options), every scenario of B, C and D of the batches below ends in other final states than under problem A (checked on the host
        before the first GPU run: the smallest difference is 8e-6 m, scenario 9 of the 16, the others 5e-3 .. 0.5 m; in the batch of 8,
        3.5e-6 m for scenario 1 under B, the others 7e-3 .. 0.5 m);
   (ii) a plain handle created with the problem's constants agrees with the host replay in status and iterations: that is
        test_mixed_batch_equals_separate_handles (plain handles equal the mixed rows bit for bit) together with test_against_the_host_replay.
+
+What every per-scenario pool has is tests/loop_cases.py's, written against `POOL`; here: the numbered statement, that call, what is special.
 """
 import os
 import sys
@@ -25,11 +27,22 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import disturbance_binding as db  # noqa: E402
 import problem_pool_binding as pb  # noqa: E402
+import loop_cases as lc  # noqa: E402
 from loop_cases import orders as _orders, planned as _planned, run as _run, same as _same  # noqa: E402
 
 SIG = db.SIGMA
 SEED = 2024
 S16, K6 = 16, 6
+
+
+def _plain(spec, p, max_batch):
+    from conflict_rez_amd import engine
+
+    return engine.Engine(pb.spec_of(p), max_batch=max_batch, **pb.options_of(p))
+
+
+POOL = lc.Pool(set=lambda e, probs, problem_of: e.loop_set_problems(probs, problem_of), off=lambda e: e.loop_set_problems(None),
+               own=lambda e: e.spec, entries=pb.problems, plain=_plain, names=pb.NAMES)
 
 
 @pytest.fixture(scope="module")
@@ -52,16 +65,10 @@ def probs(eng):
 @pytest.fixture(scope="module")
 def plain_engines(eng, probs):
     """One plain engine per problem, created with that problem's spec and options: the parent's code path."""
-    from conflict_rez_amd import engine
-
-    es = [engine.Engine(pb.spec_of(p), max_batch=S16 * 4, **pb.options_of(p)) for p in probs]
+    es = [POOL.plain(eng.spec, p, S16 * 4) for p in probs]
     yield es
     for e in es:
         e.close()
-
-
-def _rows(a, rows):
-    return {k: (v[:, rows] if k.startswith("rec_") else v[rows]) for k, v in a.items()}
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
@@ -70,20 +77,9 @@ def test_off_is_off(eng, how, exchange):
     """1. No call, P = 1 with the handle's own problem, P = 3 identical copies under a random problem_of, and set-then-unset give equal
     state, prediction, status, iterations and record, bit for bit.  S = 16, K = 6."""
     S, K, V = S16, K6, eng.spec.n_nbr + 1
-    init = _planned(eng, S)
     order = _orders(S, V, 11) if exchange == "sequential" else None
-    pof3 = np.random.default_rng(4).integers(0, 3, S)
-    assert len(set(pof3)) == 3
-
-    def set_unset(e):
-        e.loop_set_problems(pb.problems(e.spec), np.arange(S) % 4)
-        e.loop_set_problems(None)
-
-    plain = _run(eng, init, K, how, order)
+    plain = lc.off_is_off(POOL, eng, _planned(eng, S), K, how, order)
     assert (plain["rec_status"] == 0).mean() > 0.5
-    _same(plain, _run(eng, init, K, how, order, lambda e: e.loop_set_problems([e.spec], np.zeros(S, int))), "P = 1, the handle's own")
-    _same(plain, _run(eng, init, K, how, order, lambda e: e.loop_set_problems([e.spec] * 3, pof3)), "P = 3 identical copies")
-    _same(plain, _run(eng, init, K, how, order, set_unset), "set, then unset")
 
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
@@ -95,19 +91,8 @@ def test_off_is_off_under_a_lossy_exchange(eng, how, exchange):
     S, K, V = S16, K6, eng.spec.n_nbr + 1
     init = _planned(eng, S)
     order = _orders(S, V, 11) if exchange == "sequential" else None
-    pof3 = np.random.default_rng(4).integers(0, 3, S)
-
-    def comm(then=None):
-        def f(e):
-            e.loop_set_comm(SEED + 1, 0.3, max_age=3, compensate=True)
-            if then is not None:
-                then(e)
-        return f
-
-    plain = _run(eng, init, K, how, order, comm())
+    plain = lc.off_is_off(POOL, eng, init, K, how, order, under=lambda e: e.loop_set_comm(SEED + 1, 0.3, max_age=3, compensate=True))
     assert not np.array_equal(plain["state"], _run(eng, init, K, how, order)["state"])  # the loss is felt
-    _same(plain, _run(eng, init, K, how, order, comm(lambda e: e.loop_set_problems([e.spec], np.zeros(S, int)))), "P = 1, the handle's own")
-    _same(plain, _run(eng, init, K, how, order, comm(lambda e: e.loop_set_problems([e.spec] * 3, pof3))), "P = 3 identical copies")
 
 
 @pytest.mark.parametrize("disturbed", [False, True], ids=["exact", "noise+loss"])
@@ -117,28 +102,14 @@ def test_mixed_batch_equals_separate_handles(eng, probs, plain_engines, exchange
     a plain engine created with p's spec and options gives for p's four scenarios alone; once more under noise and a lossy exchange
     (p_drop 0.3) with the sub-batch on the stream ids of its rows.  The rows of B, C and D differ from a plain run of the whole batch."""
     S, K, V = S16, K6, eng.spec.n_nbr + 1
-    table, k0, noise = _planned(eng, S)
+    init = _planned(eng, S)
     pof = np.arange(S) % 4
     order = _orders(S, V, 11) if exchange == "sequential" else None
-
-    def settings(stream):
-        def f(e):
-            if disturbed:
-                e.loop_set_disturbance(SEED, stream=stream, **SIG)
-                e.loop_set_comm(SEED + 1, 0.3, max_age=3, compensate=True, stream=stream)
-        return f
-
-    def mixed_setup(e):
-        settings(np.arange(S))(e)
-        e.loop_set_problems(probs, pof)
-
-    whole = _run(eng, (table, k0, noise), K, "run", order, settings(np.arange(S)))
-    for how in ("step", "run", (3, K - 3)):
-        mixed = _run(eng, (table, k0, noise), K, how, order, mixed_setup)
-        for p, pe in enumerate(plain_engines):
+    settings = lambda stream: lc.noise_and_loss(SIG, stream, SEED) if disturbed else None
+    whole = _run(eng, init, K, "run", order, settings(np.arange(S)))
+    for how, mixed in lc.mixed_batch_equals_separate_handles(POOL, eng, probs, plain_engines, init, K, order, settings).items():
+        for p in range(4):
             sel = np.flatnonzero(pof == p)
-            alone = _run(pe, (table, k0[sel], noise[sel]), K, how, None if order is None else order[sel], settings(sel))
-            _same(_rows(mixed, sel), alone, (how, pb.NAMES[p]))
             differs = not np.array_equal(mixed["state"][sel], whole["state"][sel])
             assert differs == (p > 0), (how, pb.NAMES[p])
             if p > 0:  # every scenario of the problem, not just one of them
@@ -147,12 +118,14 @@ def test_mixed_batch_equals_separate_handles(eng, probs, plain_engines, exchange
 
 @pytest.mark.parametrize("exchange", ["jacobi", "sequential"])
 def test_against_the_host_replay(eng, ospec, probs, exchange):
-    """3. S = 8, two scenarios per problem, K = 8: the port replayed scenario by scenario with the scenario's own MpcSpec and options gives
+    """3. S = 8, two scenarios per problem, K = 8: the port replayed with every scenario's own MpcSpec and options gives
     equal status and iterations solve for solve and states within 1e-6 (the tolerance of test_pool_matches_oracle_replay and
     test_disturbance_gpu.py::test_against_the_host_replay); at least one solve of problem D ends with status 1.
     problem_of[s] = s % 4, chosen on the host replay alone: every problem then has converged and failed solves among its 64 (status 4 and
     5; status 2 under A; status 1 under D), C 55 converged.  With problem_of[s] = s // 2 both starts
     of C are faster than C's speed box allows and none of its 64 solves converges, which compares statuses and fallbacks only."""
+    from oracle.closed_loop import replay
+
     S, K, V = 8, 8, eng.spec.n_nbr + 1
     table, k0, noise = _planned(eng, S)
     pof = np.arange(S) % 4
@@ -161,20 +134,13 @@ def test_against_the_host_replay(eng, ospec, probs, exchange):
     if order is not None:
         eng.loop_set_order(order)
     eng.loop_set_problems(probs, pof)
-    got = []
-    for _ in range(K):
-        eng.loop_step()
-        got.append(eng.loop_get())
-    ref = pb.replay_mixed(ospec, probs, pof, table, k0, noise, K, eng.spec.dt, eng.spec.wb, order=order)
-    worst = 0.0
+    got = lc.stepwise(eng, K)
+    osp, opt = zip(*(pb.oracle_problem(ospec, probs[p]) for p in pof))
+    worst, _ = lc.against_replay(got, replay(osp, table, k0, noise, K, dt=eng.spec.dt, wb=eng.spec.wb, opt=opt, order=order))
     status = np.stack([g["status"] for g in got])
-    for t, (state, st, it) in enumerate(ref):
-        worst = max(worst, float(np.abs(got[t]["state"] - state).max()))
     conv = {pb.NAMES[p]: float((status[:, pof == p] == 0).mean()) for p in range(4)}
     print(f"{exchange}: max |state - replay| {worst:.2e}; converged share per problem {conv}; "
           f"problem D: {int((status[:, pof == 3] == 1).sum())} solves at the iteration limit")
-    for t, (state, st, it) in enumerate(ref):
-        assert np.array_equal(got[t]["status"], st) and np.array_equal(got[t]["iters"], it), t
     assert worst < 1e-6
     assert (status[:, pof == 3] == 1).any()
 
@@ -183,25 +149,8 @@ def test_against_the_host_replay(eng, ospec, probs, exchange):
 def test_mapping_changes_between_calls(eng, probs, exchange):
     """4. loop_run(3), another problem_of, loop_run(3) equals the same sequence stepped, bit for bit; the change matters."""
     S, K, V = S16, K6, eng.spec.n_nbr + 1
-    init = _planned(eng, S)
     order = _orders(S, V, 11) if exchange == "sequential" else None
-    pof0, pof1 = np.arange(S) % 4, (np.arange(S) + 1) % 4
-    first = lambda e: e.loop_set_problems(probs, pof0)
-    ran = _run(eng, init, K, (3, 3), order, first, lambda e: e.loop_set_problems(probs, pof1))
-    eng.loop_init(*init)
-    if order is not None:
-        eng.loop_set_order(order)
-    first(eng)
-    eng.loop_record(K)
-    for t in range(K):
-        if t == 3:
-            eng.loop_set_problems(probs, pof1)
-        eng.loop_step()
-    stepped = eng.loop_get()
-    stepped.update({"rec_" + k: v for k, v in eng.loop_history().items()})
-    _same(ran, stepped, "run / remap / run against the same sequence stepped")
-    kept = _run(eng, init, K, (3, 3), order, first)
-    assert np.array_equal(kept["rec_traj"][:3], ran["rec_traj"][:3]) and not np.array_equal(kept["state"], ran["state"])
+    lc.mapping_changes_between_calls(POOL, eng, probs, _planned(eng, S), K, order)
 
 
 @pytest.mark.parametrize("how", ["step", "run"])
@@ -234,7 +183,7 @@ def test_audit_and_record_under_a_pool(eng, probs, plain_engines):
     table, k0, noise = _planned(eng, S)
     _run(eng, (table, k0, noise), K, "run", None, lambda e: e.loop_set_problems(probs, np.arange(S) % 4))
     traj = eng.loop_history()["traj"]
-    goals = np.broadcast_to(table[:, -1, :3], (S,) + table[:, -1, :3].shape).copy()
+    goals = lc.goals(table, S)
     a = eng.loop_audit()
     _same(a, eng.audit(traj, goals), "loop_audit against audit of the history")
     eng.loop_set_problems([probs[1]], np.zeros(S, int))
@@ -260,36 +209,23 @@ def test_refusals(eng, probs):
     with pytest.raises(RuntimeError, match="cfz_loop_init has not been called"):
         fresh.loop_set_problems(probs, pof)
     fresh.close()
-    eng.loop_init(*init)
-    eng.loop_set_problems(probs, pof)
-    eng.loop_run(2)
-    before = eng.loop_get()
     _, specs, opts = engine.pack_problems(probs)
-    assert eng.lib.cfz_loop_set_problems(eng._h, -1, specs, opts, pof.astype(np.int32).ctypes.data_as(C.c_void_p)) != 0
-    assert b"P must not be negative" in eng.lib.cfz_last_error()
-    for bad in (np.where(pof == 3, 4, pof), np.where(pof == 0, -1, pof)):
-        with pytest.raises(RuntimeError, match="problem_of"):
-            eng.loop_set_problems(probs, bad)
-    A2, b2, g2 = np.array(sp.A_obs), np.array(sp.b_obs), np.array(sp.g)
-    b2[2, 1] += 0.25
-    g2[0] += 0.1
-    lo_hi = np.array(sp.bounds, float); lo_hi[8], lo_hi[9] = 0.5, -0.5
-    for entry, text in ((dataclasses.replace(sp, N=sp.N - 2), " N"), (dataclasses.replace(sp, A_obs=A2[:5], b_obs=np.array(sp.b_obs)[:5]), "n_obs"),
-                        (dataclasses.replace(sp, b_obs=b2), r"b_obs\[2\]"), (dataclasses.replace(sp, g=g2), " g"),
-                        (dataclasses.replace(sp, dt=0.2), " dt"), (dataclasses.replace(sp, wb=2.6), " wb"), ((sp, dict(carry_duals=0)), "carry_duals"),
-                        (dataclasses.replace(sp, bounds=lo_hi), "lo > hi")):
-        with pytest.raises(RuntimeError, match="problem 1: .*" + text):
-            eng.loop_set_problems([sp, entry], np.zeros(S, int))
-    after = eng.loop_get()
-    _same(before, after, "state after the refusals")
-    eng.loop_run(K - 2)
-    end = eng.loop_get()
-    ref = _run(eng, init, K, "run", None, lambda e: e.loop_set_problems(probs, pof))
-    _same(end, {k: ref[k] for k in end}, "the setting in force stayed")
-    # loop_init: off
-    eng.loop_init(*init)
-    eng.loop_run(K)
-    off = eng.loop_get()
-    assert not np.array_equal(off["state"], end["state"])
-    plain = _run(eng, init, K, "run")
-    _same(off, {k: plain[k] for k in off}, "loop_init switches the pool off")
+
+    def refused(eng):
+        assert eng.lib.cfz_loop_set_problems(eng._h, -1, specs, opts, pof.astype(np.int32).ctypes.data_as(C.c_void_p)) != 0
+        assert b"P must not be negative" in eng.lib.cfz_last_error()
+        for bad in (np.where(pof == 3, 4, pof), np.where(pof == 0, -1, pof)):
+            with pytest.raises(RuntimeError, match="problem_of"):
+                eng.loop_set_problems(probs, bad)
+        A2, b2, g2 = np.array(sp.A_obs), np.array(sp.b_obs), np.array(sp.g)
+        b2[2, 1] += 0.25
+        g2[0] += 0.1
+        lo_hi = np.array(sp.bounds, float); lo_hi[8], lo_hi[9] = 0.5, -0.5
+        for entry, text in ((dataclasses.replace(sp, N=sp.N - 2), " N"), (dataclasses.replace(sp, A_obs=A2[:5], b_obs=np.array(sp.b_obs)[:5]), "n_obs"),
+                            (dataclasses.replace(sp, b_obs=b2), r"b_obs\[2\]"), (dataclasses.replace(sp, g=g2), " g"),
+                            (dataclasses.replace(sp, dt=0.2), " dt"), (dataclasses.replace(sp, wb=2.6), " wb"), ((sp, dict(carry_duals=0)), "carry_duals"),
+                            (dataclasses.replace(sp, bounds=lo_hi), "lo > hi")):
+            with pytest.raises(RuntimeError, match="problem 1: .*" + text):
+                eng.loop_set_problems([sp, entry], np.zeros(S, int))
+
+    lc.refusals_change_nothing(POOL, eng, probs, init, K, refused, rest=(K - 2,))

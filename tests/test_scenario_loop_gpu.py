@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import audit_binding as ab  # noqa: E402
+from loop_cases import against_replay, stepwise as _stepwise  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = dict(pos_tol=0.3, psi_tol=0.1, v_tol=0.1)
@@ -71,14 +72,6 @@ def _three_tables():
     tabs = [ws, pl, pl[:, 20:]]
     T = max(t.shape[1] for t in tabs)
     return tabs, np.stack([_hold(t, T) for t in tabs])
-
-
-def _stepwise(e, K):
-    out = []
-    for _ in range(K):
-        e.loop_step()
-        out.append(e.loop_get())
-    return out
 
 
 def test_pool_of_one_equals_loop_init(eng):
@@ -173,11 +166,8 @@ def test_pool_matches_oracle_replay(eng, ospec):
     k0, noise = scenarios.sample_scenarios(S, tabs[2], seed=3)
     eng.loop_init(pool, k0, noise, table_of=tof)
     got = _stepwise(eng, steps)
-    for s in range(S):
-        rep = list(replay(ospec, tabs[tof[s]], k0[s : s + 1], noise[s : s + 1], steps, dt=eng.spec.dt, wb=eng.spec.wb))
-        for t, (state, pred, status, iters) in enumerate(rep):
-            assert np.array_equal(got[t]["status"][s], status[0]) and np.array_equal(got[t]["iters"][s], iters[0]), (s, t)
-            assert np.abs(got[t]["state"][s] - state[0]).max() < 1e-6, (s, t)
+    worst, _ = against_replay(got, replay(ospec, pool, k0, noise, steps, dt=eng.spec.dt, wb=eng.spec.wb, table_of=tof))
+    assert worst < 1e-6
 
 
 def test_record(eng):
