@@ -41,12 +41,6 @@
 #define CFZC_PIECE inline
 #endif
 
-#ifndef CFZC_NO_EASE
-#define CFZC_NO_EASE 0  // experiments: 1 = mu falls only when the barrier problem's own test passes
-#endif
-#ifndef CFZC_VV_TANGENTIAL
-#define CFZC_VV_TANGENTIAL 1.0
-#endif
 namespace cfzc {
 
 // Dual regularisation of proximal type: the constraint rows of the Newton system read  J dx - delta_c (nu + dnu) = -c
@@ -194,6 +188,9 @@ CFZP_FN int veh_of_chk(const CDims &d, int T) { int a = 0; while (a + 1 < d.V &&
 // half-bandwidth of the ordering of build_order: the 30 ODE rows of an interval sit between its third and fourth point
 constexpr int kCB = 51;  // half-bandwidth of the single-vehicle plan's ordering
 constexpr int kWideMaxKb = 448;  // widest half-bandwidth the eight-wavefront eliminations are compiled for (the host sizes LDS with it)
+// pivots per panel of those eliminations (four-vehicle plan: 8 is 7 % slower, 32 is 14 % slower: every pivot step carries 32-wide rows;
+// the host sizes LDS with it)
+constexpr int kPanel = 16;
 // point of tube checkpoint T (global index): start of interval (t+1) Nps of its vehicle, or the vehicle's very last point
 CFZP_FN int chk_point(const CSpec &sp, const CDims &d, int T) {
   const int a = veh_of_chk(d, T), t = T - d.coff[a];
@@ -241,7 +238,7 @@ CFZP_FN double pair_row(const double *pa, const double *pb, const double g[4], i
       const double nda = -n0 * ray + n1 * rax, ndb = -n0 * rby + n1 * rbx, tda = n1 * ray + n0 * rax, tdb = n1 * rby + n0 * rbx;
       gr[0] = n0; gr[1] = n1; gr[2] = nda; gr[3] = -n0; gr[4] = -n1; gr[5] = -ndb;
       const double tau[6] = {-n1, n0, tda, n1, -n0, -tdb};
-      for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) H[i][j] = CFZC_VV_TANGENTIAL * tau[i] * tau[j] * ir;
+      for (int i = 0; i < 6; ++i) for (int j = 0; j < 6; ++j) H[i][j] = tau[i] * tau[j] * ir;
       H[2][2] -= n0 * rax + n1 * ray;
       H[5][5] += n0 * rbx + n1 * rby;
     }
@@ -665,7 +662,7 @@ CFZC_PIECE double assemble(const CSpec &sp, const CWork &w, const Band &Bd, doub
         if ((sl >> 6) == 3) {
           const double bx = (vtx == 0 || vtx == 3) ? sp.g[0] : -sp.g[2], by = (vtx < 2) ? sp.g[1] : -sp.g[3];
           const double rbx = cs * bx - sn * by, rby = sn * bx + cs * by, a0 = gr[rr][0], a1 = gr[rr][1];
-          const double nq = CFZC_VV_TANGENTIAL * nr_ / sep[0], t2 = a1 * rby + a0 * rbx;
+          const double nq = nr_ / sep[0], t2 = a1 * rby + a0 * rbx;
           dg[0] += nq * a1 * a1; dg[1] += nq * a0 * a0; p01 += -nq * a1 * a0;
           p02 += -nq * a1 * t2; p12 += nq * a0 * t2;
           dg[2] += nq * t2 * t2 - nr_ * (a0 * rbx + a1 * rby);
@@ -735,7 +732,7 @@ CFZC_PIECE double assemble(const CSpec &sp, const CWork &w, const Band &Bd, doub
         if ((sl >> 6) == 3) {  // distance r of two vertices, n = (a0,a1): tau tau' / r - n.(R b_v) e_psi e_psi', tau = (-a1, a0, t.dw)
           const double bx = (vtx == 0 || vtx == 3) ? sp.g[0] : -sp.g[2], by = (vtx < 2) ? sp.g[1] : -sp.g[3];
           const double rbx = cs * bx - sn * by, rby = sn * bx + cs * by, a0 = gr[rr][0], a1 = gr[rr][1];
-          const double nq = CFZC_VV_TANGENTIAL * nr_ / sep[0], t2 = a1 * rby + a0 * rbx;  // sep[0] = r (the second slot's value carries the margin)
+          const double nq = nr_ / sep[0], t2 = a1 * rby + a0 * rbx;  // sep[0] = r (the second slot's value carries the margin)
           bnd(Bd, px[b], px[b]) += nq * a1 * a1; bnd(Bd, px[b + 1], px[b + 1]) += nq * a0 * a0; put(Bd, px[b], px[b + 1], -nq * a1 * a0);
           put(Bd, px[b], px[b + 2], -nq * a1 * t2); put(Bd, px[b + 1], px[b + 2], nq * a0 * t2);
           bnd(Bd, px[b + 2], px[b + 2]) += nq * t2 * t2 - nr_ * (a0 * rbx + a1 * rby);
@@ -1293,25 +1290,16 @@ __device__ __attribute__((noinline)) int band_factor_panel_core(glb_f64 *ab, int
   return 0;
 }
 
-#ifndef CFZ_PANEL
-#define CFZ_PANEL 16  // pivots per panel (four-vehicle plan: 8 is 7 % slower, 32 is 14 % slower: every pivot step carries 32-wide rows)
-#endif
-#ifndef CFZ_NO_PANEL
-#define CFZ_NO_PANEL 0
-#endif
-#ifndef CFZ_FORCE_SBIG
-#define CFZ_FORCE_SBIG 0  // diagnostic builds: the wide-register instantiation (kb > 304) whatever kb is; passes the planning GPU tests
-#endif
 // lds: the kernel's dynamic LDS (free during the elimination; the substitution keeps its right-hand side there)
 __device__ inline int band_factor_panel(const Band &B, int n, int *ipiv, long long *ptk, double *lds, double *b1, double *b2) {
-  __shared__ double pb[16 + 18 * (CFZ_PANEL + 1)], tks[3];
-  __shared__ int pj[64], meta[3 * CFZ_PANEL + 4], ext[1024];
+  __shared__ double pb[16 + 18 * (kPanel + 1)], tks[3];
+  __shared__ int pj[64], meta[3 * kPanel + 4], ext[1024];
   if (threadIdx.x == 0) { tks[0] = 0.0; tks[1] = 0.0; tks[2] = 0.0; }
   __syncthreads();
-  constexpr int SBIG = (kWideMaxKb + CFZ_PANEL + 63) / 64;
-  const int fail = (B.kb + CFZ_PANEL <= 320 && !CFZ_FORCE_SBIG)
-      ? band_factor_panel_core<CFZ_PANEL, 5>((glb_f64 *)B.ab, B.kb, B.ld, n, (glb_i32 *)ipiv, cfzb::opaque((lds_f64 *)lds), cfzb::opaque((lds_f64 *)pb), cfzb::opaque((lds_i32 *)pj), cfzb::opaque((lds_i32 *)meta), cfzb::opaque((lds_i32 *)ext), cfzb::opaque((lds_f64 *)tks), (glb_f64 *)b1, (glb_f64 *)b2)
-      : band_factor_panel_core<CFZ_PANEL, SBIG>((glb_f64 *)B.ab, B.kb, B.ld, n, (glb_i32 *)ipiv, cfzb::opaque((lds_f64 *)lds), cfzb::opaque((lds_f64 *)pb), cfzb::opaque((lds_i32 *)pj), cfzb::opaque((lds_i32 *)meta), cfzb::opaque((lds_i32 *)ext), cfzb::opaque((lds_f64 *)tks), (glb_f64 *)b1, (glb_f64 *)b2);
+  constexpr int SBIG = (kWideMaxKb + kPanel + 63) / 64;
+  const int fail = B.kb + kPanel <= 320
+      ? band_factor_panel_core<kPanel, 5>((glb_f64 *)B.ab, B.kb, B.ld, n, (glb_i32 *)ipiv, cfzb::opaque((lds_f64 *)lds), cfzb::opaque((lds_f64 *)pb), cfzb::opaque((lds_i32 *)pj), cfzb::opaque((lds_i32 *)meta), cfzb::opaque((lds_i32 *)ext), cfzb::opaque((lds_f64 *)tks), (glb_f64 *)b1, (glb_f64 *)b2)
+      : band_factor_panel_core<kPanel, SBIG>((glb_f64 *)B.ab, B.kb, B.ld, n, (glb_i32 *)ipiv, cfzb::opaque((lds_f64 *)lds), cfzb::opaque((lds_f64 *)pb), cfzb::opaque((lds_i32 *)pj), cfzb::opaque((lds_i32 *)meta), cfzb::opaque((lds_i32 *)ext), cfzb::opaque((lds_f64 *)tks), (glb_f64 *)b1, (glb_f64 *)b2);
   __syncthreads();
   for (int i = 0; i < 3; ++i) ptk[i] += (long long)tks[i];
   return fail;
@@ -1764,7 +1752,7 @@ CFZP_FN void solve_colloc(const CSpec &sp, double *X, double *slab, int kb, int 
         // termination, so it falls now instead of after the barrier problem's own, tighter, test (kappa_eps mu < tol at the last two
         // levels of a tol = 1e-2 solve).  Measured on the 254-plan launch of configs[3]: a plan at err 3e-3 after 28 iterations spent
         // 120 more at mu = 1.5e-4 driving the dual infeasibility from 3e-3 to 1.5e-3 through inertia corrections.
-        if (!CFZC_NO_EASE && !mu_eased && fmax(dual_inf / s_d, cviol) <= sp.tol && dual_inf <= sp.dual_inf_tol && cviol <= sp.constr_viol_tol && cmp0 > sp.compl_inf_tol) {
+        if (!mu_eased && fmax(dual_inf / s_d, cviol) <= sp.tol && dual_inf <= sp.dual_inf_tol && cviol <= sp.constr_viol_tol && cmp0 > sp.compl_inf_tol) {
           mu = fmax(mu_floor, fmin(sp.kappa_mu * mu, pow(mu, sp.theta_mu))); mu_eased = true;
         }
         break;
@@ -1804,7 +1792,7 @@ CFZP_FN void solve_colloc(const CSpec &sp, double *X, double *slab, int kb, int 
       if (jstructured) { fail = jstruct_solve(sp, d, w, JW, Bd, w.rhs, w.rhs2, tk + 6, nullptr); solved = true; } else
 #endif
 #if defined(__HIP_DEVICE_COMPILE__)
-      if (MODE == 2 && blockDim.x >= 512 && blockDim.x >= kb + CFZ_PANEL && kb <= kWideMaxKb && CFZ_PANEL * (kb + CFZ_PANEL) <= lds_doubles && !CFZ_NO_PANEL && !(sp.no_prox & 2)) {
+      if (MODE == 2 && blockDim.x >= 512 && blockDim.x >= kb + kPanel && kb <= kWideMaxKb && kPanel * (kb + kPanel) <= lds_doubles && !(sp.no_prox & 2)) {
         extern __shared__ double wlds[];
         fail = band_factor_panel(Bd, d.nk, w.ipiv, tk + 6, wlds, w.rhs, w.rhs2);
         fwd_done = true;

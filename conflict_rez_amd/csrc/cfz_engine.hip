@@ -67,11 +67,9 @@ struct DualPtrs { double *l, *m, *lam_ij, *lam_ji, *s; };
 // (scalar loads, scalar cache) instead of holding all ~200 of them in scalar registers from the kernel's first instruction
 struct KArgs { cfz::KSpec sp; cfz::KDer dv; cfz::Lay L; };
 
-#ifndef CFZ_WAVES_PER_SIMD
-#define CFZ_WAVES_PER_SIMD 2
-#endif
+constexpr int kWavesPerSimd = 2;  // the second argument of every solver kernel's launch bound
 // Two kernels, one body (cfz_solve_body.inl, included into both, as the persistent kernels share cfz_loop_body.inl).
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(const KArgs *__restrict__ ka, int B, const double *x0,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void solve_kernel(const KArgs *__restrict__ ka, int B, const double *x0,
                                                    const double *ref, const double *nbr, double *zu, int32_t *status,
                                                    int32_t *iters, double *stats, DualPtrs du, const int32_t *order,
                                                    double *wst, int wst_stride, const int32_t *carry, int carry_all,
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel(con
 // solve_kernel for the stepwise closed loop under cfz_loop_set_problems: instance b = (scenario s, vehicle) of V solves the problem
 // pool[problem_of[s]] (its spec and derived constants; the layout is the handle's, ka->L).  The index depends on the workgroup alone,
 // so the block is read through scalar loads as ka is.  A kernel of its own: solve_kernel keeps its code.
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void solve_kernel_pool(const KArgs *__restrict__ ka, int B, const double *x0,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void solve_kernel_pool(const KArgs *__restrict__ ka, int B, const double *x0,
                                                    const double *ref, const double *nbr, double *zu, int32_t *status,
                                                    int32_t *iters, double *stats, DualPtrs du, const int32_t *order,
                                                    double *wst, int wst_stride, const int32_t *carry, int carry_all,
@@ -292,7 +290,7 @@ __device__ long long *cfz_loop_trace_buf;
                       const int32_t *kidx0, int t_base, double *pred, double *state, double *scratch, int32_t *qbuf, int32_t *ctrl,       \
                       int32_t *done, int32_t *status, int32_t *iters, double *stats, int32_t *iter_sum, double *wst, int wst_stride,     \
                       int prio_lag, int prio_tail, double *rec, int32_t *rec_si
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(CFZ_LOOP_ARGS) {
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel(CFZ_LOOP_ARGS) {
   constexpr bool kSeq = false, kDist = false, kComm = false, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
@@ -302,7 +300,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel(CFZ_
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank) {
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_seq(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank) {
   constexpr bool kSeq = true, kDist = false, kComm = false, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
@@ -314,7 +312,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq(
 // The two kernels above with the disturbances of cfz_loop_set_disturbance (kDist): dz is the setting, step0 the MPC iterations done
 // since cfz_loop_init* (iteration t of this launch is step step0 + t of the streams).  Kernels of their own, made as loop_kernel_seq
 // was, so that the two undisturbed kernels keep the code they had before disturbances existed.
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_dist(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0) {
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_dist(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0) {
   constexpr bool kSeq = false, kDist = true, kComm = false, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
   const cfz::CommArgs cm = cfz::comm_none();
@@ -322,7 +320,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_dist
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_dist(CFZ_LOOP_ARGS, const int32_t *xperm,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_seq_dist(CFZ_LOOP_ARGS, const int32_t *xperm,
                                                                  const int32_t *xrank, cfz::DisturbArgs dz, int step0) {
   constexpr bool kSeq = true, kDist = true, kComm = false, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
@@ -335,7 +333,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
 // without further variants; with no noise set, dz is an all-zero sigma, which is bit-neutral.  Kernels of their own again: the
 // four above keep their code.  The release / acquire edges are those of the kernels above: the older slots a reader may take were
 // published by earlier iterations of the same scenario, which the chain of edges to this item covers.
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_comm(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_comm(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0,
                                                              cfz::CommArgs cm) {
   constexpr bool kSeq = false, kDist = true, kComm = true, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
@@ -343,7 +341,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_comm
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_comm(CFZ_LOOP_ARGS, const int32_t *xperm,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_seq_comm(CFZ_LOOP_ARGS, const int32_t *xperm,
                                                                  const int32_t *xrank, cfz::DisturbArgs dz, int step0, cfz::CommArgs cm) {
   constexpr bool kSeq = true, kDist = true, kComm = true, kPool = false;
   const KArgs *const pool = nullptr; const int32_t *const problem_of = nullptr; constexpr bool dz_clip = true;
@@ -356,7 +354,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
 // an all-zero sigma, which is bit-neutral once the clip of the applied input is left out as well (dz_clip 0: the undisturbed loop clips
 // nothing, and a prediction seeded from the plan may lie outside a problem's tighter input box).  Kernels of their own once more: the
 // six above keep their code.
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_pool(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_pool(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0,
                                                              const KArgs *__restrict__ pool, const int32_t *__restrict__ problem_of, int dz_clip) {
   constexpr bool kSeq = false, kDist = true, kComm = false, kPool = true;
   const cfz::CommArgs cm = cfz::comm_none();
@@ -364,7 +362,7 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_pool
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_pool(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_seq_pool(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank,
                                                                  cfz::DisturbArgs dz, int step0, const KArgs *__restrict__ pool,
                                                                  const int32_t *__restrict__ problem_of, int dz_clip) {
   constexpr bool kSeq = true, kDist = true, kComm = false, kPool = true;
@@ -372,14 +370,14 @@ __global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_pool_comm(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0, cfz::CommArgs cm,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_pool_comm(CFZ_LOOP_ARGS, cfz::DisturbArgs dz, int step0, cfz::CommArgs cm,
                                                                   const KArgs *__restrict__ pool, const int32_t *__restrict__ problem_of, int dz_clip) {
   constexpr bool kSeq = false, kDist = true, kComm = true, kPool = true;
   const int32_t *const xperm = nullptr, *const xrank = nullptr;
 #include "cfz_loop_body.inl"
 }
 
-__global__ __launch_bounds__(cfz::kNL, CFZ_WAVES_PER_SIMD) void loop_kernel_seq_pool_comm(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank,
+__global__ __launch_bounds__(cfz::kNL, kWavesPerSimd) void loop_kernel_seq_pool_comm(CFZ_LOOP_ARGS, const int32_t *xperm, const int32_t *xrank,
                                                                       cfz::DisturbArgs dz, int step0, cfz::CommArgs cm,
                                                                       const KArgs *__restrict__ pool, const int32_t *__restrict__ problem_of, int dz_clip) {
   constexpr bool kSeq = true, kDist = true, kComm = true, kPool = true;
@@ -882,10 +880,10 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
   h->spec0 = *spec; h->opt0 = *opt;
   h->lay = cfz::make_layout(k.N, k.n_obs + k.n_nbr, k.n_nbr);
   h->lds_bytes = (size_t)h->lay.total * sizeof(double);
-  if (const char *pad = std::getenv("CFZ_LDS_PAD")) h->lds_bytes += (size_t)std::atoi(pad);  // occupancy experiments only
   if (h->lds_bytes > 160 * 1024) return fail("problem does not fit the 160 KiB LDS of one CU");
   if (h->lds_bytes > 64 * 1024) {
-    // (no shape the ABI admits gets here: the widest, N 32 with 8 obstacles and 7 neighbours, takes 60,216 B (tools/src/loop_variant_check.hip prints it); CFZ_LDS_PAD does)
+    // (a guard: no shape the ABI admits gets here -- the widest, N 32 with 8 obstacles and 7 neighbours, takes 60,216 B
+    // (tools/src/loop_variant_check.hip prints it) -- and nothing else changes lds_bytes)
     std::vector<const void *> kerns = {(const void *)solve_kernel, (const void *)solve_kernel_pool};
     for (const LoopVariant &v : kLoopVariants) kerns.push_back(v.fn);
     for (const void *kern : kerns) {

@@ -459,132 +459,17 @@ __device__ __attribute__((noinline)) void jstruct_back_all(int w0, int nw, const
   }
 }
 
-// The recursion over the joint separators, one wavefront per direction: side 0 eliminates blocks i0 .. i1 - 1 downwards (block i into
-// i + 1), side 1 blocks i0 .. i1 + 1 upwards (block j into j - 1).  Block i: D_i (column-major), right-hand sides [U_i | b1 b2] with U_i =
-// the coupling of block i's pt0 rows (row 16 a + p0 + c) with block i + 1's rows 16 b + be (column 7 b + be).  The elimination (lu64_build,
-// on the matrix cores) leaves Z_i = D_i^-1 [..] in LDS, row = unknown (X, 64 x 33); every lane keeps its own row of it in global memory
-// for the back-substitution (read again by the same lane), and accumulates the neighbour block's update for the row it will LOAD there
-// from broadcast reads of X: the words of global memory a lane reads in the next step are words the same lane wrote (no hand-off between
-// lanes through global memory, no fence; the hand-off inside the wavefront goes through LDS).  nvp: N[a] packed, 8 bits each.
-constexpr int kJXld = 33;  // row stride of X (odd: the lane = row reads are conflict-free)
-__device__ __attribute__((noinline)) int jstruct_chain(int side, int i0, int i1, unsigned nvp, int V, cfzb::glb_f64 *Ds, cfzb::glb_f64 *Us, cfzb::glb_f64 *Zl,
-                                                       cfzb::lds_f64 *lds, cfzb::lds_f64 *X) {
-  const int lane = threadIdx.x & 63, va = lane >> 4, la = lane & 15;
-  const int cu = la < 7 ? 7 * va + la : -1;  // this lane's row as a right-coupled row of its block: its column of U
-  Ds = juni(Ds); Us = juni(Us); Zl = juni(Zl); lds = juni_lds(lds); X = juni_lds(X); side = juni(side); i0 = juni(i0); i1 = juni(i1); V = juni(V); nvp = (unsigned)juni((int)nvp);
-  for (int i = i0; side ? i > i1 : i < i1; i += side ? -1 : 1) {
-    const cfzb::glb_f64 *Di = Ds + (size_t)i * kJB * kJB, *Ui = Us + (size_t)i * kJB * kJU;
-    const int ip = side ? i - 1 : i;                 // the coupling block involved: U_ip couples blocks ip and ip + 1
-    const int p0 = ip == 0 ? 7 : 8;                  // pt0's first local row in block ip
-    const cfzb::glb_f64 *Uc = Us + (size_t)ip * kJB * kJU;
-    if (lu64_build<32, kJXld, 1, cfzb::lds_f64>(lds, X, [&](auto Jc, double (&v)[16]) {
-          constexpr int J = decltype(Jc)::value;
-          if constexpr (J < 4) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) v[k] = Di[(16 * J + k) * kJB + lane];
-          } else if (side == 0) {
-#pragma unroll
-            for (int k = 0; k < 16; ++k) { const int q = 16 * (J - 4) + k; v[k] = q < 30 ? Ui[q * kJB + lane] : 0.0; }
-          } else {
-            const int cuc = cu >= 0 ? cu : 0;  // (clamped: the loads of a tile stand in one block, their results masked)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-              const int q = 16 * (J - 4) + k;
-              const double x = q < 28 ? Uc[cuc * kJB + 16 * (q / 7) + p0 + (q % 7)] : (q < 30 ? Ui[q * kJB + lane] : 0.0);  // U_{i-1}' (zero where a vehicle has no interior i - 1)
-              v[k] = (q < 28 && cu < 0) ? 0.0 : x;
-            }
-          }
-        })) return 1;
-    lu_wave_sync();
-    cfzb::glb_f64 *Zi = Zl + (size_t)i * kJB * kJU;
-#pragma unroll
-    for (int q = 0; q < 30; ++q) Zi[q * kJB + lane] = X[lane * kJXld + q];
-    // the neighbour block's update: acc[q] = sum over the coupled rows r of this block of U[r, this lane's row there] Z[r, q]
-    double acc[30];
-#pragma unroll
-    for (int q = 0; q < 30; ++q) acc[q] = 0.0;
-    if (side == 0) {
-      for (int b = 0; b < V; ++b) {
-        if (i >= (int)((nvp >> (8 * b)) & 255u)) continue;
-#pragma unroll
-        for (int c = 0; c < 7; ++c) {
-          const int r = 16 * b + p0 + c;
-          const double u = cu >= 0 ? Uc[cu * kJB + r] : 0.0;
-#pragma unroll
-          for (int q = 0; q < 30; ++q) acc[q] += u * X[r * kJXld + q];
-        }
-      }
-      if (cu >= 0) {
-        cfzb::glb_f64 *Dn = Ds + (size_t)(i + 1) * kJB * kJB, *Un = Us + (size_t)(i + 1) * kJB * kJU;
-#pragma unroll
-        for (int q = 0; q < 28; ++q) Dn[(16 * (q / 7) + (q % 7)) * kJB + lane] -= acc[q];
-        Un[28 * kJB + lane] -= acc[28]; Un[29 * kJB + lane] -= acc[29];
-      }
-    } else {
-      const bool isl = la >= p0 && la < p0 + 7 && ip < (int)((nvp >> (8 * va)) & 255u);  // this lane's row is a pt0 row of block i - 1
-      for (int b = 0; b < V; ++b) {
-        if (ip >= (int)((nvp >> (8 * b)) & 255u)) continue;
-#pragma unroll
-        for (int be = 0; be < 7; ++be) {
-          const int r = 16 * b + be;
-          const double u = isl ? Uc[(7 * b + be) * kJB + lane] : 0.0;
-#pragma unroll
-          for (int q = 0; q < 30; ++q) acc[q] += u * X[r * kJXld + q];
-        }
-      }
-      if (isl) {
-        cfzb::glb_f64 *Dn = Ds + (size_t)ip * kJB * kJB, *Un = Us + (size_t)ip * kJB * kJU;
-#pragma unroll
-        for (int q = 0; q < 28; ++q) Dn[(16 * (q / 7) + p0 + (q % 7)) * kJB + lane] -= acc[q];
-        Un[28 * kJB + lane] -= acc[28]; Un[29 * kJB + lane] -= acc[29];
-      }
-    }
-    lu_wave_sync();  // (X is rewritten by the next block's elimination)
-  }
-  return 0;
-}
-// the middle block (both neighbours folded in) and the back-substitution outwards: side 0 blocks mid - 1 .. 0, side 1 blocks mid + 1 .. Nm;
-// xs[i][s][row] receives the solutions.  Side 1 takes x_mid from xs (written by side 0 before a workgroup barrier: `phase`)
-__device__ __attribute__((noinline)) int jstruct_chain_mid(int mid, cfzb::glb_f64 *Ds, cfzb::glb_f64 *Us, cfzb::glb_f64 *xs) {
-  const int lane = threadIdx.x & 63;
-  const cfzb::glb_f64 *Di = Ds + (size_t)mid * kJB * kJB, *Ui = Us + (size_t)mid * kJB * kJU;
-  double a[kJB + 2];
-#pragma unroll
-  for (int j = 0; j < kJB; ++j) a[j] = Di[j * kJB + lane];
-  a[kJB] = Ui[28 * kJB + lane]; a[kJB + 1] = Ui[29 * kJB + lane];
-  int ord;
-  if (wave_lu_regs<kJB, 2>(a, lane, ord)) return 1;
-  xs[(size_t)mid * 2 * kJB + ord] = a[kJB]; xs[(size_t)mid * 2 * kJB + kJB + ord] = a[kJB + 1];
-  return 0;
-}
-__device__ __attribute__((noinline)) void jstruct_chain_back(int side, int mid, int Nm, const cfzb::glb_f64 *Zl, cfzb::glb_f64 *xs) {
-  const int lane = threadIdx.x & 63;
-  double xp1 = xs[(size_t)mid * 2 * kJB + lane], xp2 = xs[(size_t)mid * 2 * kJB + kJB + lane];  // x of the block before, lane = unknown
-  for (int i = side ? mid + 1 : mid - 1; side ? i <= Nm : i >= 0; i += side ? 1 : -1) {
-    const cfzb::glb_f64 *Zi = Zl + (size_t)i * kJB * kJU;
-    const int ip = side ? i - 1 : i, p0 = ip == 0 ? 7 : 8;
-    double x1 = Zi[28 * kJB + lane], x2 = Zi[29 * kJB + lane];
-#pragma unroll
-    for (int q = 0; q < 28; ++q) {
-      const int r = side ? 16 * (q / 7) + p0 + (q % 7) : 16 * (q / 7) + (q % 7);  // the unknown of the block before that column q stands for
-      const double z = Zi[q * kJB + lane];
-      x1 -= z * struct_lane_get(xp1, r); x2 -= z * struct_lane_get(xp2, r);
-    }
-    xs[(size_t)i * 2 * kJB + lane] = x1; xs[(size_t)i * 2 * kJB + kJB + lane] = x2;
-    xp1 = x1; xp2 = x2;
-  }
-}
-
 // ---- the recursion over the joint separators by block CYCLIC REDUCTION (round 6) ------------------------------------------
-// The chain above keeps two of the workgroup's eight wavefronts busy for 26 dependent steps each.  The separator system is block
+// Block i: D_i (column-major), right-hand sides [U_i | b1 b2].  The separator system is block
 // tridiagonal with a special coupling: block i and its right neighbour meet only in 28 x 28 entries -- the pt0 rows of block i (row
 // 16 a + p0 + c, p0 = 7 for block 0 and 8 otherwise) against the right-coupled rows of the neighbour (row 16 b + be) -- and eliminating a
 // block leaves exactly such a coupling between ITS two neighbours:
 //   D_l[P, P] -= C_l G_FF C_l',   D_r[F, F] -= C_i' G_PP C_i,   C_l <- -C_l G_FP C_i     (G = D_i^-1; F, P: the block's right-coupled / pt0 rows)
 // so every other block can leave at once, level by level (strides 1, 2, 4, ..: 25 + 13 + 6 + 3 + 2 + 1 blocks for 51), each needing the
 // columns F and P of its inverse: two 64-row eliminations on the matrix cores with 30 and 28 right-hand sides (unit vectors and the two
-// right-hand sides), all eight wavefronts at work.  tools/joint_condense_study.py: as accurate as the chain (the blocks are as well
-// conditioned without their neighbours' updates as with them: 1e12-6e15 either way, solutions equal to 5e-14 .. 2e-9).
+// right-hand sides), all eight wavefronts at work.  It replaced a recursion from both ends, a wavefront each, which kept two of the eight
+// wavefronts busy for 26 dependent steps each (git history).  tools/joint_condense_study.py: as accurate as that recursion (the blocks are
+// as well conditioned without their neighbours' updates as with them: 1e12-6e15 either way, solutions equal to 5e-14 .. 2e-9).
 // Per block: Za = G [E_F | r] (64 x 30), Zb = G E_P (64 x 28), Lc = the left link as it stood (28 x 28), all for the back-substitution
 //   x_i = g - G[:, F] (C_l' x_l[P]) - G[:, P] (C_i x_r[F]).
 __device__ __forceinline__ int jrowF(int q) { return 16 * (q / 7) + (q % 7); }              // right-coupled unknown q = 7 b + be of a block
@@ -842,7 +727,8 @@ __device__ __attribute__((noinline)) void j1_sep_all(int w0, int nw, const cfzb:
     U[9 * 16 + la] = 0.0;
   }
 }
-// the recursion from one end (as jstruct_chain): 16-row blocks, 10 right-hand sides, lanes 16.. idle
+// the recursion from one end, one wavefront per direction: side 0 eliminates blocks i0 .. i1 - 1 downwards (block i into i + 1), side 1
+// blocks i0 .. i1 + 1 upwards (block j into j - 1); 16-row blocks, 10 right-hand sides, lanes 16.. idle
 __device__ __attribute__((noinline)) int j1_chain(int side, int i0, int i1, cfzb::glb_f64 *D1, cfzb::glb_f64 *U1, cfzb::glb_f64 *Z1, cfzb::glb_i32 *ordl) {
   const int lane = threadIdx.x & 63, la = lane & 15;
   D1 = juni(D1); U1 = juni(U1); Z1 = juni(Z1); ordl = juni(ordl); side = juni(side); i0 = juni(i0); i1 = juni(i1);
@@ -1190,7 +1076,6 @@ CFZP_FN int jstruct_solve(const CSpec &sp, const CDims &d, const CWork &w, const
   { const long long t1 = tick(); ptk[1] += t1 - tp; tp = t1; }
   // ---- phase 3: recursion over the joint separators -------------------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__)
-#if !defined(CFZ_JCHAIN)
   {  // block cyclic reduction (round 6): levels of stride 1, 2, 4, ..; per level the leaving blocks' eliminations on all eight wavefronts, then
      // their neighbours' updates; block 0 is what remains; the back-substitution runs through the levels in reverse
     const int wv = CFZS_WAVE, nwv = CFZS_NW;
@@ -1216,27 +1101,6 @@ CFZP_FN int jstruct_solve(const CSpec &sp, const CDims &d, const CWork &w, const
       __syncthreads();
     }
   }
-#else
-  {  // from both ends, a wavefront each; the middle block receives both; back-substitution outwards
-    const int mid = (Nm + 1) / 2, wv = CFZS_WAVE;
-    unsigned nvp = 0;
-    for (int a = 0; a < V; ++a) nvp |= (unsigned)sp.N[a] << (8 * a);
-    int f = 0;
-    // (LDS: a wavefront's own kLuLdsWave doubles for the elimination; X in the areas of two of the six idle wavefronts)
-    static_assert(2 * kLuLdsWave >= kJB * kJXld, "X fits two areas");
-    cfzb::lds_f64 *lb = cfzb::opaque((cfzb::lds_f64 *)lds);
-    if (wv == 0) f = jstruct_chain(0, 0, mid, nvp, V, (cfzb::glb_f64 *)s.Ds, (cfzb::glb_f64 *)s.Us, (cfzb::glb_f64 *)s.Zs, lb, lb + 2 * kLuLdsWave);
-    else if (wv == 1) f = jstruct_chain(1, Nm, mid, nvp, V, (cfzb::glb_f64 *)s.Ds, (cfzb::glb_f64 *)s.Us, (cfzb::glb_f64 *)s.Zs, lb + kLuLdsWave, lb + 4 * kLuLdsWave);
-    if (f && CFZS_LANE == 0) flag[0] = 1.0;
-    __syncthreads();
-    if (flag[0] != 0.0) return 1;
-    if (wv == 0 && jstruct_chain_mid(mid, (cfzb::glb_f64 *)s.Ds, (cfzb::glb_f64 *)s.Us, (cfzb::glb_f64 *)s.xs) && CFZS_LANE == 0) flag[0] = 1.0;
-    __syncthreads();
-    if (flag[0] != 0.0) return 1;
-    if (wv < 2) jstruct_chain_back(wv, mid, Nm, (const cfzb::glb_f64 *)s.Zs, (cfzb::glb_f64 *)s.xs);
-    __syncthreads();
-  }
-#endif
 #else
   for (int i = 0; i <= Nm; ++i) {
     double *Di = s.Ds + (size_t)i * kJB * kJB, *Ui = s.Us + (size_t)i * kJB * kJU, *Zi = s.Zs + (size_t)i * kJB * kJU;

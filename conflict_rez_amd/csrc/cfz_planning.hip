@@ -15,9 +15,6 @@
 #include <string>
 #include <vector>
 
-#ifndef CFZ_PANEL
-#define CFZ_PANEL 16  // pivots per panel of the eight-wavefront elimination (cfz_colloc.inl; the host sizes its LDS)
-#endif
 #include "../../include/confrez_hip.h"
 #include "cfz_common.h"
 #include "cfz_solver.inl"
@@ -42,10 +39,7 @@ __global__ __launch_bounds__(512) void state_ws_kernel(int B, const cfzp::PSpec 
 // workspace in global memory, elimination from global memory a panel at a time; see cfz_colloc.inl.
 // bound 512: with 64 (or 256) the register allocator may use AGPRs beyond 256 VGPRs, and every such build of this kernel died with
 // HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION on gfx950 / ROCm 7.2 while the 256-VGPR builds of the same source run.
-#ifndef CFZC_BOUNDS
-#define CFZC_BOUNDS 512
-#endif
-__global__ __launch_bounds__(CFZC_BOUNDS) void colloc_kernel(int B, const cfzc::CSpec *specs, double *X, const long long *x_off, double *slab,
+__global__ __launch_bounds__(512) void colloc_kernel(int B, const cfzc::CSpec *specs, double *X, const long long *x_off, double *slab,
                               const long long *slab_off, const int32_t *kbs, int32_t *oi, double *od, int lds_doubles, int lds_rhs) {
   const int b = blockIdx.x;
   // dynamic LDS (lds_doubles): the multipliers of a panel during the elimination; lds_rhs (<= lds_doubles, 0 = none): room for one
@@ -459,7 +453,7 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
   // (docs/notebook.md).  `kernel` is still accepted (0, 1, 2) and means nothing.
   {
     // Dynamic LDS beside the kernel's static arrays (read from the code object, not assumed): the panel's multipliers
-    // (CFZ_PANEL x (kb + CFZ_PANEL) doubles, <= 58 KB) must fit; a right-hand side of the largest instance rides along only if it
+    // (kPanel x (kb + kPanel) doubles, <= 58 KB) must fit; a right-hand side of the largest instance rides along only if it
     // fits as well (it serves band_substitute_wide, the fallback substitution) -- the panel path does not depend on it.
     int nk_max = 0, kb_max = 0, lds_max = 0;
     for (int b = 0; b < B; ++b) { nk_max = std::max(nk_max, cfzc::cdims(specs[b]).nk); kb_max = std::max(kb_max, (int)kbs[b]); }
@@ -468,7 +462,7 @@ static int colloc_run(cfz_plan_ws *w, int B, const int32_t *nveh, const std::vec
     if (lds_per_workgroup(w->device, &lds_max)) return -1;
     if (profile) fprintf(stderr, "cfz_colloc: LDS per workgroup %d B, static %zu B\n", lds_max, (size_t)fa.sharedSizeBytes);
     const long long avail = ((long long)lds_max - (long long)fa.sharedSizeBytes) / 8;
-    const long long pl = kb_max <= cfzc::kWideMaxKb ? (long long)CFZ_PANEL * (kb_max + CFZ_PANEL) : 0;
+    const long long pl = kb_max <= cfzc::kWideMaxKb ? (long long)cfzc::kPanel * (kb_max + cfzc::kPanel) : 0;
     const int lds_rhs = nk_max <= avail ? nk_max : 0;
     int lds_doubles = (int)std::max<long long>(pl <= avail ? pl : 0, lds_rhs), lds_rhs_ = lds_rhs;
     // the structured eliminations' 64-row blocks on the matrix cores stage their operands in LDS: kLuLdsWave doubles for each of the eight

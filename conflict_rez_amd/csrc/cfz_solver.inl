@@ -16,9 +16,8 @@
 //             each propagates its own columns of the sensitivities: lane sub column sub, every lane column 4
 //   stage     condensed H_k, g_k, bound multipliers, costs: computed by the whole quad, written by sub 0
 //   Riccati   backward sweep: 30 dependent stages, out of line (registers of its own) -- since round 5 on the matrix cores, the first
-//             wavefront's 64 lanes holding the stage's 16 x 16 tiles (riccati_backward_mfma; the one-lane sweep remains as
-//             -DCFZ_RICCATI_SCALAR); forward step and costates: linear recurrences once the gains are known -> Kogge-Stone scans,
-//             one stage per lane of wavefront 0
+//             wavefront's 64 lanes holding the stage's 16 x 16 tiles (riccati_backward_mfma); forward step and costates: linear
+//             recurrences once the gains are known -> Kogge-Stone scans, one stage per lane of wavefront 0
 // (CFZ_LPS = 8: eight lanes per stage, four wavefronts per instance -- round 6's go / no-go, a diagnostic build; the product is 4.)
 // Reductions over the workgroup run on registers: DPP butterflies inside a row of 16 lanes, v_readlane across the four
 // rows of a wavefront, one 16-double LDS exchange between the two wavefronts.
@@ -67,8 +66,6 @@ constexpr int kXS = 7;              // values one workgroup reduction can carry 
 #define CFZ_P(name, i) name[i]
 #define CFZ_QSUM(name, i) cfz::quad_sum(name[i])
 #define CFZ_REDUCE(NS, NX, NI, part, out) cfz::reduce_all<NS, NX, NI>(m, L, xpar, part, out)
-// the sweeps run on lane 0 of the workgroup, out of line; every lane calls (uniform control flow), lane 0 works
-#define CFZ_SERIAL(call) do { call; __syncthreads(); } while (0)
 #define CFZ_WAVE0(call) do { if (threadIdx.x < cfz::kMaxN) { call; } __syncthreads(); } while (0)  // the lanes that own a stage
 #define CFZ_WSP(p) cfz::opaque_wsp((cfz::wsp_f64 *)(p))
 #define CFZ_UNIFORM(v) cfz::uniform_value(v)
@@ -81,7 +78,6 @@ constexpr int kXS = 7;              // values one workgroup reduction can carry 
 #define CFZ_P(name, i) name[i][tid]
 #define CFZ_QSUM(name, i) cfz::quad_sum_emu(name[i], tid)
 #define CFZ_REDUCE(NS, NX, NI, part, out) cfz::reduce_all_emu<NS, NX, NI>(part, out)
-#define CFZ_SERIAL(call) do { call; } while (0)
 #define CFZ_WAVE0(call) do { call; } while (0)
 #define CFZ_WSP(p) (p)
 #define CFZ_UNIFORM(v) (v)
@@ -946,163 +942,15 @@ CFZ_CALL void merit_partials(const KSpec &sp, const KDer &dv, const double *refg
   th_o = th; ph_o = ph; ll_o = (bad == 0.0) ? log(lprod) : 0.0; bad_o = bad;
 }
 
-// ------------------------------------------------------------------------------ Riccati sweeps (lane 0, out of line)
-// Functions of their own so that their registers are their own (inlined into the solver the backward sweep kept ~100
-// doubles live on top of the solver's state and spilled into AGPRs and scratch).  Device: they must not NAME any LDS
+// ------------------------------------------------------------------------------ Riccati backward sweep (out of line)
+// A function of its own so that its registers are its own (inlined into the solver the backward sweep kept ~100
+// doubles live on top of the solver's state and spilled into AGPRs and scratch).  Device: it must not NAME any LDS
 // (toolchain, see cfz_band.inl); the workspace comes in as an address-space-3 pointer, so every access is a DS
-// instruction.  Every lane calls them (uniform control flow), lane 0 does the work.
+// instruction.
 // Structure used: A_k = I + [0 0 s00 s01 s02; 0 0 s10 s11 s12; 0 0 0 s21 s22; 0; 0] (s20 = 1),
 // B_k = [s03 s04; s13 s14; s23 s24; dt 0; 0 dt]; H_k = diag(h0..h6) + pose off-diagonals h7 (0,1), h8 (0,2), h9 (1,2) +
-// the v-w cross term h10 (3,6).  A lane-parallel variant (matrix entries spread over lanes, exchange through LDS) measured
-// 2.2x slower: every exchange is a dependent LDS round trip.  Round 4 built the register-only variant (five lanes, lane j
-// owning column j of P; W, e, three rows of M and the gains' columns broadcast by v_readlane, 40 doubles per stage, no LDS, no
-// barrier): bit-compatible results, 70 k cycles per sweep against 60 k here -- the 80 v_readlane of a stage cost more than the 150
-// multiply-adds they save a lane (docs/notebook.md); taken out again.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(CFZ_SWEEP_INLINE)
-#define CFZ_SWEEP __device__ __forceinline__ void
-#define CFZ_SWEEP_GUARD if (threadIdx.x != 0) return;
-#elif defined(__HIP_DEVICE_COMPILE__)
-#define CFZ_SWEEP __device__ __attribute__((noinline)) void
-#define CFZ_SWEEP_GUARD if (threadIdx.x != 0) return;
-#else
-#define CFZ_SWEEP static void
-#define CFZ_SWEEP_GUARD
-#endif
-
-// The sweep is software-pipelined by hand: the loads of the NEXT stage are issued before the stores of this one.
-// The compiler cannot do that itself (loads and stores go through the same workspace pointer, so it must assume that a
-// store may feed a later load) and without it every stage waits for an LDS round trip per operand group.
-
-// backward sweep: gains K_k (12 per stage) into kk, value function of stage 0 into rP (25) and rP + 25 (5).
-// P is kept as its upper triangle.  With W = B'P:  Hux = W A,  Huu = R + W B,  hu = g_u + B'(p + P d);  M = P A,
-// Hxx = Q + A'M (upper triangle only);  K = -Huu^-1 [Hux hu];  P <- Hxx - Hux' Huu^-1 Hux,  p <- hx - Hux' Huu^-1 hu.
-CFZ_SWEEP riccati_backward(wsp_f64 *m, int N, double dt, int o_ab, int o_hc, int o_gk, int o_d, int o_kk, int o_rP) {
-  CFZ_SWEEP_GUARD
-  // upper triangle of P: P00 P01 P02 P03 P04 | P11 P12 P13 P14 | P22 P23 P24 | P33 P34 | P44
-  double P00, P01, P02, P03 = 0.0, P04 = 0.0, P11, P12, P13 = 0.0, P14 = 0.0, P22, P23 = 0.0, P24 = 0.0, P33, P34 = 0.0, P44;
-  double p0, p1, p2, p3, p4;
-  {
-    const int k = N - 1;  // terminal stage: its inputs a,w are costed but drive no dynamics
-    const wsp_f64 *h = m + o_hc + k * 11, *gk = m + o_gk + k * kNP;
-    wsp_f64 *K = m + o_kk + k * 12;
-    const double h10 = h[10], h6 = h[6];
-    const double k53 = -h10 / h6, k10 = -gk[5] / h[5], k11 = -gk[6] / h6;
-    P00 = h[0]; P11 = h[1]; P22 = h[2]; P33 = h[3] + h10 * k53; P44 = h[4];
-    P01 = h[7]; P02 = h[8]; P12 = h[9];
-    p0 = gk[0]; p1 = gk[1]; p2 = gk[2]; p3 = gk[3] + h10 * k11; p4 = gk[4];
-    for (int q = 0; q < 10; ++q) K[q] = 0.0;
-    K[5 + 3] = k53; K[10] = k10; K[11] = k11;
-  }
-  // dynamics data (s, d: needed first) of the stage being processed are loaded one stage ahead; its cost data (h, g: needed
-  // later in the stage) at the top of the stage, where their latency hides behind the first hundred multiply-adds
-  double sc[15], dc[5];
-  if (N >= 2) {
-    const int k = N - 2;
-    const wsp_f64 *s = m + o_ab + k * 15, *d = m + o_d + k * 5;
-#pragma unroll
-    for (int i = 0; i < 15; ++i) sc[i] = s[i];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) dc[i] = d[i];
-  }
-  for (int k = N - 2; k >= 0; --k) {
-    double hc_[11], gc[7];
-    {
-      const wsp_f64 *h = m + o_hc + k * 11, *g = m + o_gk + k * kNP;
-#pragma unroll
-      for (int i = 0; i < 11; ++i) hc_[i] = h[i];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) gc[i] = g[i];
-    }
-    const double s00 = sc[0], s01 = sc[1], s02 = sc[2], s03 = sc[3], s04 = sc[4];
-    const double s10 = sc[5], s11 = sc[6], s12 = sc[7], s13 = sc[8], s14 = sc[9];
-    const double s21 = sc[11], s22 = sc[12], s23 = sc[13], s24 = sc[14];
-    // W = B'P (2 x 5); rows of B': (s03 s13 s23 dt 0), (s04 s14 s24 0 dt)
-    const double W00 = s03 * P00 + s13 * P01 + s23 * P02 + dt * P03;
-    const double W01 = s03 * P01 + s13 * P11 + s23 * P12 + dt * P13;
-    const double W02 = s03 * P02 + s13 * P12 + s23 * P22 + dt * P23;
-    const double W03 = s03 * P03 + s13 * P13 + s23 * P23 + dt * P33;
-    const double W04 = s03 * P04 + s13 * P14 + s23 * P24 + dt * P34;
-    const double W10 = s04 * P00 + s14 * P01 + s24 * P02 + dt * P04;
-    const double W11 = s04 * P01 + s14 * P11 + s24 * P12 + dt * P14;
-    const double W12 = s04 * P02 + s14 * P12 + s24 * P22 + dt * P24;
-    const double W13 = s04 * P03 + s14 * P13 + s24 * P23 + dt * P34;
-    const double W14 = s04 * P04 + s14 * P14 + s24 * P24 + dt * P44;
-    // Hux = W A (+ the v-w cross term of the stage cost)
-    const double X00 = W00, X01 = W01, X02 = W02 + s00 * W00 + s10 * W01;
-    const double X03 = W03 + s01 * W00 + s11 * W01 + s21 * W02, X04 = W04 + s02 * W00 + s12 * W01 + s22 * W02;
-    const double X10 = W10, X11 = W11, X12 = W12 + s00 * W10 + s10 * W11;
-    const double X13 = W13 + s01 * W10 + s11 * W11 + s21 * W12 + hc_[10], X14 = W14 + s02 * W10 + s12 * W11 + s22 * W12;
-    // Huu = R + W B
-    const double a00 = hc_[5] + s03 * W00 + s13 * W01 + s23 * W02 + dt * W03;
-    const double a01 = s04 * W00 + s14 * W01 + s24 * W02 + dt * W04;
-    const double a11 = hc_[6] + s04 * W10 + s14 * W11 + s24 * W12 + dt * W14;
-    // Pd = p + P d
-    const double d0 = dc[0], d1 = dc[1], d2 = dc[2], d3 = dc[3], d4 = dc[4];
-    const double e0 = p0 + P00 * d0 + P01 * d1 + P02 * d2 + P03 * d3 + P04 * d4;
-    const double e1 = p1 + P01 * d0 + P11 * d1 + P12 * d2 + P13 * d3 + P14 * d4;
-    const double e2 = p2 + P02 * d0 + P12 * d1 + P22 * d2 + P23 * d3 + P24 * d4;
-    const double e3 = p3 + P03 * d0 + P13 * d1 + P23 * d2 + P33 * d3 + P34 * d4;
-    const double e4 = p4 + P04 * d0 + P14 * d1 + P24 * d2 + P34 * d3 + P44 * d4;
-    const double hu0 = gc[5] + s03 * e0 + s13 * e1 + s23 * e2 + dt * e3;
-    const double hu1 = gc[6] + s04 * e0 + s14 * e1 + s24 * e2 + dt * e4;
-    const double hx0 = gc[0] + e0, hx1 = gc[1] + e1;
-    const double hx2 = gc[2] + e2 + s00 * e0 + s10 * e1;
-    const double hx3 = gc[3] + e3 + s01 * e0 + s11 * e1 + s21 * e2;
-    const double hx4 = gc[4] + e4 + s02 * e0 + s12 * e1 + s22 * e2;
-    // M = P A: columns 0, 1 are P's; columns 2..4 of every row
-    const double M02 = P02 + s00 * P00 + s10 * P01, M03 = P03 + s01 * P00 + s11 * P01 + s21 * P02, M04 = P04 + s02 * P00 + s12 * P01 + s22 * P02;
-    const double M12 = P12 + s00 * P01 + s10 * P11, M13 = P13 + s01 * P01 + s11 * P11 + s21 * P12, M14 = P14 + s02 * P01 + s12 * P11 + s22 * P12;
-    const double M22 = P22 + s00 * P02 + s10 * P12, M23 = P23 + s01 * P02 + s11 * P12 + s21 * P22, M24 = P24 + s02 * P02 + s12 * P12 + s22 * P22;
-    const double M33 = P33 + s01 * P03 + s11 * P13 + s21 * P23, M34 = P34 + s02 * P03 + s12 * P13 + s22 * P23;
-    const double M43 = P34 + s01 * P04 + s11 * P14 + s21 * P24, M44 = P44 + s02 * P04 + s12 * P14 + s22 * P24;
-    // Hxx = Q + A'M, upper triangle
-    const double H00 = P00 + hc_[0], H01 = P01 + hc_[7], H02 = M02 + hc_[8], H03 = M03, H04 = M04;
-    const double H11 = P11 + hc_[1], H12 = M12 + hc_[9], H13 = M13, H14 = M14;
-    const double H22 = M22 + s00 * M02 + s10 * M12 + hc_[2], H23 = M23 + s00 * M03 + s10 * M13, H24 = M24 + s00 * M04 + s10 * M14;
-    const double H33 = M33 + s01 * M03 + s11 * M13 + s21 * M23 + hc_[3], H34 = M34 + s01 * M04 + s11 * M14 + s21 * M24;
-    const double H44 = M44 + s02 * M04 + s12 * M14 + s22 * M24 + hc_[4];
-    (void)M43;
-    const double idet = 1.0 / (a00 * a11 - a01 * a01);
-    const double i00 = a11 * idet, i01 = -a01 * idet, i11 = a00 * idet;
-    // t = Huu^-1 [Hux hu]
-    const double t00 = i00 * X00 + i01 * X10, t01 = i00 * X01 + i01 * X11, t02 = i00 * X02 + i01 * X12, t03 = i00 * X03 + i01 * X13,
-                 t04 = i00 * X04 + i01 * X14, t05 = i00 * hu0 + i01 * hu1;
-    const double t10 = i01 * X00 + i11 * X10, t11 = i01 * X01 + i11 * X11, t12 = i01 * X02 + i11 * X12, t13 = i01 * X03 + i11 * X13,
-                 t14 = i01 * X04 + i11 * X14, t15 = i01 * hu0 + i11 * hu1;
-    // new value function (registers), then the loads of the next stage, then this stage's gains: in that order, see above
-    const double N00 = H00 - (X00 * t00 + X10 * t10), N01 = H01 - (X00 * t01 + X10 * t11), N02 = H02 - (X00 * t02 + X10 * t12);
-    const double N03 = H03 - (X00 * t03 + X10 * t13), N04 = H04 - (X00 * t04 + X10 * t14);
-    const double N11 = H11 - (X01 * t01 + X11 * t11), N12 = H12 - (X01 * t02 + X11 * t12), N13 = H13 - (X01 * t03 + X11 * t13);
-    const double N14 = H14 - (X01 * t04 + X11 * t14);
-    const double N22 = H22 - (X02 * t02 + X12 * t12), N23 = H23 - (X02 * t03 + X12 * t13), N24 = H24 - (X02 * t04 + X12 * t14);
-    const double N33 = H33 - (X03 * t03 + X13 * t13), N34 = H34 - (X03 * t04 + X13 * t14);
-    const double N44 = H44 - (X04 * t04 + X14 * t14);
-    p0 = hx0 - (X00 * t05 + X10 * t15); p1 = hx1 - (X01 * t05 + X11 * t15); p2 = hx2 - (X02 * t05 + X12 * t15);
-    p3 = hx3 - (X03 * t05 + X13 * t15); p4 = hx4 - (X04 * t05 + X14 * t15);
-    P00 = N00; P01 = N01; P02 = N02; P03 = N03; P04 = N04; P11 = N11; P12 = N12; P13 = N13; P14 = N14;
-    P22 = N22; P23 = N23; P24 = N24; P33 = N33; P34 = N34; P44 = N44;
-    {
-      const int kn = k > 0 ? k - 1 : 0;  // the last pass re-reads stage 0 (harmless) so that the loop body has no branch here
-      const wsp_f64 *s = m + o_ab + kn * 15, *d = m + o_d + kn * 5;
-#pragma unroll
-      for (int i = 0; i < 15; ++i) sc[i] = s[i];
-#pragma unroll
-      for (int i = 0; i < 5; ++i) dc[i] = d[i];
-    }
-    wsp_f64 *K = m + o_kk + k * 12;
-    K[0] = -t00; K[1] = -t01; K[2] = -t02; K[3] = -t03; K[4] = -t04;
-    K[5] = -t10; K[6] = -t11; K[7] = -t12; K[8] = -t13; K[9] = -t14;
-    K[10] = -t05; K[11] = -t15;
-  }
-  wsp_f64 *rP = m + o_rP;
-  rP[0] = P00; rP[1] = P01; rP[2] = P02; rP[3] = P03; rP[4] = P04;
-  rP[5] = P01; rP[6] = P11; rP[7] = P12; rP[8] = P13; rP[9] = P14;
-  rP[10] = P02; rP[11] = P12; rP[12] = P22; rP[13] = P23; rP[14] = P24;
-  rP[15] = P03; rP[16] = P13; rP[17] = P23; rP[18] = P33; rP[19] = P34;
-  rP[20] = P04; rP[21] = P14; rP[22] = P24; rP[23] = P34; rP[24] = P44;
-  rP[25] = p0; rP[26] = p1; rP[27] = p2; rP[28] = p3; rP[29] = p4;
-}
-
+// the v-w cross term h10 (3,6).
+// Result: gains K_k (12 per stage) into kk, value function of stage 0 into rP (25) and rP + 25 (5).
 // Operands of the sweep in homogeneous coordinates (below), as workspace words or constants, and the sweep itself in plain loops with
 // every sum in the order v_mfma_f64_16x16x4_f64 forms it (k ascending, one fused multiply-add per k onto the accumulator): what the CPU
 // build runs, bit for bit what the matrix-core sweep returns (tools/src/riccati_mfma_bench.hip: 0 of 2,880 gains differ); oracle/cfz_port.c
@@ -1156,19 +1004,22 @@ static void riccati_backward_dense(wsp_f64 *m, int N, double dt, int o_ab, int o
   for (int i = 0; i < 5; ++i) { for (int j = 0; j < 5; ++j) m[o_rP + 5 * i + j] = P[i][j]; m[o_rP + 25 + i] = P[5][i]; }
 }
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(CFZ_RICCATI_SCALAR)
+#if defined(__HIP_DEVICE_COMPILE__)
 // The same sweep on the matrix cores (round 5; tools/src/riccati_mfma_bench.hip is the go / no-go measurement: 1,150 cycles per stage
-// against 1,850 for the one-lane sweep above, gains equal to 9e-16).  The first wavefront, all 64 lanes.  Homogeneous coordinates, variables
-// ordered [z (5), 1, u (2)]:  [z+; 1] = T [z; 1; u],  T = [[A d B], [0 1 0]]  (6 x 8),  Pt = [[P p], [p' 0]]  (6 x 6),
+// against 1,850 for the hand-pipelined sweep on one lane it replaced, gains equal to 9e-16).  Measured before it and removed (git
+// history): entries spread over lanes with exchange through LDS, 2.2x slower than one lane (every exchange a dependent LDS round
+// trip); five lanes on registers only (v_readlane broadcasts, no LDS, no barrier), 70 k cycles per sweep against one lane's 60 k.
+// The first wavefront, all 64 lanes.  Homogeneous coordinates, variables ordered [z (5), 1, u (2)]:
+//   [z+; 1] = T [z; 1; u],  T = [[A d B], [0 1 0]]  (6 x 8),  Pt = [[P p], [p' 0]]  (6 x 6),
 //   M = T' Pt T + Ht  (8 x 8; Ht = the stage's Hessian with its gradient in row / column 5),   Pt <- M_kk - M_ke M_ee^-1 M_ek,  K = -M_ee^-1 M_ek,
 // as five dependent v_mfma_f64_16x16x4_f64 per stage (result register r of lane l = row (l >> 4) + 4 r, column l & 15):
 //   Y = Pt T     two k-steps; the A operand is Pt's accumulator as it stands (Pt is symmetric: register s of lane l is A[l & 15][(l >> 4) + 4 s]);
 //   M = Tt' Y    two k-steps onto an accumulator that starts as Ht; the B operand is Y's accumulator as it stands; Tt' repeats the rows of
 //                u at rows 8, 9 and (crossed) 12, 13, so that the 16-lane groups 0 and 1 hold M's rows of u in their own registers;
 //   Pt <- M - U V   one k-step: A = -M_ke (groups 0, 1: register 2), B = V = M_ee^-1 M_ek (from registers 2 and 3; M_ee by v_readlane).
-// The operands are built on the fly from the stage data the one-lane sweep reads (15 sensitivities, d, 11 Hessian entries, 7 gradient
+// The operands are built on the fly from the stage data as the solver leaves it (15 sensitivities, d, 11 Hessian entries, 7 gradient
 // entries): every lane knows once and for all which workspace word (or constant) each of its eight operand entries is.  The terminal
-// stage is the same step from Pt = 0.  (The CPU build and the oracle run the one-lane algebra: same recursion, sums in another order.)
+// stage is the same step from Pt = 0.
 typedef double ric_v4d __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ double ric_lane(double v, int l) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
@@ -1242,8 +1093,6 @@ __device__ __attribute__((noinline)) void riccati_backward_mfma(wsp_f64 *m, int 
   }
 }
 #define CFZ_RICCATI(...) do { if (threadIdx.x < 64) { riccati_backward_mfma(__VA_ARGS__); } __syncthreads(); } while (0)
-#elif defined(__HIP_DEVICE_COMPILE__)
-#define CFZ_RICCATI(...) CFZ_SERIAL(riccati_backward(__VA_ARGS__))  // (-DCFZ_RICCATI_SCALAR: the one-lane sweep, for comparison)
 #else
 #define CFZ_RICCATI(...) riccati_backward_dense(__VA_ARGS__)
 #endif
@@ -1348,11 +1197,8 @@ CFZ_FN void cos5_stage(wsp_f64 *m, int k, int N, int o_ab, int o_hc, int o_gk, i
 // allocation suffers), but only the first 32 lanes call them (CFZ_WAVE0; one stage per lane, N <= 32): the prologue of
 // forward_scan saves 37 callee-saved registers of every calling lane to scratch, and every finished solve's release writes
 // that back to HBM.
-#ifndef CFZ_SCAN
-#define CFZ_SCAN __device__ __attribute__((noinline)) void
-#endif
-CFZ_SCAN forward_scan(wsp_f64 *m, int N, double dt, int o_ab, int o_d, int o_kk, int o_rP, int o_p, int o_dp, int o_x0,
-                       int o_pi0, int o_dpi0) {
+__device__ __attribute__((noinline)) void forward_scan(wsp_f64 *m, int N, double dt, int o_ab, int o_d, int o_kk, int o_rP, int o_p, int o_dp,
+                                                       int o_x0, int o_pi0, int o_dpi0) {
   if (threadIdx.x >= 64) return;  // the first wavefront, stage k on lane k
   const int k = threadIdx.x;
   Aff5 t;
@@ -1409,7 +1255,7 @@ CFZ_SCAN forward_scan(wsp_f64 *m, int N, double dt, int o_ab, int o_d, int o_kk,
   if (k == 0) { wsp_f64 *dp = m + o_dp; dp[0] = z0; dp[1] = z1; dp[2] = z2; dp[3] = z3; dp[4] = z4; }
 }
 
-CFZ_SCAN costate_scan(wsp_f64 *m, int N, int o_ab, int o_hc, int o_gk, int o_kk, int o_dp, int o_dpi, int o_pi) {
+__device__ __attribute__((noinline)) void costate_scan(wsp_f64 *m, int N, int o_ab, int o_hc, int o_gk, int o_kk, int o_dp, int o_dpi, int o_pi) {
   if (threadIdx.x >= 64) return;
   const int k = threadIdx.x;
   Cos5 t;
@@ -1469,11 +1315,6 @@ static void costate_scan(double *m, int N, int o_ab, int o_hc, int o_gk, int o_k
 }
 #endif
 
-#if defined(CFZ_NO_DELTAC)  // diagnostic builds: what the dual regularisation costs the hot loop
-#define kDeltaC(sp) 0.0
-#else
-#define kDeltaC(sp) (sp).reg_dual_rows
-#endif
 // ------------------------------------------------------------------------------ feasibility restoration
 // IPOPT answers a failed line search with its restoration phase (paper sec. 3.3).  Here (oracle/mpc_nlp.py MpcNlp.restore, oracle/cfz_port.c
 // restore): Levenberg-Marquardt on the squared violations of the separation rows of stages >= 1 and of the boxes,
@@ -1521,11 +1362,7 @@ CFZ_CALL void resto_partials(const KSpec &sp, const KDer &dv, double *m, const L
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
-#if defined(CFZ_RESTO_INLINE)
-#define CFZ_COLD __device__ __forceinline__
-#else
 #define CFZ_COLD __device__ __attribute__((noinline, cold))
-#endif
 #else
 #define CFZ_COLD static
 #endif
@@ -1890,11 +1727,7 @@ CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, c
       return;
     }
   }
-#if defined(CFZ_NO_RESTO)  // diagnostic builds: what the restoration phase's presence costs the hot loop
-  const bool resto_on = false;
-#else
   const bool resto_on = sp.resto > 0 && L.nr > 0;
-#endif
   CFZ_LANES(tid)
     const int k = tid >> kLPSBits, sub = tid & (kLPS - 1);
     if (k < N && sub == 0) {
@@ -2178,14 +2011,9 @@ CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, c
             const int t = k * nr + 2 * jb + r_;
             // delta_c on the row (IPOPT's dual regularisation, eliminated together with the slack): the row's stiffness is
             // S0 / (1 + delta_c S0) and its right-hand side sees the distance of nu from its centred value -mu / sigma
-#if defined(CFZ_NO_DELTAC)
-            const double isg = 1.0 / m[L.sg + t], S = m[L.zs + t] * isg + sp.reg_primal;
-            const double coef = S * m[L.cj + t] - mu * isg;
-#else
             const double isg = 1.0 / m[L.sg + t], S0 = m[L.zs + t] * isg + sp.reg_primal;
-            const double iD = 1.0 / (1.0 + kDeltaC(sp) * S0), S = S0 * iD;
-            const double coef = S * m[L.cj + t] - mu * isg * iD + kDeltaC(sp) * S * m[L.nuc + t];
-#endif
+            const double iD = 1.0 / (1.0 + sp.reg_dual_rows * S0), S = S0 * iD;
+            const double coef = S * m[L.cj + t] - mu * isg * iD + sp.reg_dual_rows * S * m[L.nuc + t];
             const double a2 = bap[r_];
             ac[0] += a0 * coef; ac[1] += a1 * coef; ac[2] += a2 * coef;
             ac[3] += S * a0 * a0; ac[4] += S * a1 * a1; ac[5] += S * a2 * a2;
@@ -2297,12 +2125,8 @@ CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, c
           for (int r_ = 0; r_ < 2; ++r_) {
             const int t = k * nr + 2 * jb + r_;
             const double sg = m[L.sg + t], zs = m[L.zs + t], isg = 1.0 / sg;
-#if defined(CFZ_NO_DELTAC)
-            const double ds = m[L.cj + t] + ba0 * dpk[0] + ba1 * dpk[1] + bap[r_] * dpk[2];
-#else
-            const double ds = (m[L.cj + t] + ba0 * dpk[0] + ba1 * dpk[1] + bap[r_] * dpk[2] + kDeltaC(sp) * (mu * isg + m[L.nuc + t])) /
-                              (1.0 + kDeltaC(sp) * (zs * isg + sp.reg_primal));
-#endif
+            const double ds = (m[L.cj + t] + ba0 * dpk[0] + ba1 * dpk[1] + bap[r_] * dpk[2] + sp.reg_dual_rows * (mu * isg + m[L.nuc + t])) /
+                              (1.0 + sp.reg_dual_rows * (zs * isg + sp.reg_primal));
             m[L.dsg + t] = ds;
             const double dzs = mu * isg - zs - zs * isg * ds;
             dphi -= mu * isg * ds;

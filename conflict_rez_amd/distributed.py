@@ -121,21 +121,6 @@ class VehicleShardedExchange:
         return torch.stack(rows, 1).reshape(-1, self.V - 1, 3, all_pred.shape[-1])
 
 
-def rk4_plant(z, u, dt, wb, substeps=10):
-    """Plant step (`simulator`, dynamic_model.py:61-93) on torch tensors z [B,5], u [B,2]: RK4, `substeps` sub-steps."""
-    import torch
-
-    def f(zz):
-        psi, v, de = zz[:, 2], zz[:, 3], zz[:, 4]
-        return torch.stack([v * torch.cos(psi), v * torch.sin(psi), v / wb * torch.tan(de), u[:, 0], u[:, 1]], 1)
-
-    h = dt / substeps
-    for _ in range(substeps):
-        k1 = f(z); k2 = f(z + 0.5 * h * k1); k3 = f(z + 0.5 * h * k2); k4 = f(z + h * k3)
-        z = z + h / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
-    return z
-
-
 class VehicleShardedLoop:
     """Closed loop of partitioning B on GPUs: this rank owns `exchange.owned` vehicles of its shard of the scenarios; every
     MPC iteration all-gathers the owned predictions inside the rank's exchange group (RCCL) and then runs ONE call of
