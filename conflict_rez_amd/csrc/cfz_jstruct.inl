@@ -1094,7 +1094,7 @@ CFZP_FN int jstruct_solve(const CSpec &sp, const CDims &d, const CWork &w, const
     if (jbcr_lu_all(wv, nwv, 0, Nm, (const cfzb::glb_f64 *)s.Ds, (const cfzb::glb_f64 *)s.Us, (cfzb::glb_f64 *)s.Zs, (cfzb::glb_f64 *)s.Zb, lb) && CFZS_LANE == 0) flag[0] = 1.0;
     __syncthreads();
     if (flag[0] != 0.0) return 1;
-    if (wv < 2) s.xs[wv * kJB + CFZS_LANE] = s.Zs[(28 + wv) * kJB + CFZS_LANE];
+    for (int c = wv; c < 2; c += nwv) s.xs[c * kJB + CFZS_LANE] = s.Zs[(28 + c) * kJB + CFZS_LANE];  // (a workgroup of one wavefront copies both)
     __syncthreads();
     for (int st = top; st >= 1; st /= 2) {
       jbcr_back_all(wv, nwv, st, Nm, (const cfzb::glb_f64 *)s.Us, (const cfzb::glb_f64 *)s.Zs, (const cfzb::glb_f64 *)s.Zb, (const cfzb::glb_f64 *)s.Lc, (cfzb::glb_f64 *)s.xs);
