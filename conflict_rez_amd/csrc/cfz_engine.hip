@@ -23,6 +23,8 @@
 //                  from the caller; the two share the __device__ function prep_stage
 //   audit_kernel   signed distances, first contact and arrivals along a recorded trajectory (cfz_audit.inl), one
 //                  wavefront per scenario, each against the obstacles of its own map
+//   score_kernel   what every vehicle's recorded closed loop cost against its plan (cfz_score.inl: the reference's objective
+//                  :263-272 along the trajectory driven, waiting, reversals, fallback runs :501-524), one wavefront per scenario
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
@@ -50,6 +52,7 @@
 #include "../../include/confrez_hip.h"
 #include "cfz_solver.inl"
 #include "cfz_audit.inl"
+#include "cfz_score.inl"
 #include "cfz_disturb.inl"
 #include "cfz_comm.inl"
 #include "cfz_common.h"
@@ -637,6 +640,66 @@ __global__ __launch_bounds__(64) void audit_kernel(const KArgs *__restrict__ ka,
     cfz::audit_merge(acc, o);
   }
   if (lane == 0) cfz::audit_store(acc, V, clear + (size_t)s * 2, where + (size_t)s * 6, first_contact + s, arrive + (size_t)s * V);
+}
+
+// ---- score of a recorded closed loop (cfz_score.inl) -----------------------------------------------------------------
+// One wavefront per scenario.  Vehicle v owns the L = score_group(V) lanes [v L, (v + 1) L), lane j of them the contiguous steps
+// [j C, min((j + 1) C, K)), C = ceil(K / L); lanes past V L and lanes with an empty chunk hold the identity and take part in every
+// shuffle.  Pass 1: the arrival, a minimum over the group.  Pass 2: every lane summarises its chunk cut at upto; a __shfl_xor butterfly
+// over off = 1 .. L / 2 merges the summaries with the LOWER lane as the left (earlier) operand, so every lane of a group ends with the
+// same total and the floating-point sums are added in one fixed tree: the same bits on every run.  traj[K][S][V][7] from the window's
+// first step, cs its headings (audit_headings); status / iters point at the window's first step, steps si_stride apart (NULL: all 0);
+// tables[P][V][T][7], table_of[S]; the window's k0 of scenario s is k0[s] - back.  val[S][V][kScoreNVal], cnt[S][V][kScoreNCnt],
+// stored by the group's first lane with plain stores.
+__global__ __launch_bounds__(64) void score_kernel(const KArgs *__restrict__ ka, int K, int S, int V, const double *traj, const double *cs,
+                                                   const int32_t *status, const int32_t *iters, long si_stride, int T,
+                                                   const double *tables, const int32_t *table_of, const int32_t *k0, int back, double il0,
+                                                   double il1, double pos_tol, double psi_tol, double v_tol, double near2, double *val,
+                                                   int32_t *cnt) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  const int L = cfz::score_group(V);
+  int v = 0;
+  while ((v + 1) * L <= lane) ++v;
+  const int j = lane - v * L;
+  const bool active = v < V;
+  cfz::ScoreIn in;
+  in.K = K; in.V = V; in.v = active ? v : 0; in.T = T;
+  in.k0 = k0[s] - back;
+  if (in.k0 < 0) in.k0 = 0;
+  in.traj = traj + (size_t)s * V * 7; in.cs = cs + (size_t)s * V * 2;
+  in.plan = tables + ((size_t)table_of[s] * V + in.v) * T * 7;
+  in.step_stride = (long)S * V * 7; in.si_stride = si_stride;
+  in.status = status ? status + (size_t)s * V + in.v : nullptr;
+  in.iters = iters ? iters + (size_t)s * V + in.v : nullptr;
+  for (int i = 0; i < 4; ++i) in.g[i] = ka->sp.g[i];
+  in.il[0] = il0; in.il[1] = il1;
+  in.pos_tol = pos_tol; in.psi_tol = psi_tol; in.v_tol = v_tol; in.near2 = near2;
+  int t0, t1;
+  cfz::score_lane_chunk(K, L, j, t0, t1);
+  if (!active) t0 = t1 = K;
+  int arrive = cfz::score_arrive_chunk(in, t0, t1);
+  for (int off = 1; off < L; off <<= 1) {
+    const int o = __shfl_xor(arrive, off, 64);
+    arrive = o < arrive ? o : arrive;
+  }
+  if (arrive == INT32_MAX) arrive = -1;
+  cfz::ScoreSeg a;
+  cfz::score_chunk(a, in, t0, t1, arrive);
+  for (int off = 1; off < L; off <<= 1) {
+    cfz::ScoreSeg o;
+    for (int i = 0; i < cfz::kScoreNSum; ++i) o.sum[i] = __shfl_xor(a.sum[i], off, 64);
+    o.dev2 = __shfl_xor(a.dev2, off, 64); o.dev_t = __shfl_xor(a.dev_t, off, 64);
+    o.failed = __shfl_xor(a.failed, off, 64); o.run_n = __shfl_xor(a.run_n, off, 64); o.run_pre = __shfl_xor(a.run_pre, off, 64);
+    o.run_suf = __shfl_xor(a.run_suf, off, 64); o.run_best = __shfl_xor(a.run_best, off, 64);
+    o.rv_first = __shfl_xor(a.rv_first, off, 64); o.rv_last = __shfl_xor(a.rv_last, off, 64); o.rv_count = __shfl_xor(a.rv_count, off, 64);
+    o.waiting = __shfl_xor(a.waiting, off, 64); o.near_steps = __shfl_xor(a.near_steps, off, 64);
+    o.first_near = __shfl_xor(a.first_near, off, 64);
+    o.iters_sum = __shfl_xor(a.iters_sum, off, 64); o.iters_max = __shfl_xor(a.iters_max, off, 64);
+    if (lane & off) { cfz::score_merge(o, a); a = o; }  // the partner is the lower lane: its segment is the earlier one
+    else cfz::score_merge(a, o);
+  }
+  if (active && j == 0)
+    cfz::score_store(a, K, arrive, val + ((size_t)s * V + v) * cfz::kScoreNVal, cnt + ((size_t)s * V + v) * cfz::kScoreNCnt);
 }
 
 }  // namespace
@@ -1315,6 +1378,35 @@ int audit_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const
   return 0;
 }
 
+// the score of K steps of S scenarios x V vehicles that lie on the device (score_kernel); val, cnt are the caller's host arrays
+int score_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const int32_t *d_status, const int32_t *d_iters, long si_stride,
+                 int T, const double *d_tables, const int32_t *d_table_of, const int32_t *d_k0, int back, double pos_tol, double psi_tol,
+                 double v_tol, double near, double *val, int32_t *cnt) {
+  static_assert(cfz::kScoreNVal == CFZ_SCORE_NVAL && cfz::kScoreNCnt == CFZ_SCORE_NCNT, "cfz_score.inl and confrez_hip.h disagree");
+  const double *g = h->ks.g;
+  const long n = (long)K * S * V;
+  const size_t B = (size_t)S * V;
+  double *dcs = nullptr, *dv = nullptr;
+  int32_t *dc = nullptr;
+  ARENA_ALLOC(h->arena, dcs, (size_t)n * 2 * 8); ARENA_ALLOC(h->arena, dv, B * CFZ_SCORE_NVAL * 8); ARENA_ALLOC(h->arena, dc, B * CFZ_SCORE_NCNT * 4);
+  hipLaunchKernelGGL(audit_headings, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, d_traj, dcs);
+  HIP_OK(hipGetLastError());
+  hipLaunchKernelGGL(score_kernel, dim3(S), dim3(64), 0, h->stream, h->kargs, K, S, V, d_traj, dcs, d_status, d_iters, si_stride, T, d_tables,
+                     d_table_of, d_k0, back, 1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), pos_tol, psi_tol, v_tol, near * near, dv, dc);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipMemcpyAsync(val, dv, B * CFZ_SCORE_NVAL * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipMemcpyAsync(cnt, dc, B * CFZ_SCORE_NCNT * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// what both score entry points refuse before they look at the handle
+int score_args(double near, const double *val, const int32_t *cnt) {
+  if (!(near >= 0.0) || !std::isfinite(near)) return fail("near must be finite and not negative");
+  if (!val || !cnt) return fail("null val or cnt");
+  return 0;
+}
+
 // What the pool kernels take, composed from the two per-scenario settings: one KArgs block per (problem, map) pair that some scenario
 // uses, in the order of first use, and the block of every scenario.  probs[P], problem_of[S] as cfz_loop_set_problems fills them (probs
 // NULL: the handle's problem for every scenario); map_tab[M][n_obs][20] (device), map_of[S] as cfz_loop_set_maps does (map_tab NULL: the
@@ -1489,6 +1581,48 @@ int cfz_audit_maps(cfz_handle *h, int K, int S, int V, const double *traj, const
     HIP_OK(hipMemcpyAsync(dof, map_of, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
   }
   return audit_launch(h, K, S, V, dt_, dg, dpoly, dof, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);  // (ends synchronised: `poly` outlives its copy)
+}
+
+int cfz_loop_score(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double near, double *val, int32_t *cnt) {
+  if (score_args(near, val, cnt)) return -1;
+  if (loop_ready(h)) return -1;
+  if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  const int S = h->lp.S, V = h->ks.n_nbr + 1;
+  const size_t B = (size_t)S * V;
+  if (arena_reset(h->arena)) return -1;
+  // the clock stands rec_used - t0 steps after the state before step t0 (every recorded step advanced it by one)
+  const int32_t *si = h->lp.rec_si + (size_t)t0 * 2 * B;
+  return score_launch(h, K, S, V, h->lp.rec + (size_t)t0 * B * 7, si, si + B, (long)(2 * B), h->lp.T, h->lp.ref_table, h->lp.table_of, h->lp.kidx,
+                      h->lp.rec_used - t0, pos_tol, psi_tol, v_tol, near, val, cnt);
+}
+
+int cfz_score(cfz_handle *h, int K, int S, int V, const double *traj, const int32_t *status, const int32_t *iters, int P, int T,
+              const double *tables, const int32_t *table_of, const int32_t *k0, double pos_tol, double psi_tol, double v_tol, double near,
+              double *val, int32_t *cnt) {
+  if (score_args(near, val, cnt)) return -1;
+  if (K < 1 || S < 1 || V < 1 || V > CFZ_MAX_NBR + 1) return fail("K, S must be positive and V in 1..CFZ_MAX_NBR+1");
+  if (P < 1 || T < 1) return fail("P, T must be positive");
+  if (!traj || !tables || !table_of || !k0) return fail("null trajectory, tables, table_of or k0");
+  if ((size_t)K * S * V * 7 > ((size_t)1 << 31)) return fail("trajectory too large");
+  if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
+  for (int s = 0; s < S; ++s) {
+    if (table_of[s] < 0 || table_of[s] >= P) return fail("table_of[s] outside [0, P)");
+    if (k0[s] < 0) return fail("k0[s] must not be negative");
+  }
+  if (!h) return fail("null handle");
+  HIP_OK(hipSetDevice(h->device));
+  if (arena_reset(h->arena)) return -1;
+  const size_t B = (size_t)S * V, nt = (size_t)K * B * 7 * 8, np = (size_t)P * V * T * 7 * 8;
+  double *dt_ = nullptr, *dp = nullptr;
+  int32_t *dof = nullptr, *dk = nullptr, *dst = nullptr, *dit = nullptr;
+  ARENA_ALLOC(h->arena, dt_, nt); ARENA_ALLOC(h->arena, dp, np); ARENA_ALLOC(h->arena, dof, (size_t)S * 4); ARENA_ALLOC(h->arena, dk, (size_t)S * 4);
+  HIP_OK(hipMemcpyAsync(dt_, traj, nt, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(dp, tables, np, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(dof, table_of, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_OK(hipMemcpyAsync(dk, k0, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
+  if (status) { ARENA_ALLOC(h->arena, dst, (size_t)K * B * 4); HIP_OK(hipMemcpyAsync(dst, status, (size_t)K * B * 4, hipMemcpyHostToDevice, h->stream)); }
+  if (iters) { ARENA_ALLOC(h->arena, dit, (size_t)K * B * 4); HIP_OK(hipMemcpyAsync(dit, iters, (size_t)K * B * 4, hipMemcpyHostToDevice, h->stream)); }
+  return score_launch(h, K, S, V, dt_, dst, dit, (long)B, T, dp, dof, dk, 0, pos_tol, psi_tol, v_tol, near, val, cnt);  // (ends synchronised)
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {

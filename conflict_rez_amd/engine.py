@@ -189,6 +189,10 @@ def load_library(path=None):
     lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.cfz_loop_audit.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.cfz_audit.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    if hasattr(lib, "cfz_loop_score"):
+        lib.cfz_loop_score.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
+        lib.cfz_score.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, vp, vp]
     _lib = lib
     return lib
 
@@ -197,11 +201,50 @@ EXPORTS = (
     "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
-    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps"
+    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps "
+    "cfz_loop_score cfz_score"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
 ARRIVE_TOL = dict(pos_tol=0.3, psi_tol=0.1, v_tol=0.1)
+
+# columns of the score's raw arrays, in the order of include/confrez_hip.h (CFZ_SCORE_NVAL, CFZ_SCORE_NCNT)
+SCORE_VAL = ("dx2", "dy2", "psi2", "a2", "vw2", "delta2", "da2", "dw2", "absv", "dev2_max")
+SCORE_CNT = ("steps", "arrive", "failed", "fail_run", "reversals", "waiting", "near_steps", "first_near", "iters_sum", "iters_max", "dev_max_step")
+
+
+def score_summary(val, cnt, dt, weights):
+    """The score of a closed loop from the raw arrays of `cfz_loop_score` / `cfz_score`: val [S,V,10], cnt [S,V,11], the time step dt
+    and the six weights of the reference's objective (`ProblemSpec.weights`: x, y, psi, a, v w, delta), [6] or one row per scenario [S,6]
+    -> dict of every column by name (`SCORE_VAL`, `SCORE_CNT`), each [S,V], and
+    cost = weights . (dx2, dy2, psi2, a2, vw2, delta2); track_rms = sqrt((dx2 + dy2) / steps), track_max = sqrt(dev2_max) [m];
+    time = dt steps, distance = dt absv, wait = dt waiting."""
+    val, cnt = np.asarray(val, dtype=np.float64), np.asarray(cnt)
+    if val.ndim != 3 or val.shape[2] != len(SCORE_VAL) or cnt.shape != val.shape[:2] + (len(SCORE_CNT),):
+        raise ValueError(f"expected val [S, V, {len(SCORE_VAL)}] and cnt [S, V, {len(SCORE_CNT)}], got {val.shape} and {cnt.shape}")
+    S = val.shape[0]
+    w = np.asarray(weights, dtype=np.float64)
+    if w.shape not in ((6,), (S, 6)):
+        raise ValueError(f"weights must have shape (6,) or ({S}, 6), got {w.shape}")
+    w = np.broadcast_to(w, (S, 6))
+    out = {name: val[..., i] for i, name in enumerate(SCORE_VAL)}
+    out.update({name: cnt[..., i] for i, name in enumerate(SCORE_CNT)})
+    out["cost"] = (val[..., :6] * w[:, None, :]).sum(-1)
+    out["track_rms"] = np.sqrt((out["dx2"] + out["dy2"]) / out["steps"])
+    out["track_max"] = np.sqrt(out["dev2_max"])
+    out["time"] = dt * out["steps"]
+    out["distance"] = dt * out["absv"]
+    out["wait"] = dt * out["waiting"]
+    return out
+
+
+def _score_args(near, tol):
+    """(pos_tol, psi_tol, v_tol, near) of a score call as floats: the tolerances default to ARRIVE_TOL, unknown names are refused."""
+    unknown = set(tol) - set(ARRIVE_TOL)
+    if unknown:
+        raise TypeError(f"unknown tolerance(s) {sorted(unknown)}: expected {sorted(ARRIVE_TOL)}")
+    t = {**ARRIVE_TOL, **tol}
+    return float(t["pos_tol"]), float(t["psi_tol"]), float(t["v_tol"]), float(near)
 
 
 def _options(struct_type, default_fn_name, what, options):
@@ -847,6 +890,46 @@ class Engine:
         self._ck(self.lib.cfz_audit_maps(self._h, K, S, V, _ptr(traj), _ptr(goal), M, _ptr(A), _ptr(b), _ptr(mo), float(pos_tol), float(psi_tol),
                                          float(v_tol), _ptr(o["clear"]), _ptr(o["where"]), _ptr(o["first_contact"]), _ptr(o["arrive"])), "cfz_audit_maps")
         return o
+
+    def loop_score(self, t0=0, K=None, near=0.5, weights=None, **tol):
+        """`cfz_loop_score` over recorded steps [t0, t0 + K) (K None: all recorded so far): what every vehicle's realised closed loop
+        cost against the plan it follows -> the dict of `score_summary` (every raw column by name, cost, track_rms, track_max, time,
+        distance, wait; each [S,V]).  near [m]: the distance to another body below which a step counts in `near_steps`; weights [6] or
+        [S,6] (None: the engine's `spec.weights`); pos_tol, psi_tol, v_tol as `loop_audit`."""
+        args = _score_args(near, tol)
+        K = self._rec_used - int(t0) if K is None else int(K)
+        S, V = self._S, self._V
+        val, cnt = np.empty((S, V, len(SCORE_VAL))), np.empty((S, V, len(SCORE_CNT)), np.int32)
+        self._ck(self.lib.cfz_loop_score(self._h, int(t0), K, *args, _ptr(val), _ptr(cnt)), "cfz_loop_score")
+        return score_summary(val, cnt, self.spec.dt, self.spec.weights if weights is None else weights)
+
+    def score(self, traj, tables, table_of, k0, status=None, iters=None, near=0.5, weights=None, **tol):
+        """`cfz_score` of a host record traj [K,S,V,7] (with status, iters [K,S,V]; None: all 0: what `loop_history` returns) against
+        the plan sets tables [P,V,T,7], scenario s following set table_of[s] from the clock index k0[s] of the state before the first
+        row; this engine's body, any V up to 8 -> the dict of `loop_score`."""
+        args = _score_args(near, tol)
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        if traj.ndim != 4 or traj.shape[3] != 7:
+            raise ValueError(f"expected traj of shape [K, S, V, 7], got {traj.shape}")
+        K, S, V = traj.shape[:3]
+        tables = np.ascontiguousarray(tables, dtype=np.float64)
+        if tables.ndim != 4 or tables.shape[1] != V or tables.shape[3] != 7:
+            raise ValueError(f"expected tables of shape [P, {V}, T, 7], got {tables.shape}")
+        P, T = tables.shape[0], tables.shape[2]
+        ints = []
+        for name, a, shape in (("table_of", table_of, (S,)), ("k0", k0, (S,)), ("status", status, (K, S, V)), ("iters", iters, (K, S, V))):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.int32)
+                if a.shape != shape:
+                    raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+            ints.append(a)
+        tof, k0, status, iters = ints
+        if tof is None or k0 is None:
+            raise ValueError("table_of and k0 are required")
+        val, cnt = np.empty((S, V, len(SCORE_VAL))), np.empty((S, V, len(SCORE_CNT)), np.int32)
+        self._ck(self.lib.cfz_score(self._h, K, S, V, _ptr(traj), _ptr(status), _ptr(iters), P, T, _ptr(tables), _ptr(tof), _ptr(k0), *args,
+                                    _ptr(val), _ptr(cnt)), "cfz_score")
+        return score_summary(val, cnt, self.spec.dt, self.spec.weights if weights is None else weights)
 
     def loop_last_converged(self):
         """Solves of the last `loop_run` that converged (status 0)."""

@@ -9,6 +9,10 @@
    first (order, delays) combination that gives the strategy; `Engine.loop_set_order`) instead of the reference's Jacobi exchange.
 5. One row per strategy: plans converged, share of converged MPC solves, smallest vehicle / obstacle clearance, scenarios with
    contact, arrival step p50 / max.
+6. One `Engine.loop_score()` call on the same record: what every realised loop cost (the reference's objective along the trajectory
+   driven, time to arrive, time spent waiting, changes of direction, steps within 0.5 m of another body).  The rows gain the medians
+   over the strategy's scenarios, and a closing table ranks the contact-free strategies by (median makespan, median cost).  The same
+   columns computed with numpy from `loop_history()` are timed next to it.
    --noise-levels 0,0.5,1,2: every (strategy, start) runs once per level in the same launch, disturbed by level x NOISE_SIGMA
    (`Engine.loop_set_disturbance`: measurement, actuator and process noise drawn on the device); the replicas of a start share one
    stream id, so the levels are compared on common random numbers.  The table gains the share of scenarios with contact per level.
@@ -68,6 +72,44 @@ def replicate(k0, noise, tof, levels=None, rates=None, dmins=None, margins=None)
             S = len(out["k0"])
             tile(len(values))
             out[name] = np.repeat(np.asarray(values, dtype), S)
+    return out
+
+
+def host_score(hist, tables, tof, k0, dt, weights, pos_tol=0.3, psi_tol=0.1, v_tol=0.1):
+    """What a user computed on the host before `Engine.loop_score`: the score's columns (all but near_steps / first_near, which need the
+    bodies' signed distances) from `loop_history()` with numpy, vectorised over scenarios and vehicles.  Timed against the device
+    in main() and compared with it."""
+    traj, bad, it = hist["traj"], hist["status"] != 0, hist["iters"]
+    K, S, V = traj.shape[:3]
+    T = tables.shape[2]
+    wrap = lambda e: e - 2 * np.pi * np.rint(e / (2 * np.pi))  # noqa: E731
+    rows = np.minimum(k0[None, :] + np.arange(K)[:, None] + 1, T - 1)
+    r = tables[tof[None, :, None], np.arange(V)[None, None, :], rows[:, :, None]]  # [K, S, V, 7]
+    goal = tables[tof, :, -1]
+    at = (((traj[..., 0] - goal[..., 0]) ** 2 + (traj[..., 1] - goal[..., 1]) ** 2 <= pos_tol ** 2) & (np.abs(wrap(traj[..., 2] - goal[..., 2])) <= psi_tol)
+          & (np.abs(traj[..., 3]) <= v_tol))
+    arrive = np.where(at.any(0), at.argmax(0), -1)
+    steps = np.where(arrive >= 0, arrive + 1, K)
+    t = np.arange(K)[:, None, None]
+    live = t < steps[None]
+    dx2, dy2, dp2 = (traj[..., 0] - r[..., 0]) ** 2, (traj[..., 1] - r[..., 1]) ** 2, wrap(traj[..., 2] - r[..., 2]) ** 2
+    dev2 = np.where(live, dx2 + dy2, -1.0)
+    out = dict(steps=steps, arrive=arrive, dx2=(dx2 * live).sum(0), dy2=(dy2 * live).sum(0), psi2=(dp2 * live).sum(0),
+               a2=(traj[..., 5] ** 2 * live).sum(0), vw2=((traj[..., 3] * traj[..., 6]) ** 2 * live).sum(0), delta2=(traj[..., 4] ** 2 * live).sum(0),
+               da2=(np.diff(traj[..., 5], axis=0) ** 2 * live[1:]).sum(0), dw2=(np.diff(traj[..., 6], axis=0) ** 2 * live[1:]).sum(0),
+               absv=(np.abs(traj[..., 3]) * live).sum(0), dev2_max=dev2.max(0), dev_max_step=dev2.argmax(0), failed=(bad & live).sum(0),
+               iters_sum=(it * live).sum(0), iters_max=(it * live).max(0),
+               waiting=((np.abs(traj[..., 3]) <= v_tol) & live & (t != arrive[None])).sum(0))
+    run, best, last, rev = (np.zeros((S, V), np.int64) for _ in range(4))
+    for k in range(K):  # the two ordered columns: one pass over the steps
+        run = np.where(bad[k] & live[k], run + 1, 0)
+        best = np.maximum(best, run)
+        sg = np.where(live[k] & (np.abs(traj[k, ..., 3]) > v_tol), np.sign(traj[k, ..., 3]), 0).astype(np.int64)
+        rev += (sg != 0) & (last != 0) & (sg != last)
+        last = np.where(sg != 0, sg, last)
+    out.update(fail_run=best, reversals=rev)
+    out["cost"] = sum(w * out[n] for w, n in zip(weights, ("dx2", "dy2", "psi2", "a2", "vw2", "delta2")))
+    out["time"], out["distance"], out["wait"] = dt * steps, dt * out["absv"], dt * out["waiting"]
     return out
 
 
@@ -156,12 +198,32 @@ def main():
     t0 = time.perf_counter()
     aud = eng.loop_audit()
     sync(); t_audit = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    sc = eng.loop_score()
+    sync(); t_score = time.perf_counter() - t0
+    t0 = time.perf_counter()
     hist = eng.loop_history()
+    t_hist = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    hsc = host_score(hist, plan["tables"], tof, k0, spec.dt, spec.weights)
+    t_host = time.perf_counter() - t0
+    for n, hv in hsc.items():  # the device against the host's numpy: integers equal, sums to rounding
+        assert np.array_equal(sc[n], hv) if np.issubdtype(np.asarray(hv).dtype, np.integer) else np.allclose(sc[n], hv, rtol=1e-9, atol=1e-12), n
     print(f"closed loop: {S} scenarios x {V} vehicles x {K} steps in one launch, {t_loop:.2f} s; audit {t_audit * 1e3:.1f} ms"
           + ("; sequential exchange in each strategy's planning priority" if a.exchange == "sequential" else ""))
+    print(f"score {t_score * 1e3:.1f} ms on the device (cfz_loop_score, the call with its read-back); the same columns without near_steps on the host: "
+          f"loop_history {t_hist * 1e3:.1f} ms + numpy {t_host * 1e3:.1f} ms (equal integers, sums to rounding)")
+    # per scenario: the time of the last arrival (nan unless every vehicle arrived), the cost, waiting time, reversals and near steps over its vehicles
+    makespan = np.where((sc["arrive"] >= 0).all(1), sc["time"].max(1), np.nan)
+    cost, wait, revs, near = sc["cost"].sum(1), sc["wait"].sum(1), sc["reversals"].sum(1), sc["near_steps"].sum(1)
+
+    def med(x, sel):
+        x = x[sel]
+        return float(np.nanmedian(x)) if len(x) and not np.isnan(x).all() else float("nan")
 
     print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}"
-          + "".join(f" {'c@%g' % l:>6}" for l in levels or []))
+          + "".join(f" {'c@%g' % l:>6}" for l in levels or [])
+          + f" {'mksp s':>7} {'cost':>9} {'wait s':>7} {'revs':>5} {'near':>5}")
     no_contact = []
     for p in range(P):
         row = f"{p:5d} {len(combos[p]):6d} {int((plan['colloc_status'][p] == 0).sum()):3d}/{V}"
@@ -177,26 +239,34 @@ def main():
         n_sel = int(sel.sum())  # M starts x noise levels x drop rates x clearances x margins
         print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{n_sel:<2d} "
               f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
-              + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or []))
+              + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or [])
+              + f" {med(makespan, sel):7.1f} {med(cost, sel):9.1f} {med(wait, sel):7.1f} {med(revs, sel):5.0f} {med(near, sel):5.0f}")
         if n_contact == 0:
             no_contact.append(p)
+    for l in levels or []:
+        print(f"noise level {l:g}: median cost {med(cost, lvl == l):.1f}")
     for r in rates or []:
         sel = drop == r
         free = int((aud["first_contact"][sel] < 0).sum())
         print(f"drop rate {r:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
-              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
+              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged; median cost {med(cost, sel):.1f}")
     for i, d in enumerate(dmins or []):
         sel = pof == i
         free = int((aud["first_contact"][sel] < 0).sum())
         print(f"dmin {d:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
-              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
+              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged; median cost {med(cost, sel):.1f}")
     for i, m in enumerate(margins or []):
         sel = mof == i
         free = int((aud["first_contact"][sel] < 0).sum())
         print(f"obstacle margin {m:g}: {free} of {int(sel.sum())} closed loops contact-free; smallest clearance vehicle-vehicle {aud['clear'][sel, 0].min():.3f}, "
-              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged")
+              f"vehicle-obstacle {aud['clear'][sel, 1].min():.3f}; {float((hist['status'][:, sel] == 0).mean()):.3f} of the solves converged; median cost {med(cost, sel):.1f}")
     print(f"strategies whose {M * len(levels or [1]) * len(rates or [1]) * len(dmins or [1]) * len(margins or [1])} sampled closed loops all finish without contact: {len(no_contact)} of {int(ok.sum())} run: {no_contact}")
-    print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms")
+    print("contact-free strategies by (median makespan, median cost) over their scenarios (median over the scenarios in which every vehicle arrived; nan: none did):")
+    print(f"{'rank':>4} {'strat':>5} {'mksp s':>7} {'cost':>9} {'wait s':>7} {'revs':>5} {'near':>5}")
+    rows = [(med(makespan, tof == p), med(cost, tof == p), p) for p in no_contact]
+    for i, (mk, c, p) in enumerate(sorted(rows, key=lambda r: (np.isnan(r[0]), r[0], r[1]))):
+        print(f"{i + 1:4d} {p:5d} {mk:7.1f} {c:9.1f} {med(wait, tof == p):7.1f} {med(revs, tof == p):5.0f} {med(near, tof == p):5.0f}")
+    print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms, score {t_score * 1e3:.1f} ms")
     eng.close()
 
 

@@ -563,6 +563,44 @@ int cfz_audit_maps(cfz_handle *h, int K, int S, int V, const double *traj, const
                    const double *b_obs /* [M][n_obs][4] */, const int32_t *map_of /* [S] */, double pos_tol, double psi_tol, double v_tol,
                    double *clear, int32_t *where, int32_t *first_contact, int32_t *arrive);
 
+/* ---- score of a realised trajectory --------------------------------------------------------------------------------------
+ * What the closed loop cost, per scenario s and vehicle v over the recorded steps [t0, t0 + K) (step numbers relative to t0).  The audit
+ * above says whether the loop was safe; this measures the reference's own objective along the trajectory actually driven
+ * (vehicle_follower.py:263-272: tracking error, a^2, v^2 w^2, delta^2; the six sums below in the order of cfz_spec.weights), the price
+ * of yielding and how long a vehicle ran on the shift fallback (:501-524; back_up_steps counts the same consecutive failures).
+ * Record row z_t = (x, y, psi, v, delta, a, w) with status_t, iters_t as cfz_loop_history returns them; its plan row is
+ * r_t = plan[min(k0[s] + t + 1, T - 1)], plan[T][7] the vehicle's plan in the set table_of[s] and k0[s] the clock index of the state
+ * before the window's first step (the loop seeds the state at plan[k0] and step t integrates the plant from clock k0 + t to
+ * k0 + t + 1, so a vehicle that follows its plan exactly has z_t = r_t; the clamp is that of the loop's reference window).
+ * arrive is cfz_loop_audit's arrival against the plan's last sample; upto = arrive + 1 if the vehicle arrived, else K.  Every quantity
+ * runs over t < upto: a vehicle that parks early is not charged for standing at its goal.
+ *   val[s][v][0:3]  dx2, dy2, psi2: sum (x - x_r)^2, (y - y_r)^2, wrap(psi - psi_r)^2, wrap(e) = e - 2 pi rint(e (1 / 2 pi))
+ *   val[s][v][3:6]  a2, vw2, delta2: sum a^2, (v w)^2, delta^2
+ *   val[s][v][6:8]  da2, dw2: sum over 1 <= t < upto of (a_t - a_{t-1})^2, (w_t - w_{t-1})^2
+ *   val[s][v][8]    absv: sum |v_t| (dt absv is the distance travelled)
+ *   val[s][v][9]    dev2_max: max_t (x - x_r)^2 + (y - y_r)^2, ties to the lowest step
+ *   cnt[s][v][0:2]  steps = upto, arrive (-1: never)
+ *   cnt[s][v][2:4]  failed: steps with status != 0; fail_run: the longest run of consecutive such steps
+ *   cnt[s][v][4]    reversals: changes of sign in the sequence of sign(v_t) over the steps with |v_t| > v_tol
+ *   cnt[s][v][5]    waiting: steps with |v_t| <= v_tol and (t < arrive or never arrived)
+ *   cnt[s][v][6:8]  near_steps: steps at which the signed distance of this body to any other body of the scenario is < near [m] (bodies
+ *                   that touch count at every near); first_near: the first such step, -1 none
+ *   cnt[s][v][8:10] iters_sum, iters_max of iters_t
+ *   cnt[s][v][10]   dev_max_step: the step of dev2_max
+ * Raw sums: means, roots, dt and the weights are the caller's (conflict_rez_amd/engine.py, score_summary).  One wavefront per scenario;
+ * a vehicle's steps are summed in one fixed tree, so the same record gives the same bits on every run (conflict_rez_amd/csrc/cfz_score.inl).
+ * cfz_loop_score: the handle's record, plan pool, table_of and clock (k0[s] = the clock now minus the steps recorded after t0).
+ * cfz_score: host arrays traj[K][S][V][7], status[K][S][V] and iters[K][S][V] (either NULL: all 0), tables[P][V][T][7], table_of[S],
+ * k0[S]; V in 1..CFZ_MAX_NBR+1 need not be the handle's; the body is the handle's.
+ * Refused: a window outside the record, non-positive sizes, a table_of[s] outside [0, P), a negative k0[s], a negative or non-finite
+ * near, a NULL pointer other than status and iters. */
+#define CFZ_SCORE_NVAL 10
+#define CFZ_SCORE_NCNT 11
+int cfz_loop_score(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double near, double *val, int32_t *cnt);
+int cfz_score(cfz_handle *h, int K, int S, int V, const double *traj, const int32_t *status, const int32_t *iters, int P, int T,
+              const double *tables /* [P][V][T][7] */, const int32_t *table_of /* [S] */, const int32_t *k0 /* [S] */, double pos_tol,
+              double psi_tol, double v_tol, double near, double *val, int32_t *cnt);
+
 const char *cfz_last_error(void);
 /* First 16 hex digits of the SHA-256 over the kernel sources this library was built from (__graft_entry__.source_hash; "unknown" for
  * a build made by hand).  bench.py quotes profiler counters from profiles/ only if they were taken on a library with the same hash. */
