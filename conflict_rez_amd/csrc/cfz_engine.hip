@@ -25,6 +25,8 @@
 //                  wavefront per scenario, each against the obstacles of its own map
 //   score_kernel   what every vehicle's recorded closed loop cost against its plan (cfz_score.inl: the reference's objective
 //                  :263-272 along the trajectory driven, waiting, reversals, fallback runs :501-524), one wavefront per scenario
+//   conflict_kernel  the conflict map of a plan pool (cfz_conflict.inl): body clearance of every pair of plans against their relative
+//                  delay, one workgroup per (set, pair), the pair's columns (conflict_columns) staged in LDS
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
@@ -53,6 +55,7 @@
 #include "cfz_solver.inl"
 #include "cfz_audit.inl"
 #include "cfz_score.inl"
+#include "cfz_conflict.inl"
 #include "cfz_disturb.inl"
 #include "cfz_comm.inl"
 #include "cfz_common.h"
@@ -700,6 +703,61 @@ __global__ __launch_bounds__(64) void score_kernel(const KArgs *__restrict__ ka,
   }
   if (active && j == 0)
     cfz::score_store(a, K, arrive, val + ((size_t)s * V + v) * cfz::kScoreNVal, cnt + ((size_t)s * V + v) * cfz::kScoreNCnt);
+}
+
+// ---- conflict map of a plan pool (cfz_conflict.inl) ------------------------------------------------------------------
+// cols[n / T][4][T]: x, y, cos psi, sin psi of the n = P V T samples of tables[n][7] as columns, one thread per sample (the one place
+// where the conflict map takes a sin / cos: P V T of them, not one per evaluation)
+__global__ void conflict_columns(long n, int T, const double *tables, double *cols) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long v = i / T, t = i - v * T;
+  double s, c;
+  sincos(tables[i * 7 + 2], &s, &c);
+  double *col = cols + v * 4 * T + t;
+  col[0] = tables[i * 7]; col[T] = tables[i * 7 + 1]; col[2 * (long)T] = c; col[3 * (long)T] = s;
+}
+
+// the lags of one wavefront: wave k of the workgroup's four takes lags k, k + 4, ... of the 2 D + 1, its lanes the steps lane, lane + 64, ...
+// of a lag; a __shfl_xor butterfly merges the lanes (conflict_merge: the same result however the steps are dealt out) and lane 0 stores
+// with plain stores.  Forced inline, so that each of its two calls reads U, W in the address space they lie in.
+__device__ __forceinline__ void conflict_lags(int T, int D, const double *U, const double *W, const double g[4], const double il[2],
+                                              double margin, double margin2, double *clear, int32_t *info) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int j = wave; j < 2 * D + 1; j += 4) {
+    cfz::ConflictAcc acc;
+    cfz::conflict_lane(acc, lane, 64, T, j - D, U, W, g, il, margin, margin2);
+    for (int off = 32; off > 0; off >>= 1) {
+      cfz::ConflictAcc o;
+      o.key = __shfl_xor(acc.key, off, 64); o.when = __shfl_xor(acc.when, off, 64);
+      o.first = __shfl_xor(acc.first, off, 64); o.count = __shfl_xor(acc.count, off, 64);
+      cfz::conflict_merge(acc, o);
+    }
+    if (lane == 0) cfz::conflict_store(acc, clear + j, info + (size_t)j * cfz::kConflictNInfo);
+  }
+}
+
+// One workgroup of 256 lanes per (set, pair); blockIdx.x = p npair + q.  staged (T <= kConflictLdsT, 64 T bytes of dynamic LDS): the
+// workgroup copies the eight columns of its two vehicles into LDS once and every lag reads them there; else the same function reads
+// them from global memory (any T).  clear[P][npair][2D+1] as keys (the host takes the root), info[P][npair][2D+1][3].
+__global__ __launch_bounds__(256) void conflict_kernel(const KArgs *__restrict__ ka, int V, int T, int D, int staged, const double *cols,
+                                                       double il0, double il1, double margin, double margin2, double *clear, int32_t *info) {
+  extern __shared__ __attribute__((aligned(16))) double conflict_lds[];
+  const int npair = V * (V - 1) / 2, p = blockIdx.x / npair, q = blockIdx.x - p * npair;
+  int u, w;
+  cfz::conflict_pair(V, q, u, w);
+  const double *U = cols + ((size_t)p * V + u) * 4 * T, *W = cols + ((size_t)p * V + w) * 4 * T;
+  double g[4];
+  for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
+  const double il[2] = {il0, il1};
+  const size_t out = (size_t)blockIdx.x * (2 * D + 1);
+  if (staged) {
+    for (int i = threadIdx.x; i < 4 * T; i += 256) { conflict_lds[i] = U[i]; conflict_lds[4 * T + i] = W[i]; }
+    __syncthreads();
+    conflict_lags(T, D, conflict_lds, conflict_lds + 4 * T, g, il, margin, margin2, clear + out, info + out * cfz::kConflictNInfo);
+  } else {
+    conflict_lags(T, D, U, W, g, il, margin, margin2, clear + out, info + out * cfz::kConflictNInfo);
+  }
 }
 
 }  // namespace
@@ -1407,6 +1465,46 @@ int score_args(double near, const double *val, const int32_t *cnt) {
   return 0;
 }
 
+// the conflict map of P plan sets x V vehicles x T samples that lie on the device (conflict_columns, conflict_kernel); clear, info are
+// the caller's host arrays (either NULL: not wanted).  The arena is reset by the caller.
+int conflict_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, int D, double margin, double *clear, int32_t *info) {
+  static_assert(cfz::kConflictNInfo == CFZ_CONFLICT_NINFO, "cfz_conflict.inl and confrez_hip.h disagree");
+  const int npair = V * (V - 1) / 2;
+  if (npair == 0) return 0;
+  const double *g = h->ks.g;
+  const long n = (long)P * V * T;
+  const size_t no = (size_t)P * npair * (2 * (size_t)D + 1);
+  double *dcol = nullptr, *dc = nullptr;
+  int32_t *di = nullptr;
+  ARENA_ALLOC(h->arena, dcol, (size_t)n * 4 * 8); ARENA_ALLOC(h->arena, dc, no * 8); ARENA_ALLOC(h->arena, di, no * CFZ_CONFLICT_NINFO * 4);
+  hipLaunchKernelGGL(conflict_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, T, d_tables, dcol);
+  HIP_OK(hipGetLastError());
+  const int staged = T <= cfz::kConflictLdsT;
+  hipLaunchKernelGGL(conflict_kernel, dim3((unsigned)(P * npair)), dim3(256), staged ? (size_t)T * 64 : 0, h->stream, h->kargs, V, T, D, staged,
+                     dcol, 1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), margin, margin * margin, dc, di);
+  HIP_OK(hipGetLastError());
+  if (clear) HIP_OK(hipMemcpyAsync(clear, dc, no * 8, hipMemcpyDeviceToHost, h->stream));
+  if (info) HIP_OK(hipMemcpyAsync(info, di, no * CFZ_CONFLICT_NINFO * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  if (clear)
+    for (size_t i = 0; i < no; ++i) clear[i] = cfz::audit_key_distance(clear[i]);
+  return 0;
+}
+
+// what both conflict entry points refuse before they look at the handle
+int conflict_args(int D, double margin) {
+  if (D < 0) return fail("D must not be negative");
+  if (!(margin >= 0.0) || !std::isfinite(margin)) return fail("margin must be finite and not negative");
+  return 0;
+}
+
+// the sizes of a conflict map: every index of the kernels fits an int
+int conflict_sizes(int P, int V, int T, int D) {
+  if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
+  if ((size_t)P * (V * (V - 1) / 2) * (2 * (size_t)D + 1) * CFZ_CONFLICT_NINFO > ((size_t)1 << 31)) return fail("conflict map too large");
+  return 0;
+}
+
 // What the pool kernels take, composed from the two per-scenario settings: one KArgs block per (problem, map) pair that some scenario
 // uses, in the order of first use, and the block of every scenario.  probs[P], problem_of[S] as cfz_loop_set_problems fills them (probs
 // NULL: the handle's problem for every scenario); map_tab[M][n_obs][20] (device), map_of[S] as cfz_loop_set_maps does (map_tab NULL: the
@@ -1623,6 +1721,32 @@ int cfz_score(cfz_handle *h, int K, int S, int V, const double *traj, const int3
   if (status) { ARENA_ALLOC(h->arena, dst, (size_t)K * B * 4); HIP_OK(hipMemcpyAsync(dst, status, (size_t)K * B * 4, hipMemcpyHostToDevice, h->stream)); }
   if (iters) { ARENA_ALLOC(h->arena, dit, (size_t)K * B * 4); HIP_OK(hipMemcpyAsync(dit, iters, (size_t)K * B * 4, hipMemcpyHostToDevice, h->stream)); }
   return score_launch(h, K, S, V, dt_, dst, dit, (long)B, T, dp, dof, dk, 0, pos_tol, psi_tol, v_tol, near, val, cnt);  // (ends synchronised)
+}
+
+int cfz_plan_conflicts(cfz_handle *h, int P, int V, int T, const double *tables, int D, double margin, double *clear, int32_t *info) {
+  if (conflict_args(D, margin)) return -1;
+  if (P < 1 || T < 1) return fail("P, T must be positive");
+  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
+  if (!tables) return fail("null tables");
+  if (conflict_sizes(P, V, T, D)) return -1;
+  if (!h) return fail("null handle");
+  if (V == 1) return 0;  // no pairs: nothing to launch, nothing to write
+  HIP_OK(hipSetDevice(h->device));
+  if (arena_reset(h->arena)) return -1;
+  const size_t nt = (size_t)P * V * T * 7 * 8;
+  double *dt_ = nullptr;
+  ARENA_ALLOC(h->arena, dt_, nt);
+  HIP_OK(hipMemcpyAsync(dt_, tables, nt, hipMemcpyHostToDevice, h->stream));
+  return conflict_launch(h, P, V, T, dt_, D, margin, clear, info);  // (ends synchronised)
+}
+
+int cfz_loop_plan_conflicts(cfz_handle *h, int D, double margin, double *clear, int32_t *info) {
+  if (conflict_args(D, margin)) return -1;
+  if (loop_ready(h)) return -1;
+  const int V = h->ks.n_nbr + 1;
+  if (conflict_sizes(h->lp.P, V, h->lp.T, D)) return -1;
+  if (arena_reset(h->arena)) return -1;
+  return conflict_launch(h, h->lp.P, V, h->lp.T, h->lp.ref_table, D, margin, clear, info);
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {

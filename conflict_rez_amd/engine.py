@@ -193,6 +193,9 @@ def load_library(path=None):
         lib.cfz_loop_score.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
         lib.cfz_score.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double,
                                   C.c_double, vp, vp]
+    if hasattr(lib, "cfz_plan_conflicts"):
+        lib.cfz_plan_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp, vp]
+        lib.cfz_loop_plan_conflicts.argtypes = [vp, C.c_int, C.c_double, vp, vp]
     _lib = lib
     return lib
 
@@ -202,7 +205,7 @@ EXPORTS = (
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
     "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps "
-    "cfz_loop_score cfz_score"
+    "cfz_loop_score cfz_score cfz_plan_conflicts cfz_loop_plan_conflicts"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -245,6 +248,49 @@ def _score_args(near, tol):
         raise TypeError(f"unknown tolerance(s) {sorted(unknown)}: expected {sorted(ARRIVE_TOL)}")
     t = {**ARRIVE_TOL, **tol}
     return float(t["pos_tol"]), float(t["psi_tol"]), float(t["v_tol"]), float(near)
+
+
+def _conflict_args(max_lag, margin, spec):
+    """(D, margin) of a conflict-map call: the window as a non-negative int, margin None meaning the problem's `dmin`."""
+    D = int(max_lag)
+    if D != max_lag or D < 0:
+        raise ValueError(f"max_lag must be a non-negative whole number of samples, got {max_lag!r}")
+    return D, float(spec.dmin if margin is None else margin)
+
+
+def _conflict_out(P, V, D):
+    """The raw arrays of `cfz_plan_conflicts` / `cfz_loop_plan_conflicts`: clear [P, npair, 2D+1], info [P, npair, 2D+1, 3]."""
+    npair = V * (V - 1) // 2
+    return np.full((P, npair, 2 * D + 1), np.inf), np.full((P, npair, 2 * D + 1, 3), -1, np.int32)
+
+
+def _conflict_dict(clear, info, V, D):
+    pairs = np.array([(u, w) for u in range(V) for w in range(u + 1, V)], np.int32).reshape(-1, 2)
+    return dict(clear=clear, when=info[..., 0], first=info[..., 1], count=info[..., 2], pairs=pairs, lags=np.arange(-D, D + 1, dtype=np.int32))
+
+
+def conflict_summary(out):
+    """What a conflict map (`Engine.plan_conflicts`, `Engine.loop_plan_conflicts`) says about every plan set, pure numpy.
+    Per (set, pair) [P, npair]: clear0, the clearance at lag 0; slack_late, the largest m in [0, D] with count == 0 at every lag in
+    [0, m] (how many samples the pair's second vehicle may run late before the plans come within the margin), -1 if lag 0 itself is in
+    conflict; slack_early, likewise on [-m, 0] (the first vehicle late).  Per set [P]: depth = max(0, -min over pairs of clear0), the
+    planned penetration at lag 0; slack, the minimum over pairs of the smaller of slack_late and slack_early; critical_pair [P, 2], the
+    (first) pair that sets it.  Without pairs (V = 1): depth 0, slack D, critical_pair (-1, -1)."""
+    clear, count, pairs = np.asarray(out["clear"], dtype=np.float64), np.asarray(out["count"]), np.asarray(out["pairs"])
+    if clear.ndim != 3 or clear.shape[2] % 2 != 1 or count.shape != clear.shape or pairs.shape != (clear.shape[1], 2):
+        raise ValueError(f"expected clear, count [P, npair, 2D+1] and pairs [npair, 2], got {clear.shape}, {count.shape} and {pairs.shape}")
+    P, npair, D = clear.shape[0], clear.shape[1], clear.shape[2] // 2
+    free = count == 0
+    res = dict(clear0=clear[..., D],
+               slack_late=np.cumprod(free[..., D:], axis=-1).sum(-1).astype(np.int64) - 1,
+               slack_early=np.cumprod(free[..., D::-1], axis=-1).sum(-1).astype(np.int64) - 1)
+    if npair == 0:
+        res.update(depth=np.zeros(P), slack=np.full(P, D, np.int64), critical_pair=np.full((P, 2), -1, np.int32))
+        return res
+    pair_slack = np.minimum(res["slack_late"], res["slack_early"])
+    crit = pair_slack.argmin(1)
+    res.update(depth=np.maximum(0.0, -res["clear0"].min(1)), slack=pair_slack.min(1), critical_pair=pairs[crit])
+    return res
 
 
 def _options(struct_type, default_fn_name, what, options):
@@ -569,6 +615,7 @@ class Engine:
         self.options = dict(options)  # (the base of the overrides of loop_set_problems)
         self._h = C.c_void_p()
         self._S = self._V = 0  # scenarios and vehicles of the closed loop; 0 until loop_init (the library refuses loop calls before it)
+        self._P = 0  # plan sets of the closed loop's pool
         self._rec_cap = self._rec_used = 0
         cs, co = spec.to_c(), default_options(**options)
         _ck(self.lib.cfz_create(C.byref(cs), C.byref(co), int(device), self.max_batch, C.byref(self._h)), "cfz_create")
@@ -698,6 +745,7 @@ class Engine:
             self._ck(self.lib.cfz_loop_init_tables(self._h, S, P, T, _ptr(ref_table), _ptr(tof), _ptr(k0), _ptr(noise)),
                      "cfz_loop_init_tables")
         self._S, self._V = S, V
+        self._P = 1 if ref_table.ndim == 3 else ref_table.shape[0]
         self._rec_cap, self._rec_used = 0, 0
 
     def loop_set_order(self, order):
@@ -930,6 +978,31 @@ class Engine:
         self._ck(self.lib.cfz_score(self._h, K, S, V, _ptr(traj), _ptr(status), _ptr(iters), P, T, _ptr(tables), _ptr(tof), _ptr(k0), *args,
                                     _ptr(val), _ptr(cnt)), "cfz_score")
         return score_summary(val, cnt, self.spec.dt, self.spec.weights if weights is None else weights)
+
+    def plan_conflicts(self, tables, max_lag, margin=None):
+        """`cfz_plan_conflicts`: the conflict map of the plan sets tables [P,V,T,7] (or one set [V,T,7]: P = 1; this engine's body, any
+        V up to 8) over the lags -max_lag..max_lag [samples] -> dict(clear (smallest signed distance of the two bodies), when (the
+        lowest step that attains it), first (the lowest step closer than margin, -1 none), count (the number of such steps), each
+        [P, npair, 2 max_lag + 1]; pairs [npair, 2] (u < w); lags [2 max_lag + 1]).  At lag tau > 0 vehicle w of the pair runs tau
+        samples late, at tau < 0 vehicle u runs |tau| late.  margin [m] None: the problem's `dmin`.  `conflict_summary` condenses it."""
+        D, margin = _conflict_args(max_lag, margin, self.spec)
+        tables = np.ascontiguousarray(tables, dtype=np.float64)
+        if tables.ndim == 3:
+            tables = tables[None]
+        if tables.ndim != 4 or tables.shape[3] != 7 or 0 in tables.shape:
+            raise ValueError(f"expected tables of shape [P, V, T, 7] or [V, T, 7], got {tables.shape}")
+        P, V, T = tables.shape[:3]
+        clear, info = _conflict_out(P, V, D)
+        self._ck(self.lib.cfz_plan_conflicts(self._h, P, V, T, _ptr(tables), D, margin, _ptr(clear), _ptr(info)), "cfz_plan_conflicts")
+        return _conflict_dict(clear, info, V, D)
+
+    def loop_plan_conflicts(self, max_lag, margin=None):
+        """`cfz_loop_plan_conflicts`: `plan_conflicts` of the pool that `loop_init` left on the device (nothing is uploaded, the loop is
+        left as it is) -> the same dict, P the pool's."""
+        D, margin = _conflict_args(max_lag, margin, self.spec)
+        clear, info = _conflict_out(self._P, self._V, D)
+        self._ck(self.lib.cfz_loop_plan_conflicts(self._h, D, margin, _ptr(clear), _ptr(info)), "cfz_loop_plan_conflicts")
+        return _conflict_dict(clear, info, self._V, D)
 
     def loop_last_converged(self):
         """Solves of the last `loop_run` that converged (status 0)."""

@@ -345,6 +345,32 @@ def plan_scenarios(strategies, init_offsets=None, final_headings=None, dt=0.1, p
                 colloc_status=co_status.reshape(sh), colloc_iters=co_iters.reshape(sh), ok=(co_status.reshape(sh) == 0).all(1))
 
 
+def delay_tables(tables, delays):
+    """Plan sets in which some vehicles leave late: tables [V,T,7] or [P,V,T,7] (x, y, psi, v, delta, a, w), delays whole samples >= 0,
+    [V] (the same for every set) or [P,V].  Each vehicle is held for its delay at sample 0 (pose and steering angle kept, v = a = w = 0),
+    then follows its plan, then repeats its last sample up to the common length T + max(delays) -> tables of that length, shaped as
+    given: what `Engine.loop_init` takes.  Lag tau of `Engine.plan_conflicts` for the pair (u, w) is this with delays[w] = tau (tau > 0)
+    or delays[u] = -tau, at lag 0."""
+    tables = np.asarray(tables, dtype=np.float64)
+    single = tables.ndim == 3
+    tab = tables[None] if single else tables
+    if tab.ndim != 4 or tab.shape[3] != 7 or 0 in tab.shape:
+        raise ValueError(f"expected tables of shape [P, V, T, 7] or [V, T, 7], got {tables.shape}")
+    P, V, T = tab.shape[:3]
+    d = np.asarray(delays)
+    if d.dtype.kind not in "iu":
+        raise ValueError(f"delays must be whole numbers of samples, got dtype {d.dtype}")
+    if d.shape not in ((V,), (P, V)):
+        raise ValueError(f"delays must have shape ({V},) or ({P}, {V}), got {d.shape}")
+    if (d < 0).any():
+        raise ValueError("delays must not be negative")
+    d = np.broadcast_to(d, (P, V))
+    idx = np.clip(np.arange(T + int(d.max()))[None, None, :] - d[:, :, None], -1, T - 1)  # [P, V, T']; -1: still waiting
+    out = np.take_along_axis(tab, np.maximum(idx, 0)[..., None], axis=2)
+    out[..., [3, 5, 6]] = np.where((idx < 0)[..., None], 0.0, out[..., [3, 5, 6]])
+    return out[0] if single else out
+
+
 def distinct_strategies(n_vehicles=4, delays=(0, 1, 2)):
     """The distinct strategies `strategy.generate_strategy` gives over every priority order x start delays in delays^n (infeasible
     combinations skipped), in the order first met.  Returns (strategies, combos): combos[i] lists the (order, delays) that give

@@ -28,11 +28,18 @@
    value, `scenarios.grow_obstacles`); the replicas of a start share its stream ids.  The plans stay those of the reference map: the
    question is how much room those plans leave.  The audit measures every replica against its own map; contact-free starts and the
    smallest clearances are printed per margin.
+7. --lags D: before the loop is run, one `Engine.loop_plan_conflicts(D)` call on the pool the loop was given: the body clearance of every
+   pair of plans of every strategy against their relative delay, -D..D samples (`engine.conflict_summary`).  The rows gain the planned
+   penetration depth at lag 0, the critical pair and its slack (how many samples either vehicle of that pair may run late before the
+   plans come within dmin; -1: they do already); next to the closing ranking, how many of the strategies whose plans overlap had contact
+   in closed loop against those whose plans are clear.  The same map from a vectorised numpy statement is timed next to it, three
+   repeats each.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
                                               [--noise-levels L0,L1,...] [--noise-seed SEED]
                                               [--drop-rates P0,P1,...] [--max-age A] [--no-compensate] [--comm-seed SEED]
                                               [--dmin D0,D1,...] [--obstacle-margins M0,M1,...]
+                                              [--lags D]
 """
 import argparse
 import dataclasses
@@ -113,6 +120,47 @@ def host_score(hist, tables, tof, k0, dt, weights, pos_tol=0.3, psi_tol=0.1, v_t
     return out
 
 
+def _signed_distance(A, B):
+    """Signed distance of rectangles A, B [..., 4, 2] (corners in order): the distance if they are disjoint, else minus the penetration
+    depth; separating axes over the face normals of both, vertex-edge distances otherwise."""
+    best = None
+    for F in (A, B):
+        e = F[..., 1:3, :] - F[..., 0:2, :]  # two adjacent edges: the two face normals of a rectangle
+        n = np.stack([e[..., 1], -e[..., 0]], -1) / np.linalg.norm(e, axis=-1)[..., None]
+        ha, hb = np.einsum("...vk,...ek->...ev", A, n), np.einsum("...vk,...ek->...ev", B, n)
+        o = np.minimum(ha.max(-1) - hb.min(-1), hb.max(-1) - ha.min(-1)).min(-1)
+        best = o if best is None else np.minimum(best, o)
+    d2 = None
+    for F, G in ((A, B), (B, A)):
+        e = np.roll(G, -1, axis=-2) - G
+        w = F[..., :, None, :] - G[..., None, :, :]
+        t = np.clip((w * e[..., None, :, :]).sum(-1) / (e * e).sum(-1)[..., None, :], 0.0, 1.0)
+        r = w - t[..., None] * e[..., None, :, :]
+        m = (r * r).sum(-1).min((-1, -2))
+        d2 = m if d2 is None else np.minimum(d2, m)
+    return np.where(best >= 0.0, -np.maximum(best, 0.0) + 0.0, np.sqrt(d2))
+
+
+def host_conflicts(tables, D, margin, g):
+    """What a user computed on the host before `Engine.plan_conflicts`: the conflict map of tables [P,V,T,7] with numpy, one band
+    statement per lag, vectorised over plan sets, pairs and steps -> dict(clear, when, first, count [P, npair, 2D+1]) and d, per lag
+    the distances [P, npair, T + |lag|] they were taken from.  Timed against the device in main() and compared with it."""
+    P, V, T = tables.shape[:3]
+    BV = np.array([[g[0], g[1]], [-g[2], g[1]], [-g[2], -g[3]], [g[0], -g[3]]])
+    c, s = np.cos(tables[..., 2])[..., None], np.sin(tables[..., 2])[..., None]
+    W = np.stack([tables[..., 0, None] + c * BV[:, 0] - s * BV[:, 1], tables[..., 1, None] + s * BV[:, 0] + c * BV[:, 1]], -1)  # [P, V, T, 4, 2]
+    us, ws = np.triu_indices(V, 1)  # the pairs in the audit's order
+    out = dict(clear=[], when=[], first=[], count=[], d=[])
+    for tau in range(-D, D + 1):
+        i = np.arange(T + abs(tau))
+        iu, iw = np.clip(i - max(-tau, 0), 0, T - 1), np.clip(i - max(tau, 0), 0, T - 1)
+        d = _signed_distance(W[:, us][:, :, iu], W[:, ws][:, :, iw])
+        below = d < margin
+        out["clear"].append(d.min(-1)); out["when"].append(d.argmin(-1)); out["count"].append(below.sum(-1))
+        out["first"].append(np.where(below.any(-1), below.argmax(-1), -1)); out["d"].append(d)
+    return {k: (v if k == "d" else np.stack(v, -1)) for k, v in out.items()}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--starts", type=int, default=16, help="sampled starts per strategy")
@@ -134,6 +182,8 @@ def main():
     ap.add_argument("--obstacle-margins", type=lambda t: [float(x) for x in t.split(",")], default=None,
                     help="comma-separated margins [m] by which every obstacle face is moved outwards, e.g. 0,0.1,0.2: one replica of every start per "
                          "value, in one launch, on the plans of the reference map")
+    ap.add_argument("--lags", type=int, default=None, metavar="D",
+                    help="window of the plans' conflict map in samples, e.g. 40: body clearance of every pair of plans at relative delays -D..D")
     a = ap.parse_args()
 
     import torch
@@ -191,6 +241,30 @@ def main():
         eng.loop_set_problems([dataclasses.replace(spec, dmin=d) for d in dmins], pof)
     if margins:
         eng.loop_set_maps([scenarios.grow_obstacles(spec, m) for m in margins], mof)
+    cs = None
+    if a.lags is not None:
+        t_dev, t_np = [], []
+        for _ in range(3):  # (three repeats each: the spread is printed with the median)
+            sync(); t0 = time.perf_counter()
+            cm = eng.loop_plan_conflicts(a.lags)
+            sync(); t_dev.append(time.perf_counter() - t0)
+        for _ in range(3):  # (three repeats each: the spread is printed with the median)
+            t0 = time.perf_counter()
+            hcm = host_conflicts(plan["tables"], a.lags, spec.dmin, spec.g)
+            t_np.append(time.perf_counter() - t0)
+        # the device against the host's numpy: distances to rounding, integers equal; the step of the minimum is one at which numpy's
+        # distance is its minimum to rounding (a vehicle that waits or is parked gives runs of steps at the very same distance)
+        # (over the strategies that are run: what is left of a plan that did not converge need not be finite)
+        assert np.abs(cm["clear"][sets] - hcm["clear"][sets]).max() <= 1e-12
+        assert np.array_equal(cm["first"][sets], hcm["first"][sets]) and np.array_equal(cm["count"][sets], hcm["count"][sets])
+        for j, d in enumerate(hcm["d"]):
+            at_when = np.take_along_axis(d[sets], cm["when"][sets][..., j, None].astype(np.int64), -1)[..., 0]
+            assert (np.abs(at_when - hcm["clear"][sets][..., j]) <= 1e-12).all(), j
+        cs = engine.conflict_summary(cm)
+        fmt = lambda ts: f"{np.median(ts) * 1e3:.2f} ms (min {min(ts) * 1e3:.2f}, max {max(ts) * 1e3:.2f} of {len(ts)})"  # noqa: E731
+        print(f"conflict map of the plans: {P} sets x {V * (V - 1) // 2} pairs x {2 * a.lags + 1} lags x {plan['tables'].shape[2]}+ steps, margin dmin = {spec.dmin:g} m: "
+              f"{fmt(t_dev)} on the device (cfz_loop_plan_conflicts, the call with its read-back); the same map with numpy on the host: {fmt(t_np)} "
+              f"(distances within 1e-12, equal integers)")
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -223,7 +297,8 @@ def main():
 
     print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}"
           + "".join(f" {'c@%g' % l:>6}" for l in levels or [])
-          + f" {'mksp s':>7} {'cost':>9} {'wait s':>7} {'revs':>5} {'near':>5}")
+          + f" {'mksp s':>7} {'cost':>9} {'wait s':>7} {'revs':>5} {'near':>5}"
+          + (f" {'depth m':>7} {'crit':>5} {'slack':>5}" if cs else ""))
     no_contact = []
     for p in range(P):
         row = f"{p:5d} {len(combos[p]):6d} {int((plan['colloc_status'][p] == 0).sum()):3d}/{V}"
@@ -240,7 +315,8 @@ def main():
         print(row + f" {conv:6.3f} {aud['clear'][sel, 0].min():8.3f} {aud['clear'][sel, 1].min():8.3f} {n_contact:4d}/{n_sel:<2d} "
               f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
               + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or [])
-              + f" {med(makespan, sel):7.1f} {med(cost, sel):9.1f} {med(wait, sel):7.1f} {med(revs, sel):5.0f} {med(near, sel):5.0f}")
+              + f" {med(makespan, sel):7.1f} {med(cost, sel):9.1f} {med(wait, sel):7.1f} {med(revs, sel):5.0f} {med(near, sel):5.0f}"
+              + (f" {cs['depth'][p]:7.3f} {'%d-%d' % tuple(cs['critical_pair'][p]):>5} {cs['slack'][p]:5d}" if cs else ""))
         if n_contact == 0:
             no_contact.append(p)
     for l in levels or []:
@@ -266,6 +342,12 @@ def main():
     rows = [(med(makespan, tof == p), med(cost, tof == p), p) for p in no_contact]
     for i, (mk, c, p) in enumerate(sorted(rows, key=lambda r: (np.isnan(r[0]), r[0], r[1]))):
         print(f"{i + 1:4d} {p:5d} {mk:7.1f} {c:9.1f} {med(wait, tof == p):7.1f} {med(revs, tof == p):5.0f} {med(near, tof == p):5.0f}")
+    if cs:
+        ran = np.flatnonzero(ok)
+        deep, free = ran[cs["depth"][ran] > 0], ran[cs["depth"][ran] == 0]
+        hit = lambda ps: sum(int(p) not in no_contact for p in ps)  # noqa: E731
+        print(f"plans against closed loops: {hit(deep)} of the {len(deep)} strategies whose plans overlap at lag 0 (planned depth > 0) had contact in closed loop, "
+              f"{hit(free)} of the {len(free)} whose plans do not; smallest slack over the strategies run {int(cs['slack'][ran].min())}, largest {int(cs['slack'][ran].max())} samples")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms, score {t_score * 1e3:.1f} ms")
     eng.close()
 

@@ -601,6 +601,39 @@ int cfz_score(cfz_handle *h, int K, int S, int V, const double *traj, const int3
               const double *tables /* [P][V][T][7] */, const int32_t *table_of /* [S] */, const int32_t *k0 /* [S] */, double pos_tol,
               double psi_tol, double v_tol, double near, double *val, int32_t *cnt);
 
+/* ---- conflict map of a set of plans ---------------------------------------------------------------------------------------
+ * Body clearance of every pair of plans against their relative delay, before any closed loop is run.  The audit and the score above
+ * inspect a loop that was driven, in which all vehicles of a scenario share one clock; this inspects the plans themselves and shifts the
+ * clock of one vehicle of a pair against the other's.
+ * Inputs: tables[P][V][T][7], a pool of plan sets as cfz_loop_init_tables takes it (rows x, y, psi, ...; only those three are read); a
+ * window D >= 0 in samples; margin >= 0 in metres.
+ * Pairs q = (u, w), u < w, in the audit's order (0,1), (0,2), ..., (1,2), ...; npair = V (V - 1) / 2.  Lag tau in [-D, D] is stored at
+ * index tau + D.  tau > 0: w runs tau samples late; tau < 0: u runs |tau| samples late.  A late vehicle waits at its first sample; a
+ * vehicle past its plan stays at its last sample.  For step i in [0, T + |tau|):
+ *   iu  = clamp(i - max(-tau, 0), 0, T - 1)
+ *   iw  = clamp(i - max( tau, 0), 0, T - 1)
+ *   d_i = signed distance of the handle's body rectangle at tables[p][u][iu][0:3] and at tables[p][w][iw][0:3]: the Euclidean distance
+ *         if the bodies are disjoint, else minus the penetration depth (0 when they only touch), as the audit's clear.
+ *   clear[p][q][tau + D]    min_i d_i (+inf if every d_i is NaN)
+ *   info[p][q][tau + D][0]  when: the lowest i that attains it (-1 if every d_i is NaN)
+ *   info[p][q][tau + D][1]  first: the lowest i with d_i < margin, -1 if there is none
+ *   info[p][q][tau + D][2]  count: the number of such i
+ * The comparison with margin is made without a root, on the key that the kernel minimises (the squared distance of disjoint bodies, minus
+ * the depth otherwise): disjoint bodies count when key < margin^2, touching or overlapping bodies when key < margin, so bodies that only
+ * touch count at every margin > 0 and at margin = 0 exactly the overlapping ones do.  A d_i within rounding of margin may fall on
+ * either side.
+ * One workgroup per (set, pair); minima are taken under the total order (d, i), counts are integers: the same tables give the same bits on
+ * every run (conflict_rez_amd/csrc/cfz_conflict.inl).
+ * cfz_plan_conflicts: host tables; V in 1..CFZ_MAX_NBR+1 need not be the handle's, the body is the handle's; V = 1 has no pairs: it
+ * returns 0, launches nothing and writes nothing.  cfz_loop_plan_conflicts: the pool that cfz_loop_init* left on the device, P, V, T
+ * its own; nothing is uploaded and the loop's state, clock and record are left untouched.  Either output may be NULL.
+ * Refused: non-positive P, V or T, V above CFZ_MAX_NBR+1, D < 0, a negative or non-finite margin, NULL tables, sizes whose outputs
+ * would pass 2^31 entries, the loop form before cfz_loop_init*.  What needs no handle is checked before the handle is looked at. */
+#define CFZ_CONFLICT_NINFO 3 /* when, first, count */
+int cfz_plan_conflicts(cfz_handle *h, int P, int V, int T, const double *tables /* [P][V][T][7] */, int D, double margin,
+                       double *clear /* [P][npair][2D+1] */, int32_t *info /* [P][npair][2D+1][3] */);
+int cfz_loop_plan_conflicts(cfz_handle *h, int D, double margin, double *clear, int32_t *info);
+
 const char *cfz_last_error(void);
 /* First 16 hex digits of the SHA-256 over the kernel sources this library was built from (__graft_entry__.source_hash; "unknown" for
  * a build made by hand).  bench.py quotes profiler counters from profiles/ only if they were taken on a library with the same hash. */
