@@ -259,13 +259,15 @@ __global__ __launch_bounds__(1024) void order_by_iters(int B, const int32_t *ite
 //   ctrl[1] items completed   ctrl[2] error flag
 //   done[S]       finished vehicles of the scenario (monotone: iteration t is complete at (t+1)*V)
 //   pred[2][B][7][N] double-buffered by iteration parity (read t%2, write (t+1)%2)
-// Hand-offs between workgroups follow the agent-scope release/acquire recipe: payload stores, __threadfence()
-// (release), device-scope atomic; consumer: atomic load of the slot, __threadfence() (acquire), payload loads.
+// Hand-offs between workgroups follow the agent-scope publish/acquire recipe in its write-through form: the payload (prediction row,
+// state, carry record) is stored write-through at agent scope (cfz::store_shared), every storing wavefront waits for its stores, the
+// workgroup meets, one lane signals by device-scope atomics; consumer: atomic load of the slot, agent-scope acquire fence, plain
+// payload loads.  No item writes the XCD's L2 back: the spill frames of the workgroups resident there stay in it.
 // The pop has no lane-divergent control flow (all lanes issue the same loads; atomics add 1 from lane 0 and 0 from
 // the others): a value defined under `if (lane == 0)` and broadcast afterwards was miscompiled by hipcc 7.2.
 // CFZ_LOOP_TRACE (diagnostic builds, tools/build_variant.sh): CFZ_MARK leaves every workgroup's last phase for the watchdog;
 // CFZ_ITEM_STAMP writes item (t, b)'s record of kLoopTraceWords 64-bit words: the constant 100 MHz clock after the pop [0], at the start [1]
-// and the end [2] of the solve and after the release [3], and 1 + whether the item ran prioritised [4] (0: the item never ran).
+// and the end [2] of the solve and after the hand-off [3], and 1 + whether the item ran prioritised [4] (0: the item never ran).
 // tools/loop_priority_trace.py reads them through cfz_loop_trace_read.  Neither exists in the product build.
 #ifdef CFZ_LOOP_TRACE
 constexpr int kLoopTraceWords = 5;
@@ -284,8 +286,8 @@ __device__ long long *cfz_loop_trace_buf;
 // after another: the item of rank r publishes the item of rank r + 1 into the same queue t, the last rank publishes rank 0 of
 // t + 1.  Every iteration still receives exactly B slots, so the ticket rules above hold unchanged.  A vehicle reads the neighbours
 // ranked before it from the output parity at stage k (iteration t's predictions start at time t), the others from the input
-// parity, advanced.  The new edge, rank r to rank r + 1, has the same release / acquire pair as the edge from t to t + 1, and the
-// chain of such pairs covers the ranks below r - 1 as well (release / acquire is transitive).
+// parity, advanced.  The new edge, rank r to rank r + 1, has the same publish / acquire pair as the edge from t to t + 1, and the
+// chain of such pairs covers the ranks below r - 1 as well (their payload reached memory before their own signal).
 // It cannot deadlock: a scenario has exactly one item in flight, every completion publishes exactly one item, and the workgroup
 // that completed is then free to take it; the grid (at most S workgroups) never exceeds the items in flight.
 // Two kernels, one body (cfz_loop_body.inl, included into both): loop_kernel keeps its symbol (profiles and bench.py name rows

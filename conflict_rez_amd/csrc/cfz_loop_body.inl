@@ -73,7 +73,7 @@
     CFZ_MARK(2);
     CFZ_ITEM_STAMP(0, pr);
     // Both wavefronts of a prioritised item take issue priority over the wavefronts they share their SIMDs with (VALU issue is
-    // arbitrated by priority, then age), the others give way.  Lowered again below, after the release.
+    // arbitrated by priority, then age), the others give way.  Lowered again below, after the hand-off.
     if (pr) __builtin_amdgcn_s_setprio(3);
     const int s = b / V, v = b - s * V;
     // kPool: the constants of the scenario's problem, pool[problem_of[s]], in place of the handle's block; the index is the same in
@@ -139,7 +139,7 @@
     CFZ_ITEM_STAMP(1, 0);
     int oi[2]; double od[3];
     cfz::DualOut duo = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    cfz::solve_instance(spi, dvi, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
+    cfz::solve_instance<true>(spi, dvi, nullptr, ref, nullptr, nullptr, smem, L, oi, od, duo, wst ? wst + (size_t)b * wst_stride : nullptr, 1, 2);
     __syncthreads();
     CFZ_MARK(4);
     CFZ_ITEM_STAMP(2, 0);
@@ -147,7 +147,7 @@
     for (int i = tid; i < 7 * N; i += cfz::kNL) {
       const int c = i / N, k = i - c * N;
       const int ka = (k + 1 < N) ? k + 1 : N - 1;
-      pout[(size_t)b * 7 * N + i] = (oi[1] == 0) ? smem[L.p + k * cfz::kNP + c] : pin[((size_t)b * 7 + c) * N + ka];
+      cfz::store_shared(pout + (size_t)b * 7 * N + i, (oi[1] == 0) ? smem[L.p + k * cfz::kNP + c] : pin[((size_t)b * 7 + c) * N + ka]);
     }
     CFZ_MARK(5);
     if (tid == 0) {
@@ -168,27 +168,30 @@
       cfz::rk4_step<false>(z, a0, w0, sp.dt, sp.wb, kPlantSubsteps, out, nullptr);
       if (kDist)
         for (int i = 0; i < 5; ++i) out[i] = cfz::disturb_add(out[i], dn[2 + i]);
-      for (int i = 0; i < 5; ++i) state[b * 5 + i] = out[i];
-      status[b] = oi[1]; iters[b] = oi[0];
+      for (int i = 0; i < 5; ++i) cfz::store_shared(state + b * 5 + i, out[i]);
+      // status, iters and stats are read after the launch only, but every iteration of the launch rewrites them, from another XCD as a
+      // rule: written through as well, or an older iteration's dirty line, written back later, would overwrite the newer value
+      cfz::store_shared(status + b, (int32_t)oi[1]); cfz::store_shared(iters + b, (int32_t)oi[0]);
       if (rec) {
         double *r = rec + ((size_t)t * B + b) * 7;
         for (int i = 0; i < 5; ++i) r[i] = out[i];
         r[5] = a0; r[6] = w0;
         rec_si[(size_t)t * 2 * B + b] = oi[1]; rec_si[(size_t)(t * 2 + 1) * B + b] = oi[0];
       }
-      stats[b * 3] = od[0]; stats[b * 3 + 1] = od[1]; stats[b * 3 + 2] = od[2];
+      for (int i = 0; i < 3; ++i) cfz::store_shared(stats + b * 3 + i, od[i]);
       atomicAdd(iter_sum, oi[0]);
       if (oi[1] == 0) atomicAdd(iter_sum + 1, 1);  // converged solves of this launch
       atomicAdd(iter_sum + 2 + (oi[1] < 0 ? 0 : (oi[1] > 5 ? 5 : oi[1])), 1);  // ... and how every solve of it ended (status 0..5)
     }
-    // release: prediction and state of (s, v, t).  Every storing wavefront drains its stores, the workgroup meets, one
-    // lane writes the XCD's L2 back and only then signals (the asm wait keeps the compiler from dropping the drain).
+    // release: prediction, state and carry record of (s, v, t), the three things another workgroup reads in this launch, were stored
+    // write-through (cfz::store_shared), so no write-back of the XCD's L2 is needed -- it would sweep out every resident workgroup's
+    // spill frames with them.  Every storing wavefront waits for its stores (the asm wait: the compiler does not count on it and
+    // cannot drop it), the workgroup meets, and only then one lane signals, by atomics.  rec and rec_si are written once per item and
+    // read after the launch: plain stores.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     CFZ_MARK(6);
     if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const int c = atomicAdd(&done[s], 1);
       if (kSeq) {  // completions of a scenario are serialised: c % V is this item's rank; publish exactly one item
         const int r = c % V;

@@ -46,6 +46,23 @@
 #define CFZ_LPS 4
 #endif
 namespace cfz {
+// A store of a value that ANOTHER workgroup reads later in the same launch (the persistent closed loop: prediction rows, states, carry
+// records): written through the XCD's L2 at agent scope, so that the hand-off needs no write-back of that L2 -- the item's release is
+// then: every storing wavefront waits for its stores (s_waitcnt vmcnt(0)), the workgroup meets, one lane signals by an atomic; the
+// reader's agent-scope acquire stays.  The CPU builds: a plain store.
+template <typename T>
+#if defined(__HIPCC__)
+__host__ __device__ __forceinline__
+#else
+static inline
+#endif
+void store_shared(T *p, T v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __hip_atomic_store((__attribute__((address_space(1))) T *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+  *p = v;
+#endif
+}
 constexpr int kLPS = CFZ_LPS;  // lanes per stage: 4 (a DPP quad, two wavefronts per instance) or 8 (half a DPP row, four wavefronts)
 static_assert(kLPS == 4 || kLPS == 8, "lanes per stage");
 constexpr int kLPSBits = kLPS == 4 ? 2 : 3;
@@ -82,6 +99,10 @@ constexpr int kXS = 7;              // values one workgroup reduction can carry 
 #define CFZ_WSP(p) (p)
 #define CFZ_UNIFORM(v) (v)
 #endif
+
+// The carry record's stores in solve_instance<PUB>: published in the persistent loop's instantiation, else the plain store of the
+// kernels whose results are read after the launch (a compile-time choice: their code is that of the plain statement alone).
+#define CFZ_CARRY_STORE(lhs, val) { if (PUB) cfz::store_shared(&(lhs), (val)); else (lhs) = (val); }
 
 // Diagnostic build only (-DCFZ_STAMPS): shader-clock cycles per phase of the solver, summed over the
 // iterations of one instance and written to a debug buffer (never to an output).
@@ -1603,6 +1624,9 @@ CFZ_FN CarryLay carry_layout(int N, int nb) {
 // preloaded != 0 (the persistent loop): the caller has already put the measured state (L.x0), the neighbours' poses with
 // cos / sin (L.nb4) and the warm start (L.p) into the workspace and reads the solution from L.p afterwards; x0g, nbrg and zu
 // are then not touched (zu may be null).
+// PUB (the persistent loop, with preloaded == 2): the carry record's next reader is another workgroup of the same launch, so every
+// store to it is a store_shared.
+template <bool PUB = false>
 CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, const double *refg, const double *nbrg, double *zu,
                            double *m, const Lay &L, int *out_i, double *out_d, const DualOut &duo, double *wst = nullptr,
                            int carry_in = 0, int preloaded = 0) {
@@ -1668,7 +1692,7 @@ CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, c
   }
   if (!merged && (worst0 < sp.dmin - sp.constr_viol_tol || x0_out)) {
     out_i[0] = 0; out_i[1] = 4; out_d[0] = 0.0; out_d[1] = INFINITY; out_d[2] = worst0;
-    if (wst) { CFZ_LANES(tid) if (tid == 0) wst[CL.valid] = 0.0; CFZ_END }
+    if (wst) { CFZ_LANES(tid) if (tid == 0) CFZ_CARRY_STORE(wst[CL.valid], 0.0); CFZ_END }
     return;
   }
   const bool warm = wst != nullptr && carry_in != 0 && CFZ_UNIFORM(wst[CL.valid]) != 0.0;
@@ -1723,7 +1747,7 @@ CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, c
     worst0 = ro[0];
     if (worst0 < sp.dmin - sp.constr_viol_tol || x0_out) {
       out_i[0] = 0; out_i[1] = 4; out_d[0] = 0.0; out_d[1] = INFINITY; out_d[2] = worst0;
-      if (wst) { CFZ_LANES(tid) if (tid == 0) wst[CL.valid] = 0.0; CFZ_END }
+      if (wst) { CFZ_LANES(tid) if (tid == 0) CFZ_CARRY_STORE(wst[CL.valid], 0.0); CFZ_END }
       return;
     }
   }
@@ -2376,15 +2400,15 @@ CFZ_FN void solve_instance(const KSpec &sp, const KDer &dv, const double *x0g, c
   if (wst) {  // leave the multipliers for the next MPC iteration of this vehicle, or say that there are none
     CFZ_LANES(tid)
       if (status == 0) {
-        for (int i = tid; i < N * nr; i += kNL) wst[CL.z + i] = m[L.zs + i];
-        for (int i = tid; i < N * 6; i += kNL) { wst[CL.zl + i] = m[L.zl + i]; wst[CL.zu + i] = m[L.zu + i]; }
-        for (int i = tid; i < N * 5; i += kNL) wst[CL.pi + i] = i < (N - 1) * 5 ? m[L.pi + i] : 0.0;
-        if (tid < 5) wst[CL.pi0 + tid] = m[L.pi0 + tid];
+        for (int i = tid; i < N * nr; i += kNL) CFZ_CARRY_STORE(wst[CL.z + i], m[L.zs + i]);
+        for (int i = tid; i < N * 6; i += kNL) { CFZ_CARRY_STORE(wst[CL.zl + i], m[L.zl + i]); CFZ_CARRY_STORE(wst[CL.zu + i], m[L.zu + i]); }
+        for (int i = tid; i < N * 5; i += kNL) CFZ_CARRY_STORE(wst[CL.pi + i], i < (N - 1) * 5 ? m[L.pi + i] : 0.0);
+        if (tid < 5) CFZ_CARRY_STORE(wst[CL.pi0 + tid], m[L.pi0 + tid]);
         unsigned char *ws = reinterpret_cast<unsigned char *>(wst + CL.sel);
-        for (int i = tid; i < N * nb; i += kNL) ws[i] = sel_ptr(m, L)[i];
-        if (tid == 0) { wst[CL.mu] = mu; wst[CL.valid] = 1.0; wst[CL.shifted] = shifted_any ? 1.0 : 0.0; }
+        for (int i = tid; i < N * nb; i += kNL) CFZ_CARRY_STORE(ws[i], sel_ptr(m, L)[i]);
+        if (tid == 0) { CFZ_CARRY_STORE(wst[CL.mu], mu); CFZ_CARRY_STORE(wst[CL.valid], 1.0); CFZ_CARRY_STORE(wst[CL.shifted], shifted_any ? 1.0 : 0.0); }
       } else if (tid == 0) {
-        wst[CL.valid] = 0.0;
+        CFZ_CARRY_STORE(wst[CL.valid], 0.0);
       }
     CFZ_END
   }
