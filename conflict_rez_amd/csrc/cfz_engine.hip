@@ -27,6 +27,8 @@
 //                  :263-272 along the trajectory driven, waiting, reversals, fallback runs :501-524), one wavefront per scenario
 //   conflict_kernel  the conflict map of a plan pool (cfz_conflict.inl): body clearance of every pair of plans against their relative
 //                  delay, one workgroup per (set, pair), the pair's columns (conflict_columns) staged in LDS
+//   delay_kernel   the start delays that make a plan set conflict-free, searched over that map (cfz_delay.inl): one workgroup per set,
+//                  the windowed free mask as bits in LDS, span levels in ascending order
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
@@ -56,6 +58,7 @@
 #include "cfz_audit.inl"
 #include "cfz_score.inl"
 #include "cfz_conflict.inl"
+#include "cfz_delay.inl"
 #include "cfz_disturb.inl"
 #include "cfz_comm.inl"
 #include "cfz_common.h"
@@ -759,6 +762,67 @@ __global__ __launch_bounds__(256) void conflict_kernel(const KArgs *__restrict__
     conflict_lags(T, D, conflict_lds, conflict_lds + 4 * T, g, il, margin, margin2, clear + out, info + out * cfz::kConflictNInfo);
   } else {
     conflict_lags(T, D, U, W, g, il, margin, margin2, clear + out, info + out * cfz::kConflictNInfo);
+  }
+}
+
+// ---- start delays that resolve a conflict map (cfz_delay.inl) ---------------------------------------------------------
+// ints per set of delay_kernel's output block: delays[V], info[3], a pad to an even count, rclear as two ints
+__host__ __device__ constexpr int delay_out_ints(int V) { return ((V + cfz::kDelayNInfo + 1) & ~1) + 2; }
+
+// One workgroup of 256 lanes per plan set; blockIdx.x = p.  count[P][npair][2D+1] with entries cs ints apart (1: a caller's map; 3 and the
+// pointer at column 2: conflict_kernel's info), clear[P][npair][2D+1] or NULL (as conflict_kernel leaves it or as the caller holds it: only
+// finiteness and order are read), cap[P][V] or NULL.  npair delay_words(D) words of dynamic LDS: under (D+1)^V <= 2^31 at most 11,588 B.
+//   staging  a lane per (pair, lag) evaluates the window of slack r, a __ballot packs 32 lanes into a word of the pair's row;
+//   shells   spans m = 0, 1, ... up to the largest cap, the candidates of a shell dealt round-robin over the lanes, merged by a
+//            __shfl_xor butterfly per wavefront and a four-entry exchange in LDS that every lane reads after a barrier: the decision to
+//            stop is workgroup-uniform, no barrier sits in divergent control flow;
+//   stores   lane 0, plain stores, into one block of outputs: out[P][delay_out_ints(V)], per set the delays, info[3], a pad where V is even
+//            and rclear as a double (an even number of ints per set: every rclear is aligned).
+__global__ __launch_bounds__(256) void delay_kernel(int V, int D, int r, const int32_t *count, int cs, const double *clear, const int32_t *cap,
+                                                    int32_t *out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t delay_lds[];
+  __shared__ int xch[2][4][2];  // (total, idx) of the four wavefronts, one buffer per parity of the shell
+  const int p = blockIdx.x, npair = V * (V - 1) / 2, L = 2 * D + 1, nw = cfz::delay_words(D), tid = threadIdx.x;
+  const int32_t *cnt = count + (size_t)p * npair * L * cs;
+  const double *clr = clear ? clear + (size_t)p * npair * L : nullptr;
+  const int nbit = npair * nw * 32;
+  for (int base = 0; base < nbit; base += 256) {  // (every lane takes every round: the ballot is over whole wavefronts)
+    const int i = base + tid, q = i / (nw * 32), j = i - q * (nw * 32);
+    const bool f = i < nbit && j < L && cfz::delay_window_free(cnt + (size_t)q * L * cs, cs, clr ? clr + (size_t)q * L : nullptr, D, r, j);
+    const unsigned long long b = __ballot(f);
+    if ((tid & 31) == 0 && i < nbit) delay_lds[i >> 5] = (uint32_t)(b >> (tid & 32));
+  }
+  cfz::DelayVec capv;
+  cfz::delay_pack(V, cap ? cap + (size_t)p * V : nullptr, D, capv);
+  int maxcap = 0;
+  for (int v = 0; v < V; ++v) maxcap = max(maxcap, cfz::delay_digit(capv, v));
+  __syncthreads();
+  cfz::DelayAcc best;
+  cfz::delay_clear(best);
+  int m = 0;
+  for (; m <= maxcap; ++m) {
+    cfz::DelayShell sh;
+    cfz::delay_shell(V, m, sh);
+    cfz::DelayAcc acc;
+    cfz::delay_lane(acc, tid, 256, V, D, m, sh, capv, delay_lds, nw);
+    for (int off = 32; off > 0; off >>= 1) {
+      cfz::DelayAcc o;
+      o.total = __shfl_xor(acc.total, off, 64); o.idx = __shfl_xor(acc.idx, off, 64);
+      cfz::delay_merge(acc, o);
+    }
+    int(*x)[2] = xch[m & 1];  // (the other buffer may still be read by a wavefront that has not left the previous shell)
+    if ((tid & 63) == 0) { x[tid >> 6][0] = acc.total; x[tid >> 6][1] = acc.idx; }
+    __syncthreads();
+    for (int k = 0; k < 4; ++k) {
+      cfz::DelayAcc o;
+      o.total = x[k][0]; o.idx = x[k][1];
+      cfz::delay_merge(best, o);
+    }
+    if (best.total != INT32_MAX) break;  // (the same for every lane)
+  }
+  if (tid == 0) {
+    int32_t *o = out + (size_t)p * delay_out_ints(V);
+    cfz::delay_store(best, V, D, m, clr, o, o + V, (double *)(o + delay_out_ints(V) - 2));
   }
 }
 
@@ -1467,17 +1531,15 @@ int score_args(double near, const double *val, const int32_t *cnt) {
   return 0;
 }
 
-// the conflict map of P plan sets x V vehicles x T samples that lie on the device (conflict_columns, conflict_kernel); clear, info are
-// the caller's host arrays (either NULL: not wanted).  The arena is reset by the caller.
-int conflict_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, int D, double margin, double *clear, int32_t *info) {
+// the conflict map of P plan sets x V vehicles x T samples (V > 1) that lie on the device (conflict_columns, conflict_kernel), left on the
+// device: dc[P][npair][2D+1] as keys, di[P][npair][2D+1][3], from the arena, which the caller has reset.  Nothing is waited for.
+int conflict_device(cfz_handle *h, int P, int V, int T, const double *d_tables, int D, double margin, double *&dc, int32_t *&di) {
   static_assert(cfz::kConflictNInfo == CFZ_CONFLICT_NINFO, "cfz_conflict.inl and confrez_hip.h disagree");
   const int npair = V * (V - 1) / 2;
-  if (npair == 0) return 0;
   const double *g = h->ks.g;
   const long n = (long)P * V * T;
   const size_t no = (size_t)P * npair * (2 * (size_t)D + 1);
-  double *dcol = nullptr, *dc = nullptr;
-  int32_t *di = nullptr;
+  double *dcol = nullptr;
   ARENA_ALLOC(h->arena, dcol, (size_t)n * 4 * 8); ARENA_ALLOC(h->arena, dc, no * 8); ARENA_ALLOC(h->arena, di, no * CFZ_CONFLICT_NINFO * 4);
   hipLaunchKernelGGL(conflict_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, T, d_tables, dcol);
   HIP_OK(hipGetLastError());
@@ -1485,6 +1547,18 @@ int conflict_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, 
   hipLaunchKernelGGL(conflict_kernel, dim3((unsigned)(P * npair)), dim3(256), staged ? (size_t)T * 64 : 0, h->stream, h->kargs, V, T, D, staged,
                      dcol, 1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), margin, margin * margin, dc, di);
   HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// the same map into the caller's host arrays clear, info (either NULL: not wanted), clear as signed distances.  The arena is reset by
+// the caller.
+int conflict_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, int D, double margin, double *clear, int32_t *info) {
+  const int npair = V * (V - 1) / 2;
+  if (npair == 0) return 0;
+  const size_t no = (size_t)P * npair * (2 * (size_t)D + 1);
+  double *dc = nullptr;
+  int32_t *di = nullptr;
+  if (conflict_device(h, P, V, T, d_tables, D, margin, dc, di)) return -1;
   if (clear) HIP_OK(hipMemcpyAsync(clear, dc, no * 8, hipMemcpyDeviceToHost, h->stream));
   if (info) HIP_OK(hipMemcpyAsync(info, di, no * CFZ_CONFLICT_NINFO * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
@@ -1505,6 +1579,70 @@ int conflict_sizes(int P, int V, int T, int D) {
   if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
   if ((size_t)P * (V * (V - 1) / 2) * (2 * (size_t)D + 1) * CFZ_CONFLICT_NINFO > ((size_t)1 << 31)) return fail("conflict map too large");
   return 0;
+}
+
+// what the three delay entry points refuse before they look at the handle: the slack, the outputs, the box of the search and the caps
+// cap[P][V] (NULL: D for every vehicle)
+int delay_args(int P, int V, int D, int slack, const int32_t *cap, const int32_t *delays) {
+  static_assert(cfz::kDelayNInfo == CFZ_DELAY_NINFO && cfz::kDelayMaxV == CFZ_MAX_NBR + 1, "cfz_delay.inl and confrez_hip.h disagree");
+  if (slack < 0) return fail("slack must not be negative");
+  if (!delays) return fail("null delays");
+  double box = 1.0;
+  for (int v = 0; v < V; ++v) box *= D + 1.0;
+  if (box > 2147483648.0) return fail("search space too large: (D+1)^V must not exceed 2^31");
+  if (cap)
+    for (size_t i = 0; i < (size_t)P * V; ++i)
+      if (cap[i] < 0 || cap[i] > D) return fail("a cap lies outside [0, D]");
+  return 0;
+}
+
+// the answer of a set without pairs (V = 1): found, delay 0; rclear +inf where a map of clearances is given
+void delay_single(int P, bool with_clear, int32_t *delays, int32_t *info, double *rclear) {
+  for (int p = 0; p < P; ++p) {
+    delays[p] = 0;
+    if (info) { info[3 * p] = 1; info[3 * p + 1] = info[3 * p + 2] = 0; }
+    if (with_clear && rclear) rclear[p] = INFINITY;
+  }
+}
+
+// delay_kernel over a map on the device (V > 1): d_count with entries cs ints apart, d_clear or NULL (keys: the caller's rclear is
+// converted to a signed distance as conflict_launch converts the map), cap the caller's host array or NULL; the outputs are the caller's
+// host arrays (info, rclear may be NULL).  The arena is reset by the caller.  Ends synchronised.
+int delay_launch(cfz_handle *h, int P, int V, int D, const int32_t *d_count, int cs, const double *d_clear, bool keys, int slack,
+                 const int32_t *cap, int32_t *delays, int32_t *info, double *rclear) {
+  const int npair = V * (V - 1) / 2;
+  const int no = delay_out_ints(V);
+  int32_t *dcap = nullptr, *dout = nullptr;
+  ARENA_ALLOC(h->arena, dout, (size_t)P * no * 4);
+  if (cap) {
+    ARENA_ALLOC(h->arena, dcap, (size_t)P * V * 4);
+    HIP_OK(hipMemcpyAsync(dcap, cap, (size_t)P * V * 4, hipMemcpyHostToDevice, h->stream));
+  }
+  hipLaunchKernelGGL(delay_kernel, dim3((unsigned)P), dim3(256), (size_t)npair * cfz::delay_words(D) * 4, h->stream, V, D, slack, d_count, cs,
+                     d_clear, dcap, dout);
+  HIP_OK(hipGetLastError());
+  std::vector<int32_t> out((size_t)P * no);
+  HIP_OK(hipMemcpyAsync(out.data(), dout, out.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  for (int p = 0; p < P; ++p) {
+    const int32_t *o = out.data() + (size_t)p * no;
+    memcpy(delays + (size_t)p * V, o, (size_t)V * 4);
+    if (info) memcpy(info + (size_t)p * CFZ_DELAY_NINFO, o + V, CFZ_DELAY_NINFO * 4);
+    if (d_clear && rclear) {
+      memcpy(rclear + p, o + no - 2, 8);
+      if (keys) rclear[p] = cfz::audit_key_distance(rclear[p]);
+    }
+  }
+  return 0;
+}
+
+// the conflict map of a pool on the device, searched there: what cfz_plan_delays and cfz_loop_plan_delays share
+int plan_delays_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, int D, double margin, int slack, const int32_t *cap,
+                       int32_t *delays, int32_t *info, double *rclear) {
+  double *dc = nullptr;
+  int32_t *di = nullptr;
+  if (conflict_device(h, P, V, T, d_tables, D, margin, dc, di)) return -1;
+  return delay_launch(h, P, V, D, di + 2, CFZ_CONFLICT_NINFO, dc, true, slack, cap, delays, info, rclear);
 }
 
 // What the pool kernels take, composed from the two per-scenario settings: one KArgs block per (problem, map) pair that some scenario
@@ -1749,6 +1887,61 @@ int cfz_loop_plan_conflicts(cfz_handle *h, int D, double margin, double *clear, 
   if (conflict_sizes(h->lp.P, V, h->lp.T, D)) return -1;
   if (arena_reset(h->arena)) return -1;
   return conflict_launch(h, h->lp.P, V, h->lp.T, h->lp.ref_table, D, margin, clear, info);
+}
+
+int cfz_delay_search(cfz_handle *h, int P, int V, int D, const int32_t *count, const double *clear, int slack, const int32_t *cap,
+                     int32_t *delays, int32_t *info, double *rclear) {
+  if (P < 1 || V < 1) return fail("P, V must be positive");
+  if (V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
+  if (D < 0) return fail("D must not be negative");
+  if (!count) return fail("null count");
+  if (delay_args(P, V, D, slack, cap, delays)) return -1;
+  const size_t no = (size_t)P * (V * (V - 1) / 2) * (2 * (size_t)D + 1);
+  if (no > ((size_t)1 << 31)) return fail("conflict map too large");
+  if (!h) return fail("null handle");
+  if (V == 1) { delay_single(P, clear != nullptr, delays, info, rclear); return 0; }  // no pairs: nothing to launch
+  HIP_OK(hipSetDevice(h->device));
+  if (arena_reset(h->arena)) return -1;
+  int32_t *dn = nullptr;
+  double *dc = nullptr;
+  ARENA_ALLOC(h->arena, dn, no * 4);
+  HIP_OK(hipMemcpyAsync(dn, count, no * 4, hipMemcpyHostToDevice, h->stream));
+  if (clear) {
+    ARENA_ALLOC(h->arena, dc, no * 8);
+    HIP_OK(hipMemcpyAsync(dc, clear, no * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  return delay_launch(h, P, V, D, dn, 1, dc, false, slack, cap, delays, info, rclear);  // (ends synchronised)
+}
+
+int cfz_plan_delays(cfz_handle *h, int P, int V, int T, const double *tables, int D, double margin, int slack, const int32_t *cap,
+                    int32_t *delays, int32_t *info, double *rclear) {
+  if (conflict_args(D, margin)) return -1;
+  if (P < 1 || T < 1) return fail("P, T must be positive");
+  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
+  if (!tables) return fail("null tables");
+  if (conflict_sizes(P, V, T, D)) return -1;
+  if (delay_args(P, V, D, slack, cap, delays)) return -1;
+  if (!h) return fail("null handle");
+  if (V == 1) { delay_single(P, true, delays, info, rclear); return 0; }
+  HIP_OK(hipSetDevice(h->device));
+  if (arena_reset(h->arena)) return -1;
+  const size_t nt = (size_t)P * V * T * 7 * 8;
+  double *dt_ = nullptr;
+  ARENA_ALLOC(h->arena, dt_, nt);
+  HIP_OK(hipMemcpyAsync(dt_, tables, nt, hipMemcpyHostToDevice, h->stream));
+  return plan_delays_launch(h, P, V, T, dt_, D, margin, slack, cap, delays, info, rclear);  // (ends synchronised)
+}
+
+int cfz_loop_plan_delays(cfz_handle *h, int D, double margin, int slack, const int32_t *cap, int32_t *delays, int32_t *info, double *rclear) {
+  if (conflict_args(D, margin)) return -1;
+  if (slack < 0) return fail("slack must not be negative");
+  if (loop_ready(h)) return -1;  // (the caps, the box and the outputs are P x V, the pool's: checked below)
+  const int V = h->ks.n_nbr + 1;
+  if (conflict_sizes(h->lp.P, V, h->lp.T, D)) return -1;
+  if (delay_args(h->lp.P, V, D, slack, cap, delays)) return -1;
+  if (V == 1) { delay_single(h->lp.P, true, delays, info, rclear); return 0; }
+  if (arena_reset(h->arena)) return -1;
+  return plan_delays_launch(h, h->lp.P, V, h->lp.T, h->lp.ref_table, D, margin, slack, cap, delays, info, rclear);
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {

@@ -196,6 +196,10 @@ def load_library(path=None):
     if hasattr(lib, "cfz_plan_conflicts"):
         lib.cfz_plan_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp, vp]
         lib.cfz_loop_plan_conflicts.argtypes = [vp, C.c_int, C.c_double, vp, vp]
+    if hasattr(lib, "cfz_delay_search"):
+        lib.cfz_delay_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
+        lib.cfz_plan_delays.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
+        lib.cfz_loop_plan_delays.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -205,7 +209,7 @@ EXPORTS = (
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
     "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps "
-    "cfz_loop_score cfz_score cfz_plan_conflicts cfz_loop_plan_conflicts"
+    "cfz_loop_score cfz_score cfz_plan_conflicts cfz_loop_plan_conflicts cfz_delay_search cfz_plan_delays cfz_loop_plan_delays"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -267,6 +271,32 @@ def _conflict_out(P, V, D):
 def _conflict_dict(clear, info, V, D):
     pairs = np.array([(u, w) for u in range(V) for w in range(u + 1, V)], np.int32).reshape(-1, 2)
     return dict(clear=clear, when=info[..., 0], first=info[..., 1], count=info[..., 2], pairs=pairs, lags=np.arange(-D, D + 1, dtype=np.int32))
+
+
+def _delay_args(slack, cap, P, V, D):
+    """(slack, cap) of a delay search: the slack as a non-negative int; cap None, or [V] (every set's) or [P, V] whole numbers in
+    [0, D] as a contiguous int32 [P, V]."""
+    r = int(slack)
+    if r != slack or r < 0:
+        raise ValueError(f"slack must be a non-negative whole number of samples, got {slack!r}")
+    if cap is None:
+        return r, None
+    c = np.asarray(cap)
+    if c.shape not in ((V,), (P, V)):
+        raise ValueError(f"expected cap of shape [{V}] or [{P}, {V}], got {c.shape}")
+    ci = c.astype(np.int32)
+    if c.size and (not (ci == c).all() or ci.min() < 0 or ci.max() > D):
+        raise ValueError(f"cap must hold whole numbers in [0, {D}]")
+    return r, np.ascontiguousarray(np.broadcast_to(ci, (P, V)))
+
+
+def _delay_out(P, V):
+    """The raw arrays of the delay entry points: delays [P, V], info [P, 3], rclear [P] (NaN where the library does not write it)."""
+    return np.full((P, V), -1, np.int32), np.full((P, 3), -1, np.int32), np.full(P, np.nan)
+
+
+def _delay_dict(delays, info, rclear):
+    return dict(delays=delays, found=info[:, 0] == 1, span=info[:, 1], total=info[:, 2], clear=rclear)
 
 
 def conflict_summary(out):
@@ -1003,6 +1033,58 @@ class Engine:
         clear, info = _conflict_out(self._P, self._V, D)
         self._ck(self.lib.cfz_loop_plan_conflicts(self._h, D, margin, _ptr(clear), _ptr(info)), "cfz_loop_plan_conflicts")
         return _conflict_dict(clear, info, self._V, D)
+
+    def delay_search(self, cmap, slack=0, cap=None):
+        """`cfz_delay_search`: the start delays that make every plan set of the conflict map `cmap` (the dict `plan_conflicts` returns, or
+        an edited one: count [P, npair, 2D+1] and, optionally, clear) conflict-free -> dict(delays [P, V] int32 (-1: nothing feasible),
+        found [P] bool, span [P] (the largest delay), total [P] (their sum), clear [P] (the smallest clearance of the set under the
+        delays; +inf for V = 1, -inf if not found, NaN without cmap["clear"])).  Vehicle v of set p starts delays[p, v] samples late, waiting
+        at its first sample: `scenarios.delay_tables(tables, delays)`.  Pair (u, w) then runs at the map's lag delays[w] - delays[u]; every
+        lag within `slack` samples of it must lie inside the map's window and be free (count 0, clear finite).  cap [V] or [P, V]: the
+        most each vehicle may be delayed (None: D; 0: it leaves on time).  The answer is the smallest under (span, total, the delays as a
+        tuple)."""
+        count = np.ascontiguousarray(cmap["count"], dtype=np.int32)
+        if count.ndim != 3 or count.shape[0] == 0 or count.shape[2] % 2 != 1:
+            raise ValueError(f"expected count of shape [P, npair, 2D+1], got {count.shape}")
+        P, npair, D = count.shape[0], count.shape[1], count.shape[2] // 2
+        V = int(round((1 + np.sqrt(1 + 8 * npair)) / 2))
+        if V * (V - 1) // 2 != npair:
+            raise ValueError(f"{npair} pairs are not the pairs of a whole number of vehicles")
+        clear = cmap.get("clear")
+        if clear is not None:
+            clear = np.ascontiguousarray(clear, dtype=np.float64)
+            if clear.shape != count.shape:
+                raise ValueError(f"expected clear of the shape of count {count.shape}, got {clear.shape}")
+        slack, cap = _delay_args(slack, cap, P, V, D)
+        delays, info, rclear = _delay_out(P, V)
+        self._ck(self.lib.cfz_delay_search(self._h, P, V, D, _ptr(count), _ptr(clear), slack, _ptr(cap), _ptr(delays), _ptr(info), _ptr(rclear)),
+                 "cfz_delay_search")
+        return _delay_dict(delays, info, rclear)
+
+    def plan_delays(self, tables, max_lag, margin=None, slack=0, cap=None):
+        """`cfz_plan_delays`: `delay_search(plan_conflicts(tables, max_lag, margin), slack, cap)` with the map computed and searched on
+        the device: it never comes back to the host -> the same dict."""
+        D, margin = _conflict_args(max_lag, margin, self.spec)
+        tables = np.ascontiguousarray(tables, dtype=np.float64)
+        if tables.ndim == 3:
+            tables = tables[None]
+        if tables.ndim != 4 or tables.shape[3] != 7 or 0 in tables.shape:
+            raise ValueError(f"expected tables of shape [P, V, T, 7] or [V, T, 7], got {tables.shape}")
+        P, V, T = tables.shape[:3]
+        slack, cap = _delay_args(slack, cap, P, V, D)
+        delays, info, rclear = _delay_out(P, V)
+        self._ck(self.lib.cfz_plan_delays(self._h, P, V, T, _ptr(tables), D, margin, slack, _ptr(cap), _ptr(delays), _ptr(info), _ptr(rclear)),
+                 "cfz_plan_delays")
+        return _delay_dict(delays, info, rclear)
+
+    def loop_plan_delays(self, max_lag, margin=None, slack=0, cap=None):
+        """`cfz_loop_plan_delays`: `plan_delays` of the pool that `loop_init` left on the device (nothing is uploaded but the caps, the
+        loop is left as it is) -> the same dict, P the pool's."""
+        D, margin = _conflict_args(max_lag, margin, self.spec)
+        slack, cap = _delay_args(slack, cap, self._P, self._V, D)
+        delays, info, rclear = _delay_out(self._P, self._V)
+        self._ck(self.lib.cfz_loop_plan_delays(self._h, D, margin, slack, _ptr(cap), _ptr(delays), _ptr(info), _ptr(rclear)), "cfz_loop_plan_delays")
+        return _delay_dict(delays, info, rclear)
 
     def loop_last_converged(self):
         """Solves of the last `loop_run` that converged (status 0)."""

@@ -34,12 +34,18 @@
    plans come within dmin; -1: they do already); next to the closing ranking, how many of the strategies whose plans overlap had contact
    in closed loop against those whose plans are clear.  The same map from a vectorised numpy statement is timed next to it, three
    repeats each.
+8. --resolve R (with --lags D): one `Engine.loop_plan_delays(D, slack=R)` call on the same pool: per strategy the start delays, at most D
+   samples per vehicle, under which no pair of its plans comes within dmin even if either vehicle slips R further samples -- the
+   smallest by (largest delay, sum, tuple); "-" where the window holds none.  The rows gain the delays and the smallest clearance of the
+   delayed plans; a closing line says how many of the strategies whose plans overlap were resolved and at which spans.  The closed loop
+   is then run on the delayed plans (`scenarios.delay_tables`; starts sampled from them), so that the ranking answers which strategies
+   are contact-free once resolved.  The same search as a numpy brute force over all (D+1)^V delay vectors of a set is timed next to it.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
                                               [--noise-levels L0,L1,...] [--noise-seed SEED]
                                               [--drop-rates P0,P1,...] [--max-age A] [--no-compensate] [--comm-seed SEED]
                                               [--dmin D0,D1,...] [--obstacle-margins M0,M1,...]
-                                              [--lags D]
+                                              [--lags D [--resolve R]]
 """
 import argparse
 import dataclasses
@@ -161,6 +167,32 @@ def host_conflicts(tables, D, margin, g):
     return {k: (v if k == "d" else np.stack(v, -1)) for k, v in out.items()}
 
 
+def host_delays(count, clear, slack):
+    """What a user computed on the host before `Engine.plan_delays`: the start delays that resolve the conflict map count, clear
+    [P, npair, 2D+1], with numpy, all (D+1)^V delay vectors of one plan set at a time -> delays [P, V] (-1: none), span, total [P].
+    Timed against the device in main() and compared with it."""
+    P, npair, L = count.shape
+    D, V = L // 2, int(round((1 + np.sqrt(1 + 8 * npair)) / 2))
+    free = (count == 0) & np.isfinite(clear)
+    win = np.zeros_like(free)  # every lag within the slack is inside the window and free
+    for j in range(slack, L - slack):
+        win[..., j] = free[..., j - slack : j + slack + 1].all(-1)
+    d = np.indices((D + 1,) * V, dtype=np.int32).reshape(V, -1)  # every delay vector, in the order of the tuple rule
+    span, total = d.max(0).astype(np.int64), d.sum(0).astype(np.int64)
+    key = (span * (V * D + 1) + total) * d.shape[1] + np.arange(d.shape[1])  # (span, total, tuple) as one integer
+    us, ws = np.triu_indices(V, 1)
+    lag = [d[w] - d[u] + D for u, w in zip(us, ws)]
+    out = dict(delays=np.full((P, V), -1, np.int32), span=np.full(P, -1, np.int32), total=np.full(P, -1, np.int32))
+    for p in range(P):
+        ok = np.ones(d.shape[1], bool)
+        for q in range(npair):
+            ok &= win[p, q][lag[q]]
+        if ok.any():
+            i = np.flatnonzero(ok)[key[ok].argmin()]
+            out["delays"][p], out["span"][p], out["total"][p] = d[:, i], span[i], total[i]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--starts", type=int, default=16, help="sampled starts per strategy")
@@ -184,7 +216,12 @@ def main():
                          "value, in one launch, on the plans of the reference map")
     ap.add_argument("--lags", type=int, default=None, metavar="D",
                     help="window of the plans' conflict map in samples, e.g. 40: body clearance of every pair of plans at relative delays -D..D")
+    ap.add_argument("--resolve", type=int, default=None, metavar="R",
+                    help="with --lags D: search the start delays (at most D samples each) that make every strategy's plans conflict-free with "
+                         "R samples of slack, and run the closed loop on the delayed plans")
     a = ap.parse_args()
+    if a.resolve is not None and a.lags is None:
+        ap.error("--resolve needs --lags")
 
     import torch
 
@@ -208,16 +245,7 @@ def main():
     spec = scenarios.parking_lot_spec()
     M, K = a.starts, a.steps
     sets = np.flatnonzero(ok)
-    k0s, noises, tof = [], [], []
-    for p in sets:
-        k0, nz = scenarios.sample_scenarios(M, plan["tables"][p], seed=a.seed + int(p), spec=spec)
-        k0s.append(k0); noises.append(nz); tof.append(np.full(M, p, np.int32))
-    k0, noise, tof = np.concatenate(k0s), np.concatenate(noises), np.concatenate(tof)
     levels, rates, dmins, margins = a.noise_levels, a.drop_rates, a.dmin, a.obstacle_margins
-    rep = replicate(k0, noise, tof, levels, rates, dmins, margins)
-    k0, noise, tof, lvl, streams, drop, pof = (rep[k] for k in ("k0", "noise", "tof", "level", "stream", "drop", "problem_of"))
-    mof = rep.get("map_of")
-    comm_streams = streams
     if levels:
         print(f"noise levels {levels} x sigma: meas {NOISE_SIGMA['meas']}, act {NOISE_SIGMA['act']}, proc {NOISE_SIGMA['proc']}; "
               f"noise seed {a.noise_seed}, one stream per start shared by its {len(levels)} replicas")
@@ -228,20 +256,37 @@ def main():
         print(f"clearances dmin {dmins}: one problem per value in the pool, every replica of a start on its streams")
     if margins:
         print(f"obstacle margins {margins} m: one map per value in the pool, every replica of a start on its streams and on the reference map's plans")
+    eng = None
+
+    def start_loop(tables):
+        """M sampled starts per plan set of `tables`, replicated over the axes given, as the closed loop of `eng` with every setting."""
+        nonlocal eng
+        k0s, noises, tof = [], [], []
+        for p in sets:
+            k0, nz = scenarios.sample_scenarios(M, tables[p], seed=a.seed + int(p), spec=spec)
+            k0s.append(k0); noises.append(nz); tof.append(np.full(M, p, np.int32))
+        rep = replicate(np.concatenate(k0s), np.concatenate(noises), np.concatenate(tof), levels, rates, dmins, margins)
+        k0, noise, tof, lvl, streams, drop, pof = (rep[k] for k in ("k0", "noise", "tof", "level", "stream", "drop", "problem_of"))
+        mof = rep.get("map_of")
+        if eng is None:
+            eng = engine.Engine(spec, max_batch=len(k0) * V, device=a.device)
+        eng.loop_init(tables, k0, noise, table_of=tof)
+        if levels:
+            eng.loop_set_disturbance(a.noise_seed, level=lvl, stream=streams, **NOISE_SIGMA)
+        if a.exchange == "sequential":
+            eng.loop_set_order(np.array([combos[p][0][0] for p in tof], np.int32))
+        if rates:
+            eng.loop_set_comm(a.comm_seed, drop, max_age=a.max_age, compensate=not a.no_compensate, stream=streams)
+        if dmins:
+            eng.loop_set_problems([dataclasses.replace(spec, dmin=d) for d in dmins], pof)
+        if margins:
+            eng.loop_set_maps([scenarios.grow_obstacles(spec, m) for m in margins], mof)
+        return k0, tof, lvl, drop, pof, mof
+
+    run_tables = plan["tables"]
+    k0, tof, lvl, drop, pof, mof = start_loop(run_tables)
     S = len(k0)
-    eng = engine.Engine(spec, max_batch=S * V, device=a.device)
-    eng.loop_init(plan["tables"], k0, noise, table_of=tof)
-    if levels:
-        eng.loop_set_disturbance(a.noise_seed, level=lvl, stream=streams, **NOISE_SIGMA)
-    if a.exchange == "sequential":
-        eng.loop_set_order(np.array([combos[p][0][0] for p in tof], np.int32))
-    if rates:
-        eng.loop_set_comm(a.comm_seed, drop, max_age=a.max_age, compensate=not a.no_compensate, stream=comm_streams)
-    if dmins:
-        eng.loop_set_problems([dataclasses.replace(spec, dmin=d) for d in dmins], pof)
-    if margins:
-        eng.loop_set_maps([scenarios.grow_obstacles(spec, m) for m in margins], mof)
-    cs = None
+    cs = dl = None
     if a.lags is not None:
         t_dev, t_np = [], []
         for _ in range(3):  # (three repeats each: the spread is printed with the median)
@@ -265,6 +310,25 @@ def main():
         print(f"conflict map of the plans: {P} sets x {V * (V - 1) // 2} pairs x {2 * a.lags + 1} lags x {plan['tables'].shape[2]}+ steps, margin dmin = {spec.dmin:g} m: "
               f"{fmt(t_dev)} on the device (cfz_loop_plan_conflicts, the call with its read-back); the same map with numpy on the host: {fmt(t_np)} "
               f"(distances within 1e-12, equal integers)")
+    if a.resolve is not None:
+        t_dev, t_np = [], []
+        eng.loop_plan_delays(a.lags, slack=a.resolve)  # (not timed: the first launch loads the kernel)
+        for _ in range(3):
+            sync(); t0 = time.perf_counter()
+            dl = eng.loop_plan_delays(a.lags, slack=a.resolve)
+            sync(); t_dev.append(time.perf_counter() - t0)
+        for _ in range(3):
+            t0 = time.perf_counter()
+            hdl = host_delays(cm["count"], cm["clear"], a.resolve)
+            t_np.append(time.perf_counter() - t0)
+        for n in ("delays", "span", "total"):  # the device against the host's brute force over the map read back: equal integers
+            assert np.array_equal(dl[n], hdl[n]), n
+        print(f"start delays that resolve the plans: {P} sets x {a.lags + 1}^{V} delay vectors x {V * (V - 1) // 2} pairs, slack {a.resolve}: "
+              f"{fmt(t_dev)} on the device (cfz_loop_plan_delays: the map and the search, the call with its read-back); the same search "
+              f"with numpy on the host over the map it holds: {fmt(t_np)} (equal integers)")
+        run_tables = scenarios.delay_tables(plan["tables"], np.maximum(dl["delays"], 0))  # (no delay where the window holds no answer)
+        k0, tof, lvl, drop, pof, mof = start_loop(run_tables)
+        print(f"the closed loop below runs on the delayed plans ({run_tables.shape[2]} samples), starts sampled from them")
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -279,7 +343,7 @@ def main():
     hist = eng.loop_history()
     t_hist = time.perf_counter() - t0
     t0 = time.perf_counter()
-    hsc = host_score(hist, plan["tables"], tof, k0, spec.dt, spec.weights)
+    hsc = host_score(hist, run_tables, tof, k0, spec.dt, spec.weights)
     t_host = time.perf_counter() - t0
     for n, hv in hsc.items():  # the device against the host's numpy: integers equal, sums to rounding
         assert np.array_equal(sc[n], hv) if np.issubdtype(np.asarray(hv).dtype, np.integer) else np.allclose(sc[n], hv, rtol=1e-9, atol=1e-12), n
@@ -298,7 +362,7 @@ def main():
     print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}"
           + "".join(f" {'c@%g' % l:>6}" for l in levels or [])
           + f" {'mksp s':>7} {'cost':>9} {'wait s':>7} {'revs':>5} {'near':>5}"
-          + (f" {'depth m':>7} {'crit':>5} {'slack':>5}" if cs else ""))
+          + (f" {'depth m':>7} {'crit':>5} {'slack':>5}" if cs else "") + (f" {'delays':>12} {'rclear':>7}" if dl else ""))
     no_contact = []
     for p in range(P):
         row = f"{p:5d} {len(combos[p]):6d} {int((plan['colloc_status'][p] == 0).sum()):3d}/{V}"
@@ -316,7 +380,8 @@ def main():
               f"{(np.median(last) if len(last) else float('nan')):7.0f} {(last.max() if len(last) else -1):7d} {int(done.sum()):4d}/{n_sel:<2d}"
               + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or [])
               + f" {med(makespan, sel):7.1f} {med(cost, sel):9.1f} {med(wait, sel):7.1f} {med(revs, sel):5.0f} {med(near, sel):5.0f}"
-              + (f" {cs['depth'][p]:7.3f} {'%d-%d' % tuple(cs['critical_pair'][p]):>5} {cs['slack'][p]:5d}" if cs else ""))
+              + (f" {cs['depth'][p]:7.3f} {'%d-%d' % tuple(cs['critical_pair'][p]):>5} {cs['slack'][p]:5d}" if cs else "")
+              + ((f" {','.join(str(x) for x in dl['delays'][p]):>12} {dl['clear'][p]:7.3f}" if dl["found"][p] else f" {'-':>12} {'-':>7}") if dl else ""))
         if n_contact == 0:
             no_contact.append(p)
     for l in levels or []:
@@ -348,6 +413,15 @@ def main():
         hit = lambda ps: sum(int(p) not in no_contact for p in ps)  # noqa: E731
         print(f"plans against closed loops: {hit(deep)} of the {len(deep)} strategies whose plans overlap at lag 0 (planned depth > 0) had contact in closed loop, "
               f"{hit(free)} of the {len(free)} whose plans do not; smallest slack over the strategies run {int(cs['slack'][ran].min())}, largest {int(cs['slack'][ran].max())} samples")
+    if dl:
+        ran = np.flatnonzero(ok)
+        deep = ran[cs["depth"][ran] > 0]
+        solved = deep[dl["found"][deep]]
+        spans = np.bincount(dl["span"][solved], minlength=1)
+        print(f"resolved by start delays: {len(solved)} of the {len(deep)} strategies whose plans overlap at lag 0 have a solution inside the window of "
+              f"{a.lags} samples with slack {a.resolve}, largest span {int(dl['span'][solved].max()) if len(solved) else -1} samples "
+              f"(strategies per span: {', '.join(f'{m}: {n}' for m, n in enumerate(spans) if n)}); "
+              f"{sum(int(p) in no_contact for p in solved)} of them finish all their closed loops without contact on the delayed plans")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms, score {t_score * 1e3:.1f} ms")
     eng.close()
 

@@ -634,6 +634,48 @@ int cfz_plan_conflicts(cfz_handle *h, int P, int V, int T, const double *tables 
                        double *clear /* [P][npair][2D+1] */, int32_t *info /* [P][npair][2D+1][3] */);
 int cfz_loop_plan_conflicts(cfz_handle *h, int D, double margin, double *clear, int32_t *info);
 
+/* ---- start delays that resolve a plan set's conflicts ----------------------------------------------------------------------
+ * How late which vehicle of a plan set must leave so that no pair of plans comes within the margin, searched over the conflict map above.
+ * If the vehicles of a set start d[0..V-1] samples late, each waiting at its first sample, pair (u, w) visits exactly the body
+ * configurations of the map's lag tau = d[w] - d[u]: while both wait they stand as at step 0 of that lag, after that the steps are the
+ * same steps, beyond T + |tau| both rest at their last samples.  So the pair stays clear under d exactly when count[p][q][tau + D] == 0,
+ * and its smallest clearance under d is clear[p][q][tau + D], bit for bit.
+ * Inputs per plan set p: the map count[p][npair][2D+1], optionally clear of the same shape; a slack r >= 0 in samples; caps cap[p][v] in
+ * [0, D] (NULL: D for every vehicle), the most vehicle v may be delayed; 0: it must leave on time.
+ * A lag index j is free for pair q when count[p][q][j] == 0 and, where clear is given, clear[p][q][j] is finite (a pair whose distances
+ * are all NaN, from a plan that did not converge, is not free).
+ * A delay vector d, 0 <= d[v] <= cap[p][v], is feasible with slack r when for every pair q = (u, w) in the audit's order every lag tau' in
+ * [d[w] - d[u] - r, d[w] - d[u] + r] lies inside [-D, D] and is free; lags outside the window are unknown and count as not free, so
+ * |d[w] - d[u]| + r <= D is required.  With r > 0 the answer tolerates either vehicle of any pair slipping up to r further samples.
+ * The answer is the feasible d that is smallest under the total order (span, total, tuple): span = max_v d[v]; total = sum_v d[v]; the
+ * tuple compared lexicographically with vehicle 0 most significant, that is the integer idx = sum_v d[v] (D+1)^(V-1-v).  It always
+ * has a zero: subtracting min_v d[v] keeps the differences and the caps and lowers the span.
+ *   delays[p][V]  the answer, all -1 if nothing is feasible
+ *   info[p][0]    found: 1 or 0
+ *   info[p][1]    span, -1 if not found
+ *   info[p][2]    total, -1 if not found
+ *   rclear[p]     min over pairs of clear[p][q][d[w] - d[u] + D] at the answer; +inf for V = 1, -inf if not found; not written when
+ *                 clear is NULL
+ * V = 1: found, delay 0, nothing is launched.  D = 0: the only candidate is all zeros.  r > D: nothing is found (a result, not an error).
+ * One workgroup per plan set; the spans are searched in ascending order, so a set answered at span m costs (m+1)^V candidates and only a
+ * set without a solution costs the whole box (D+1)^V; minima of integers under a total order and one min of doubles: the same bits on
+ * every run (conflict_rez_amd/csrc/cfz_delay.inl).
+ * cfz_delay_search: a map the caller holds (as cfz_plan_conflicts returned it, or edited: the union of two margins, say).
+ * cfz_plan_delays: host tables as cfz_plan_conflicts takes them; the map is computed on the device and searched there, it never comes
+ * back to the host, and clear is always given.  cfz_loop_plan_delays: the same on the pool that cfz_loop_init* left on the device (P,
+ * V, T its own, cap[P][V] with that P); the loop's state, clock and record are left untouched.  info and rclear may be NULL.
+ * Refused before anything is launched: non-positive P or V (T, for cfz_plan_delays), V above CFZ_MAX_NBR+1, D < 0, slack < 0, a cap
+ * outside [0, D], NULL count (tables) or delays, (D+1)^V > 2^31 ("search space too large": idx must fit an int, and the bound also limits
+ * the time of a set without a solution), what cfz_plan_conflicts / cfz_loop_plan_conflicts refuse.  What needs no handle is checked
+ * before the handle is looked at. */
+#define CFZ_DELAY_NINFO 3 /* found, span, total */
+int cfz_delay_search(cfz_handle *h, int P, int V, int D, const int32_t *count /* [P][npair][2D+1] */, const double *clear /* or NULL */,
+                     int slack, const int32_t *cap /* [P][V] or NULL */, int32_t *delays /* [P][V] */, int32_t *info /* [P][3] or NULL */,
+                     double *rclear /* [P] or NULL */);
+int cfz_plan_delays(cfz_handle *h, int P, int V, int T, const double *tables /* [P][V][T][7] */, int D, double margin, int slack,
+                    const int32_t *cap, int32_t *delays, int32_t *info, double *rclear);
+int cfz_loop_plan_delays(cfz_handle *h, int D, double margin, int slack, const int32_t *cap, int32_t *delays, int32_t *info, double *rclear);
+
 const char *cfz_last_error(void);
 /* First 16 hex digits of the SHA-256 over the kernel sources this library was built from (__graft_entry__.source_hash; "unknown" for
  * a build made by hand).  bench.py quotes profiler counters from profiles/ only if they were taken on a library with the same hash. */
