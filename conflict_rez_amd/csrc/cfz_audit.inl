@@ -47,8 +47,11 @@ CFZ_CALL void audit_poly_prepare(AuditPoly &P) {
   P.nn = 4;
 }
 
-// the body rectangle g = (front, left, rear, right) at (x, y) with heading cos c, sin s, corners counter-clockwise (as
-// dual_ws_kernel); il[2] = 1 / (g[0] + g[2]), 1 / (g[1] + g[3]) (the inverse lengths of its long and short edges)
+// il[e] of the body g = (front, left, rear, right): the inverse length of its long (e = 0) or short (e = 1) edges.  Formed on the host,
+// by every launcher and every CPU build through this one function
+CFZ_CALL double audit_body_il(const double g[4], int e) { return 1.0 / (g[e] + g[e + 2]); }
+
+// the body rectangle g at (x, y) with heading cos c, sin s, corners counter-clockwise (as dual_ws_kernel); il[2] as audit_body_il
 CFZ_CALL void audit_body(const double g[4], const double il[2], double x, double y, double c, double s, AuditPoly &W) {
   const double BV[4][2] = {{g[0], g[1]}, {-g[2], g[1]}, {-g[2], -g[3]}, {g[0], -g[3]}};
   for (int i = 0; i < 4; ++i) { W.v[i][0] = x + c * BV[i][0] - s * BV[i][1]; W.v[i][1] = y + s * BV[i][0] + c * BV[i][1]; }

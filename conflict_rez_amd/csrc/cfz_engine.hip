@@ -59,6 +59,7 @@
 #include "cfz_score.inl"
 #include "cfz_conflict.inl"
 #include "cfz_delay.inl"
+#include "cfz_wave.inl"
 #include "cfz_disturb.inl"
 #include "cfz_comm.inl"
 #include "cfz_common.h"
@@ -637,25 +638,15 @@ __global__ __launch_bounds__(64) void audit_kernel(const KArgs *__restrict__ ka,
   cfz::AuditAcc acc;
   cfz::audit_lane(acc, lane, 64, K, V, traj + (size_t)s * V * 7, (long)S * V * 7, goal + (size_t)s * V * 3, cs + (size_t)s * V * 2, no,
                   obs, g, il, pos_tol, psi_tol, v_tol);
-  for (int off = 32; off > 0; off >>= 1) {
-    cfz::AuditAcc o;
-    o.vv = __shfl_xor(acc.vv, off, 64); o.vv_t = __shfl_xor(acc.vv_t, off, 64); o.vv_u = __shfl_xor(acc.vv_u, off, 64);
-    o.vv_w = __shfl_xor(acc.vv_w, off, 64);
-    o.vo = __shfl_xor(acc.vo, off, 64); o.vo_t = __shfl_xor(acc.vo_t, off, 64); o.vo_v = __shfl_xor(acc.vo_v, off, 64);
-    o.vo_j = __shfl_xor(acc.vo_j, off, 64);
-    o.first = __shfl_xor(acc.first, off, 64);
-    for (int v = 0; v < cfz::kAuditMaxV; ++v) o.arrive[v] = __shfl_xor(acc.arrive[v], off, 64);
-    cfz::audit_merge(acc, o);
-  }
+  cfz::wave_merge<cfz::AuditAcc, cfz::audit_merge>(acc, 64);
   if (lane == 0) cfz::audit_store(acc, V, clear + (size_t)s * 2, where + (size_t)s * 6, first_contact + s, arrive + (size_t)s * V);
 }
 
 // ---- score of a recorded closed loop (cfz_score.inl) -----------------------------------------------------------------
 // One wavefront per scenario.  Vehicle v owns the L = score_group(V) lanes [v L, (v + 1) L), lane j of them the contiguous steps
 // [j C, min((j + 1) C, K)), C = ceil(K / L); lanes past V L and lanes with an empty chunk hold the identity and take part in every
-// shuffle.  Pass 1: the arrival, a minimum over the group.  Pass 2: every lane summarises its chunk cut at upto; a __shfl_xor butterfly
-// over off = 1 .. L / 2 merges the summaries with the LOWER lane as the left (earlier) operand, so every lane of a group ends with the
-// same total and the floating-point sums are added in one fixed tree: the same bits on every run.  traj[K][S][V][7] from the window's
+// shuffle.  Pass 1: the arrival, a minimum over the group.  Pass 2: every lane summarises its chunk cut at upto; the ordered butterfly of
+// cfz_wave.inl merges the summaries in one fixed tree: the same bits in every lane and on every run.  traj[K][S][V][7] from the window's
 // first step, cs its headings (audit_headings); status / iters point at the window's first step, steps si_stride apart (NULL: all 0);
 // tables[P][V][T][7], table_of[S]; the window's k0 of scenario s is k0[s] - back.  val[S][V][kScoreNVal], cnt[S][V][kScoreNCnt],
 // stored by the group's first lane with plain stores.
@@ -670,18 +661,10 @@ __global__ __launch_bounds__(64) void score_kernel(const KArgs *__restrict__ ka,
   while ((v + 1) * L <= lane) ++v;
   const int j = lane - v * L;
   const bool active = v < V;
+  const double il[2] = {il0, il1};
   cfz::ScoreIn in;
-  in.K = K; in.V = V; in.v = active ? v : 0; in.T = T;
-  in.k0 = k0[s] - back;
-  if (in.k0 < 0) in.k0 = 0;
-  in.traj = traj + (size_t)s * V * 7; in.cs = cs + (size_t)s * V * 2;
-  in.plan = tables + ((size_t)table_of[s] * V + in.v) * T * 7;
-  in.step_stride = (long)S * V * 7; in.si_stride = si_stride;
-  in.status = status ? status + (size_t)s * V + in.v : nullptr;
-  in.iters = iters ? iters + (size_t)s * V + in.v : nullptr;
-  for (int i = 0; i < 4; ++i) in.g[i] = ka->sp.g[i];
-  in.il[0] = il0; in.il[1] = il1;
-  in.pos_tol = pos_tol; in.psi_tol = psi_tol; in.v_tol = v_tol; in.near2 = near2;
+  cfz::score_in(in, s, active ? v : 0, K, S, V, traj, cs, status, iters, si_stride, T, tables, table_of, k0, back, ka->sp.g, il, pos_tol, psi_tol,
+                v_tol, near2);
   int t0, t1;
   cfz::score_lane_chunk(K, L, j, t0, t1);
   if (!active) t0 = t1 = K;
@@ -693,19 +676,7 @@ __global__ __launch_bounds__(64) void score_kernel(const KArgs *__restrict__ ka,
   if (arrive == INT32_MAX) arrive = -1;
   cfz::ScoreSeg a;
   cfz::score_chunk(a, in, t0, t1, arrive);
-  for (int off = 1; off < L; off <<= 1) {
-    cfz::ScoreSeg o;
-    for (int i = 0; i < cfz::kScoreNSum; ++i) o.sum[i] = __shfl_xor(a.sum[i], off, 64);
-    o.dev2 = __shfl_xor(a.dev2, off, 64); o.dev_t = __shfl_xor(a.dev_t, off, 64);
-    o.failed = __shfl_xor(a.failed, off, 64); o.run_n = __shfl_xor(a.run_n, off, 64); o.run_pre = __shfl_xor(a.run_pre, off, 64);
-    o.run_suf = __shfl_xor(a.run_suf, off, 64); o.run_best = __shfl_xor(a.run_best, off, 64);
-    o.rv_first = __shfl_xor(a.rv_first, off, 64); o.rv_last = __shfl_xor(a.rv_last, off, 64); o.rv_count = __shfl_xor(a.rv_count, off, 64);
-    o.waiting = __shfl_xor(a.waiting, off, 64); o.near_steps = __shfl_xor(a.near_steps, off, 64);
-    o.first_near = __shfl_xor(a.first_near, off, 64);
-    o.iters_sum = __shfl_xor(a.iters_sum, off, 64); o.iters_max = __shfl_xor(a.iters_max, off, 64);
-    if (lane & off) { cfz::score_merge(o, a); a = o; }  // the partner is the lower lane: its segment is the earlier one
-    else cfz::score_merge(a, o);
-  }
+  cfz::wave_merge_ordered<cfz::ScoreSeg, cfz::score_merge>(a, lane, L);
   if (active && j == 0)
     cfz::score_store(a, K, arrive, val + ((size_t)s * V + v) * cfz::kScoreNVal, cnt + ((size_t)s * V + v) * cfz::kScoreNCnt);
 }
@@ -732,12 +703,7 @@ __device__ __forceinline__ void conflict_lags(int T, int D, const double *U, con
   for (int j = wave; j < 2 * D + 1; j += 4) {
     cfz::ConflictAcc acc;
     cfz::conflict_lane(acc, lane, 64, T, j - D, U, W, g, il, margin, margin2);
-    for (int off = 32; off > 0; off >>= 1) {
-      cfz::ConflictAcc o;
-      o.key = __shfl_xor(acc.key, off, 64); o.when = __shfl_xor(acc.when, off, 64);
-      o.first = __shfl_xor(acc.first, off, 64); o.count = __shfl_xor(acc.count, off, 64);
-      cfz::conflict_merge(acc, o);
-    }
+    cfz::wave_merge<cfz::ConflictAcc, cfz::conflict_merge>(acc, 64);
     if (lane == 0) cfz::conflict_store(acc, clear + j, info + (size_t)j * cfz::kConflictNInfo);
   }
 }
@@ -805,11 +771,7 @@ __global__ __launch_bounds__(256) void delay_kernel(int V, int D, int r, const i
     cfz::delay_shell(V, m, sh);
     cfz::DelayAcc acc;
     cfz::delay_lane(acc, tid, 256, V, D, m, sh, capv, delay_lds, nw);
-    for (int off = 32; off > 0; off >>= 1) {
-      cfz::DelayAcc o;
-      o.total = __shfl_xor(acc.total, off, 64); o.idx = __shfl_xor(acc.idx, off, 64);
-      cfz::delay_merge(acc, o);
-    }
+    cfz::wave_merge<cfz::DelayAcc, cfz::delay_merge>(acc, 64);
     int(*x)[2] = xch[m & 1];  // (the other buffer may still be read by a wavefront that has not left the previous shell)
     if ((tid & 63) == 0) { x[tid >> 6][0] = acc.total; x[tid >> 6][1] = acc.idx; }
     __syncthreads();
@@ -1001,6 +963,14 @@ int check(cfz_handle *h, int B) {
   if (!h) return fail("null handle");
   if (B < 1 || B > h->max_batch) return fail("batch size out of range");
   HIP_OK(hipSetDevice(h->device));
+  return 0;
+}
+
+// `count` elements of the caller's host array on the device: from the handle's arena, copied on its stream (nothing is waited for)
+template <class T>
+int arena_upload(cfz_handle *h, T *&dptr, const T *host, size_t count) {
+  ARENA_ALLOC(h->arena, dptr, count * sizeof(T));
+  HIP_OK(hipMemcpyAsync(dptr, host, count * sizeof(T), hipMemcpyHostToDevice, h->stream));
   return 0;
 }
 
@@ -1482,15 +1452,14 @@ int audit_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const
   if (!d_obs) {
     cfz::AuditPoly *dob = nullptr;
     audit_polys(no, h->ks.V_obs, ob.data());
-    ARENA_ALLOC(h->arena, dob, ob.size() * sizeof(cfz::AuditPoly));
-    HIP_OK(hipMemcpyAsync(dob, ob.data(), ob.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice, h->stream));
+    if (arena_upload(h, dob, ob.data(), ob.size())) return -1;
     d_obs = dob;
   }
   int32_t *dw = di, *df = di + (size_t)S * 6, *da = di + (size_t)S * 7;
   hipLaunchKernelGGL(audit_headings, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, d_traj, dcs);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(audit_kernel, dim3(S), dim3(64), 0, h->stream, h->kargs, K, S, V, d_traj, dcs, d_goal, d_obs, d_map_of,
-                     1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), pos_tol, psi_tol, v_tol, dc, dw, df, da);
+                     cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1), pos_tol, psi_tol, v_tol, dc, dw, df, da);
   HIP_OK(hipGetLastError());
   if (clear) HIP_OK(hipMemcpyAsync(clear, dc, (size_t)S * 2 * 8, hipMemcpyDeviceToHost, h->stream));
   if (where) HIP_OK(hipMemcpyAsync(where, dw, (size_t)S * 6 * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1516,13 +1485,24 @@ int score_launch(cfz_handle *h, int K, int S, int V, const double *d_traj, const
   hipLaunchKernelGGL(audit_headings, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, d_traj, dcs);
   HIP_OK(hipGetLastError());
   hipLaunchKernelGGL(score_kernel, dim3(S), dim3(64), 0, h->stream, h->kargs, K, S, V, d_traj, dcs, d_status, d_iters, si_stride, T, d_tables,
-                     d_table_of, d_k0, back, 1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), pos_tol, psi_tol, v_tol, near * near, dv, dc);
+                     d_table_of, d_k0, back, cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1), pos_tol, psi_tol, v_tol, near * near, dv, dc);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(val, dv, B * CFZ_SCORE_NVAL * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipMemcpyAsync(cnt, dc, B * CFZ_SCORE_NCNT * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_OK(hipStreamSynchronize(h->stream));
   return 0;
 }
+
+// what cfz_loop_history, cfz_loop_audit and cfz_loop_score ask of the handle: a loop that is set up and the window [t0, t0 + K) in its record
+int record_window(cfz_handle *h, int t0, int K) {
+  if (loop_ready(h)) return -1;
+  return t0 < 0 || K < 1 || t0 + K > h->lp.rec_used ? fail("steps [t0, t0 + K) are not in the record") : 0;
+}
+
+// a caller's trajectory traj[K][S][V][7] (cfz_audit_maps, cfz_score): its sizes, and that every index of the kernels fits an int.  Two
+// functions: both entry points refuse null pointers between the two, each in its own words.
+int traj_dims(int K, int S, int V) { return K < 1 || S < 1 || V < 1 || V > CFZ_MAX_NBR + 1 ? fail("K, S must be positive and V in 1..CFZ_MAX_NBR+1") : 0; }
+int traj_fits(int K, int S, int V) { return (size_t)K * S * V * 7 > ((size_t)1 << 31) ? fail("trajectory too large") : 0; }
 
 // what both score entry points refuse before they look at the handle
 int score_args(double near, const double *val, const int32_t *cnt) {
@@ -1545,7 +1525,7 @@ int conflict_device(cfz_handle *h, int P, int V, int T, const double *d_tables, 
   HIP_OK(hipGetLastError());
   const int staged = T <= cfz::kConflictLdsT;
   hipLaunchKernelGGL(conflict_kernel, dim3((unsigned)(P * npair)), dim3(256), staged ? (size_t)T * 64 : 0, h->stream, h->kargs, V, T, D, staged,
-                     dcol, 1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3]), margin, margin * margin, dc, di);
+                     dcol, cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1), margin, margin * margin, dc, di);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1581,6 +1561,21 @@ int conflict_sizes(int P, int V, int T, int D) {
   return 0;
 }
 
+// a caller's pool of plan sets tables[P][V][T][7] with the map asked of it (cfz_plan_conflicts, cfz_plan_delays): what both refuse first,
+// in this order, and its upload once the call has got as far as the device
+int plan_pool_args(int P, int V, int T, const double *tables, int D, double margin) {
+  if (conflict_args(D, margin)) return -1;
+  if (P < 1 || T < 1) return fail("P, T must be positive");
+  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
+  if (!tables) return fail("null tables");
+  return conflict_sizes(P, V, T, D);
+}
+int plan_pool_upload(cfz_handle *h, int P, int V, int T, const double *tables, double *&d_tables) {
+  HIP_OK(hipSetDevice(h->device));
+  if (arena_reset(h->arena)) return -1;
+  return arena_upload(h, d_tables, tables, (size_t)P * V * T * 7);
+}
+
 // what the three delay entry points refuse before they look at the handle: the slack, the outputs, the box of the search and the caps
 // cap[P][V] (NULL: D for every vehicle)
 int delay_args(int P, int V, int D, int slack, const int32_t *cap, const int32_t *delays) {
@@ -1614,10 +1609,7 @@ int delay_launch(cfz_handle *h, int P, int V, int D, const int32_t *d_count, int
   const int no = delay_out_ints(V);
   int32_t *dcap = nullptr, *dout = nullptr;
   ARENA_ALLOC(h->arena, dout, (size_t)P * no * 4);
-  if (cap) {
-    ARENA_ALLOC(h->arena, dcap, (size_t)P * V * 4);
-    HIP_OK(hipMemcpyAsync(dcap, cap, (size_t)P * V * 4, hipMemcpyHostToDevice, h->stream));
-  }
+  if (cap && arena_upload(h, dcap, cap, (size_t)P * V)) return -1;
   hipLaunchKernelGGL(delay_kernel, dim3((unsigned)P), dim3(256), (size_t)npair * cfz::delay_words(D) * 4, h->stream, V, D, slack, d_count, cs,
                      d_clear, dcap, dout);
   HIP_OK(hipGetLastError());
@@ -1747,8 +1739,7 @@ int cfz_loop_record(cfz_handle *h, int K) {
 }
 
 int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status, int32_t *iters) {
-  if (loop_ready(h)) return -1;
-  if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  if (record_window(h, t0, K)) return -1;
   const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
   if (traj) HIP_OK(hipMemcpy(traj, h->lp.rec + (size_t)t0 * B * 7, (size_t)K * B * 7 * 8, hipMemcpyDeviceToHost));
   if (status || iters) {
@@ -1764,8 +1755,7 @@ int cfz_loop_history(cfz_handle *h, int t0, int K, double *traj, int32_t *status
 
 int cfz_loop_audit(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
                    int32_t *first_contact, int32_t *arrive) {
-  if (loop_ready(h)) return -1;
-  if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  if (record_window(h, t0, K)) return -1;
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t B = (size_t)S * V;
   if (arena_reset(h->arena)) return -1;
@@ -1787,9 +1777,9 @@ int cfz_audit_maps(cfz_handle *h, int K, int S, int V, const double *traj, const
                    const double *b_obs, const int32_t *map_of, double pos_tol, double psi_tol, double v_tol, double *clear, int32_t *where,
                    int32_t *first_contact, int32_t *arrive) {
   if (!h) return fail("null handle");
-  if (K < 1 || S < 1 || V < 1 || V > CFZ_MAX_NBR + 1) return fail("K, S must be positive and V in 1..CFZ_MAX_NBR+1");
+  if (traj_dims(K, S, V)) return -1;
   if (!traj || !goal) return fail("null trajectory or goal");
-  if ((size_t)K * S * V * 7 > ((size_t)1 << 31)) return fail("trajectory too large");
+  if (traj_fits(K, S, V)) return -1;
   if (M < 0) return fail("M must not be negative");
   const bool maps = M > 0 && A_obs;  // else: the handle's map for every scenario
   const int no = h->ks.n_obs;
@@ -1810,21 +1800,14 @@ int cfz_audit_maps(cfz_handle *h, int K, int S, int V, const double *traj, const
   double *dt_ = nullptr, *dg = nullptr;
   cfz::AuditPoly *dpoly = nullptr;
   int32_t *dof = nullptr;
-  ARENA_ALLOC(h->arena, dt_, (size_t)K * S * V * 7 * 8); ARENA_ALLOC(h->arena, dg, (size_t)S * V * 3 * 8);
-  HIP_OK(hipMemcpyAsync(dt_, traj, (size_t)K * S * V * 7 * 8, hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(dg, goal, (size_t)S * V * 3 * 8, hipMemcpyHostToDevice, h->stream));
-  if (maps) {
-    ARENA_ALLOC(h->arena, dpoly, poly.size() * sizeof(cfz::AuditPoly)); ARENA_ALLOC(h->arena, dof, (size_t)S * 4);
-    HIP_OK(hipMemcpyAsync(dpoly, poly.data(), poly.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice, h->stream));
-    HIP_OK(hipMemcpyAsync(dof, map_of, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
-  }
+  if (arena_upload(h, dt_, traj, (size_t)K * S * V * 7) || arena_upload(h, dg, goal, (size_t)S * V * 3)) return -1;
+  if (maps && (arena_upload(h, dpoly, poly.data(), poly.size()) || arena_upload(h, dof, map_of, (size_t)S))) return -1;
   return audit_launch(h, K, S, V, dt_, dg, dpoly, dof, pos_tol, psi_tol, v_tol, clear, where, first_contact, arrive);  // (ends synchronised: `poly` outlives its copy)
 }
 
 int cfz_loop_score(cfz_handle *h, int t0, int K, double pos_tol, double psi_tol, double v_tol, double near, double *val, int32_t *cnt) {
   if (score_args(near, val, cnt)) return -1;
-  if (loop_ready(h)) return -1;
-  if (t0 < 0 || K < 1 || t0 + K > h->lp.rec_used) return fail("steps [t0, t0 + K) are not in the record");
+  if (record_window(h, t0, K)) return -1;
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   const size_t B = (size_t)S * V;
   if (arena_reset(h->arena)) return -1;
@@ -1838,10 +1821,10 @@ int cfz_score(cfz_handle *h, int K, int S, int V, const double *traj, const int3
               const double *tables, const int32_t *table_of, const int32_t *k0, double pos_tol, double psi_tol, double v_tol, double near,
               double *val, int32_t *cnt) {
   if (score_args(near, val, cnt)) return -1;
-  if (K < 1 || S < 1 || V < 1 || V > CFZ_MAX_NBR + 1) return fail("K, S must be positive and V in 1..CFZ_MAX_NBR+1");
+  if (traj_dims(K, S, V)) return -1;
   if (P < 1 || T < 1) return fail("P, T must be positive");
   if (!traj || !tables || !table_of || !k0) return fail("null trajectory, tables, table_of or k0");
-  if ((size_t)K * S * V * 7 > ((size_t)1 << 31)) return fail("trajectory too large");
+  if (traj_fits(K, S, V)) return -1;
   if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
   for (int s = 0; s < S; ++s) {
     if (table_of[s] < 0 || table_of[s] >= P) return fail("table_of[s] outside [0, P)");
@@ -1850,33 +1833,22 @@ int cfz_score(cfz_handle *h, int K, int S, int V, const double *traj, const int3
   if (!h) return fail("null handle");
   HIP_OK(hipSetDevice(h->device));
   if (arena_reset(h->arena)) return -1;
-  const size_t B = (size_t)S * V, nt = (size_t)K * B * 7 * 8, np = (size_t)P * V * T * 7 * 8;
+  const size_t B = (size_t)S * V;
   double *dt_ = nullptr, *dp = nullptr;
   int32_t *dof = nullptr, *dk = nullptr, *dst = nullptr, *dit = nullptr;
-  ARENA_ALLOC(h->arena, dt_, nt); ARENA_ALLOC(h->arena, dp, np); ARENA_ALLOC(h->arena, dof, (size_t)S * 4); ARENA_ALLOC(h->arena, dk, (size_t)S * 4);
-  HIP_OK(hipMemcpyAsync(dt_, traj, nt, hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(dp, tables, np, hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(dof, table_of, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
-  HIP_OK(hipMemcpyAsync(dk, k0, (size_t)S * 4, hipMemcpyHostToDevice, h->stream));
-  if (status) { ARENA_ALLOC(h->arena, dst, (size_t)K * B * 4); HIP_OK(hipMemcpyAsync(dst, status, (size_t)K * B * 4, hipMemcpyHostToDevice, h->stream)); }
-  if (iters) { ARENA_ALLOC(h->arena, dit, (size_t)K * B * 4); HIP_OK(hipMemcpyAsync(dit, iters, (size_t)K * B * 4, hipMemcpyHostToDevice, h->stream)); }
+  if (arena_upload(h, dt_, traj, (size_t)K * B * 7) || arena_upload(h, dp, tables, (size_t)P * V * T * 7)) return -1;
+  if (arena_upload(h, dof, table_of, (size_t)S) || arena_upload(h, dk, k0, (size_t)S)) return -1;
+  if (status && arena_upload(h, dst, status, (size_t)K * B)) return -1;
+  if (iters && arena_upload(h, dit, iters, (size_t)K * B)) return -1;
   return score_launch(h, K, S, V, dt_, dst, dit, (long)B, T, dp, dof, dk, 0, pos_tol, psi_tol, v_tol, near, val, cnt);  // (ends synchronised)
 }
 
 int cfz_plan_conflicts(cfz_handle *h, int P, int V, int T, const double *tables, int D, double margin, double *clear, int32_t *info) {
-  if (conflict_args(D, margin)) return -1;
-  if (P < 1 || T < 1) return fail("P, T must be positive");
-  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
-  if (!tables) return fail("null tables");
-  if (conflict_sizes(P, V, T, D)) return -1;
+  if (plan_pool_args(P, V, T, tables, D, margin)) return -1;
   if (!h) return fail("null handle");
   if (V == 1) return 0;  // no pairs: nothing to launch, nothing to write
-  HIP_OK(hipSetDevice(h->device));
-  if (arena_reset(h->arena)) return -1;
-  const size_t nt = (size_t)P * V * T * 7 * 8;
   double *dt_ = nullptr;
-  ARENA_ALLOC(h->arena, dt_, nt);
-  HIP_OK(hipMemcpyAsync(dt_, tables, nt, hipMemcpyHostToDevice, h->stream));
+  if (plan_pool_upload(h, P, V, T, tables, dt_)) return -1;
   return conflict_launch(h, P, V, T, dt_, D, margin, clear, info);  // (ends synchronised)
 }
 
@@ -1904,31 +1876,18 @@ int cfz_delay_search(cfz_handle *h, int P, int V, int D, const int32_t *count, c
   if (arena_reset(h->arena)) return -1;
   int32_t *dn = nullptr;
   double *dc = nullptr;
-  ARENA_ALLOC(h->arena, dn, no * 4);
-  HIP_OK(hipMemcpyAsync(dn, count, no * 4, hipMemcpyHostToDevice, h->stream));
-  if (clear) {
-    ARENA_ALLOC(h->arena, dc, no * 8);
-    HIP_OK(hipMemcpyAsync(dc, clear, no * 8, hipMemcpyHostToDevice, h->stream));
-  }
+  if (arena_upload(h, dn, count, no) || (clear && arena_upload(h, dc, clear, no))) return -1;
   return delay_launch(h, P, V, D, dn, 1, dc, false, slack, cap, delays, info, rclear);  // (ends synchronised)
 }
 
 int cfz_plan_delays(cfz_handle *h, int P, int V, int T, const double *tables, int D, double margin, int slack, const int32_t *cap,
                     int32_t *delays, int32_t *info, double *rclear) {
-  if (conflict_args(D, margin)) return -1;
-  if (P < 1 || T < 1) return fail("P, T must be positive");
-  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
-  if (!tables) return fail("null tables");
-  if (conflict_sizes(P, V, T, D)) return -1;
+  if (plan_pool_args(P, V, T, tables, D, margin)) return -1;
   if (delay_args(P, V, D, slack, cap, delays)) return -1;
   if (!h) return fail("null handle");
   if (V == 1) { delay_single(P, true, delays, info, rclear); return 0; }
-  HIP_OK(hipSetDevice(h->device));
-  if (arena_reset(h->arena)) return -1;
-  const size_t nt = (size_t)P * V * T * 7 * 8;
   double *dt_ = nullptr;
-  ARENA_ALLOC(h->arena, dt_, nt);
-  HIP_OK(hipMemcpyAsync(dt_, tables, nt, hipMemcpyHostToDevice, h->stream));
+  if (plan_pool_upload(h, P, V, T, tables, dt_)) return -1;
   return plan_delays_launch(h, P, V, T, dt_, D, margin, slack, cap, delays, info, rclear);  // (ends synchronised)
 }
 

@@ -41,6 +41,8 @@
 #ifndef CFZ_SCORE_INL
 #define CFZ_SCORE_INL
 
+#include <stddef.h>
+
 #include "cfz_audit.inl"
 
 #if defined(__clang__)
@@ -127,6 +129,25 @@ struct ScoreIn {
   double g[4], il[2];
   double pos_tol, psi_tol, v_tol, near2;
 };
+
+// vehicle v of scenario s from the arrays of the whole window, as score_kernel receives them: traj[K][S][V][7] and its headings
+// cs[K][S][V][2], status / iters at the window's first step with steps si_stride apart (NULL: all 0), tables[P][V][T][7], table_of[S];
+// the clock before the window's first step is k0[s] - back, not below 0 (the CPU build passes back = 0)
+CFZ_CALL void score_in(ScoreIn &in, int s, int v, int K, int S, int V, const double *traj, const double *cs, const int32_t *status,
+                       const int32_t *iters, long si_stride, int T, const double *tables, const int32_t *table_of, const int32_t *k0,
+                       int back, const double g[4], const double il[2], double pos_tol, double psi_tol, double v_tol, double near2) {
+  in.K = K; in.V = V; in.v = v; in.T = T;
+  in.k0 = k0[s] - back;
+  if (in.k0 < 0) in.k0 = 0;
+  in.traj = traj + (size_t)s * V * 7; in.cs = cs + (size_t)s * V * 2;
+  in.plan = tables + ((size_t)table_of[s] * V + v) * T * 7;
+  in.step_stride = (long)S * V * 7; in.si_stride = si_stride;
+  in.status = status ? status + (size_t)s * V + v : nullptr;
+  in.iters = iters ? iters + (size_t)s * V + v : nullptr;
+  for (int i = 0; i < 4; ++i) in.g[i] = g[i];
+  in.il[0] = il[0]; in.il[1] = il[1];
+  in.pos_tol = pos_tol; in.psi_tol = psi_tol; in.v_tol = v_tol; in.near2 = near2;
+}
 
 CFZ_CALL const double *score_plan_row(const ScoreIn &in, int t) {
   long kr = (long)in.k0 + t + 1;

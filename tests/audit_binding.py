@@ -14,7 +14,8 @@ _lib = None
 
 
 def build(force=False):
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_audit_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_audit.inl")]
+    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_audit_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_audit.inl"),
+            os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_wave.inl")]
     return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 

@@ -20,7 +20,8 @@ OUT = ("delays", "found", "span", "total")
 
 
 def build(force=False):
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_delay_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_delay.inl")]
+    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_delay_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_delay.inl"),
+            os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_wave.inl")]
     return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 

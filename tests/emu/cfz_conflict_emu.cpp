@@ -1,8 +1,9 @@
 // Test-only CPU build of the conflict map of a plan pool: conflict_rez_amd/csrc/cfz_conflict.inl compiled with g++ (-ffp-contract=off),
-// the lanes that conflict_kernel gives a lag executed as a loop and merged as its butterfly does.  Never shipped, never loaded by the package.
+// the lanes that conflict_kernel gives a lag executed as a loop and merged by the butterfly of cfz_wave.inl.  Never shipped, never loaded by the package.
 #include <vector>
 
 #include "../../conflict_rez_amd/csrc/cfz_conflict.inl"
+#include "../../conflict_rez_amd/csrc/cfz_wave.inl"
 
 extern "C" {
 
@@ -13,8 +14,8 @@ int cfz_emu_plan_conflicts(int P, int V, int T, const double *tables, const doub
                            int32_t *info) {
   if (P < 1 || V < 1 || V > cfz::kAuditMaxV || T < 1 || D < 0 || !(margin >= 0.0) || nl < 1 || nl > 64 || (nl & (nl - 1))) return -1;
   const int npair = V * (V - 1) / 2;
-  const double il[2] = {1.0 / (g[0] + g[2]), 1.0 / (g[1] + g[3])};  // as cfz_engine.hip's conflict_launch
-  std::vector<double> cols((size_t)P * V * 4 * T);                  // as conflict_columns
+  const double il[2] = {cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1)};
+  std::vector<double> cols((size_t)P * V * 4 * T);  // as conflict_columns
   for (size_t v = 0; v < (size_t)P * V; ++v)
     for (int t = 0; t < T; ++t) {
       const double *z = tables + (v * T + t) * 7;
@@ -27,12 +28,9 @@ int cfz_emu_plan_conflicts(int P, int V, int T, const double *tables, const doub
       cfz::conflict_pair(V, q, u, w);
       const double *U = cols.data() + ((size_t)p * V + u) * 4 * T, *W = cols.data() + ((size_t)p * V + w) * 4 * T;
       for (int j = 0; j < 2 * D + 1; ++j) {
-        cfz::ConflictAcc acc[64], nxt[64];
+        cfz::ConflictAcc acc[64];
         for (int l = 0; l < nl; ++l) cfz::conflict_lane(acc[l], l, nl, T, j - D, U, W, g, il, margin, margin * margin);
-        for (int off = nl / 2; off > 0; off >>= 1) {
-          for (int l = 0; l < nl; ++l) { nxt[l] = acc[l]; cfz::conflict_merge(nxt[l], acc[l ^ off]); }
-          for (int l = 0; l < nl; ++l) acc[l] = nxt[l];
-        }
+        cfz::wave_merge_host<cfz::ConflictAcc, cfz::conflict_merge>(acc, nl, nl);
         const size_t o = ((size_t)p * npair + q) * (2 * D + 1) + j;
         cfz::conflict_store(acc[0], clear + o, info + o * cfz::kConflictNInfo);
         clear[o] = cfz::audit_key_distance(clear[o]);

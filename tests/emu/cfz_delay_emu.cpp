@@ -1,9 +1,10 @@
 // Test-only CPU build of the delay search over a conflict map: conflict_rez_amd/csrc/cfz_delay.inl compiled with g++, the lanes that
-// delay_kernel deals a shell's candidates to executed as a loop and merged as its butterfly does.  Never shipped, never loaded by the package.
+// delay_kernel deals a shell's candidates to executed as a loop and merged by the butterfly of cfz_wave.inl.  Never shipped, never loaded by the package.
 #include <algorithm>
 #include <vector>
 
 #include "../../conflict_rez_amd/csrc/cfz_delay.inl"
+#include "../../conflict_rez_amd/csrc/cfz_wave.inl"
 
 extern "C" {
 
@@ -17,7 +18,7 @@ int cfz_emu_delay_search(int P, int V, int D, const int32_t *count, const double
   if (box > 2147483648.0) return -1;
   const int npair = V * (V - 1) / 2, L = 2 * D + 1, nw = cfz::delay_words(D);
   std::vector<uint32_t> mask((size_t)(npair ? npair : 1) * nw);
-  std::vector<cfz::DelayAcc> acc(nl), nxt(nl);
+  std::vector<cfz::DelayAcc> acc(nl);
   for (int p = 0; p < P; ++p) {
     const int32_t *cnt = count + (size_t)p * npair * L;
     const double *clr = clear ? clear + (size_t)p * npair * L : nullptr;
@@ -38,10 +39,7 @@ int cfz_emu_delay_search(int P, int V, int D, const int32_t *count, const double
       cfz::DelayShell sh;
       cfz::delay_shell(V, m, sh);
       for (int l = 0; l < nl; ++l) cfz::delay_lane(acc[l], l, nl, V, D, m, sh, capv, mask.data(), nw);
-      for (int off = nl / 2; off > 0; off >>= 1) {
-        for (int l = 0; l < nl; ++l) { nxt[l] = acc[l]; cfz::delay_merge(nxt[l], acc[l ^ off]); }
-        acc = nxt;
-      }
+      cfz::wave_merge_host<cfz::DelayAcc, cfz::delay_merge>(acc.data(), nl, nl);
       best = acc[0];
       if (best.total != INT32_MAX) break;
     }

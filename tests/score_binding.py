@@ -26,7 +26,7 @@ KS = (1, 2, 7, 8, 9, 16, 17, 37, 130)
 
 def build(force=False):
     csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_score_emu.cpp"), os.path.join(csrc, "cfz_score.inl"), os.path.join(csrc, "cfz_audit.inl")]
+    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_score_emu.cpp"), os.path.join(csrc, "cfz_score.inl"), os.path.join(csrc, "cfz_audit.inl"), os.path.join(csrc, "cfz_wave.inl")]
     return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 
