@@ -29,6 +29,10 @@
 //                  delay, one workgroup per (set, pair), the pair's columns (conflict_columns) staged in LDS
 //   delay_kernel   the start delays that make a plan set conflict-free, searched over that map (cfz_delay.inl): one workgroup per set,
 //                  the windowed free mask as bits in LDS, span levels in ascending order
+//   coord_kernel   the coordination diagrams of a plan pool (cfz_coord.inl): which sample of one plan is too close to which sample of
+//                  another, as rows of bits, one workgroup per (set, pair, block of rows), a wavefront per row, a ballot per 64 columns
+//   schedule_kernel  hold-point schedules that make a plan set conflict-free (cfz_schedule.inl): one workgroup per set, a wavefront per
+//                  priority order, the reachable samples of a vehicle as one row of bits over the lanes
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
 // Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
@@ -59,6 +63,7 @@
 #include "cfz_score.inl"
 #include "cfz_conflict.inl"
 #include "cfz_delay.inl"
+#include "cfz_schedule.inl"
 #include "cfz_wave.inl"
 #include "cfz_disturb.inl"
 #include "cfz_comm.inl"
@@ -785,6 +790,165 @@ __global__ __launch_bounds__(256) void delay_kernel(int V, int D, int r, const i
   if (tid == 0) {
     int32_t *o = out + (size_t)p * delay_out_ints(V);
     cfz::delay_store(best, V, D, m, clr, o, o + V, (double *)(o + delay_out_ints(V) - 2));
+  }
+}
+
+// ---- coordination diagrams of a plan pool (cfz_coord.inl) -------------------------------------------------------------
+constexpr int kCoordRows = 32;  // rows of either side that one workgroup of coord_kernel writes
+
+// the rows blockIdx.y kCoordRows ... of both sides of one pair: a wavefront takes a row, a lane a column, a __ballot packs 64 predicates,
+// lane 0 stores the row's words with plain stores (every word of every row is written: out needs no clearing).  Forced inline, as
+// conflict_lags is.  out: the pair's [2][T][words].
+__device__ __forceinline__ void coord_rows(int T, int lu, int lw, const double *U, const double *W, const double g[4], const double il[2],
+                                           double margin, double margin2, uint32_t *out) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = cfz::coord_words(T);
+  const int r0 = blockIdx.y * kCoordRows, r1 = min(r0 + kCoordRows, T);
+  for (int side = 0; side < 2; ++side)
+    for (int row = r0 + wave; row < r1; row += 4)
+      for (int c = 0; c * 64 < T; ++c) {  // (the same trip count for every lane: the ballot is over the whole wavefront)
+        const bool b = cfz::coord_entry(side, T, lu, lw, row, c * 64 + lane, U, W, g, il, margin, margin2);
+        const unsigned long long m = __ballot(b);
+        if (lane == 0) cfz::coord_store(out + ((size_t)side * T + row) * nw, nw, c, m);
+      }
+}
+
+// One workgroup of 256 lanes per (set, pair, block of kCoordRows rows); blockIdx.x = p npair + q.  cols as conflict_kernel reads them,
+// staged in LDS alike; length[P][V] or NULL (T).  diag[P][npair][2][T][words].
+__global__ __launch_bounds__(256) void coord_kernel(const KArgs *__restrict__ ka, int V, int T, int staged, const double *cols,
+                                                    const int32_t *length, double il0, double il1, double margin, double margin2,
+                                                    uint32_t *diag) {
+  extern __shared__ __attribute__((aligned(16))) double coord_lds[];
+  const int npair = V * (V - 1) / 2, p = blockIdx.x / npair, q = blockIdx.x - p * npair;
+  int u, w;
+  cfz::conflict_pair(V, q, u, w);
+  const double *U = cols + ((size_t)p * V + u) * 4 * T, *W = cols + ((size_t)p * V + w) * 4 * T;
+  const int lu = length ? length[(size_t)p * V + u] : T, lw = length ? length[(size_t)p * V + w] : T;
+  double g[4];
+  for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
+  const double il[2] = {il0, il1};
+  uint32_t *out = diag + cfz::coord_offset(npair, T, p, q, 0);
+  if (staged) {
+    for (int i = threadIdx.x; i < 4 * T; i += 256) { coord_lds[i] = U[i]; coord_lds[4 * T + i] = W[i]; }
+    __syncthreads();
+    coord_rows(T, lu, lw, coord_lds, coord_lds + 4 * T, g, il, margin, margin2, out);
+  } else {
+    coord_rows(T, lu, lw, U, W, g, il, margin, margin2, out);
+  }
+}
+
+// ---- hold-point schedules over the diagrams (cfz_schedule.inl) --------------------------------------------------------
+// One order by one wavefront: its vehicles in turn, lane l holding word l of the reachable row.  The free words of kScheduleAhead steps
+// are loaded before those steps' dependent chain (one __shfl_up, four bit operations and a store per step) runs.  hist[H][words] and
+// sched[V][H] (by position in the order) are the wavefront's own, in LDS or in global memory: forced inline, so that each call reads them
+// in the address space they lie in.  holdw[64] (LDS): the vehicle's hold words, for the walk back, which every lane runs alike (its
+// reads are of addresses the lanes share) and lane 0 writes.  arr[16] (LDS): arrival and waits by vehicle.  -> feasible.
+__device__ __forceinline__ bool schedule_order(int V, int T, int H, int r, uint32_t order, const uint32_t *diag, const int *lens,
+                                               const uint8_t *hold, uint32_t *hist, uint16_t *sched, uint32_t *holdw, int *arr, int &makespan,
+                                               int &total) {
+  const int lane = threadIdx.x & 63, nw = cfz::coord_words(T);
+  makespan = 0; total = 0;
+  for (int k = 0; k < V; ++k) {
+    const int v = cfz::schedule_digit(order, k), len = lens[v], g = len - 1;
+    const uint32_t valid = cfz::schedule_valid_word(len, lane), hw = cfz::schedule_hold_word(hold + (size_t)v * T, len, lane);
+    holdw[lane] = hw;
+    auto fw = [&](int t) { return lane < nw ? cfz::schedule_free_word(diag, V, T, nw, H, r, order, k, sched, t, lane, valid) : 0u; };
+    uint32_t R = cfz::schedule_first(lane, fw(0));
+    if (lane < nw) hist[lane] = R;
+    bool alive = true;
+    for (int t0 = 1; t0 < H && alive; t0 += cfz::kScheduleAhead) {
+      uint32_t fr[cfz::kScheduleAhead];
+#pragma unroll
+      for (int j = 0; j < cfz::kScheduleAhead; ++j) fr[j] = t0 + j < H ? fw(t0 + j) : 0u;
+#pragma unroll
+      for (int j = 0; j < cfz::kScheduleAhead; ++j)
+        if (t0 + j < H) {
+          uint32_t prev = __shfl_up(R, 1, 64);
+          if (lane == 0) prev = 0u;
+          R = cfz::schedule_step(R, prev, hw, fr[j]);
+          if (lane < nw) hist[(size_t)(t0 + j) * nw + lane] = R;
+        }
+      alive = __ballot(R != 0u) != 0ull;  // (the same for every lane; an empty row stays empty)
+    }
+    if (!alive) return false;
+    __threadfence_block();  // the rows were written by their lanes, the walk reads them from every lane
+    const int a = cfz::schedule_walk(hist, nw, holdw, g, H, sched + (size_t)k * H, lane == 0);
+    __threadfence_block();  // and the schedule by lane 0
+    if (a < 0) return false;
+    if (lane == 0) { arr[v] = a; arr[cfz::kScheduleMaxV + v] = a - g; }
+    makespan = max(makespan, a); total += a;
+  }
+  return true;
+}
+
+// ints per set of schedule_kernel's small outputs: arrival[V], waits[V], info[5]
+__host__ __device__ constexpr int schedule_out_ints(int V) { return 2 * V + cfz::kScheduleNInfo; }
+
+// One workgroup of four wavefronts per plan set; blockIdx.x = p.  Pass 0: wavefront k takes orders k, k + 4, ... of orders[O] (packed,
+// schedule_pack) and keeps its best (makespan, total, index); the four are merged by a four-entry LDS exchange that every lane reads
+// after a barrier (schedule_merge, a total order: the decision is workgroup-uniform, the barrier sits in no divergent control flow).
+// Pass 1: wavefront 0 runs the winning order once more and writes schedule[P][V][H] and small[P][schedule_out_ints(V)] with plain
+// stores.  in_lds: schedule_wave_words(V, T, H) words per wavefront of dynamic LDS; else ws[P][4][that many] in global memory.
+// No floating point.
+__global__ __launch_bounds__(256) void schedule_kernel(int V, int T, int H, int r, int O, const uint32_t *orders, const uint32_t *diag,
+                                                       const int32_t *length, const uint8_t *hold, int in_lds, uint32_t *ws,
+                                                       int32_t *schedule, int32_t *small) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t schedule_lds[];
+  __shared__ uint32_t holdw[4][64];
+  __shared__ int arr[4][2 * cfz::kScheduleMaxV], lens[cfz::kScheduleMaxV], xch[4][4];
+  const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, npair = V * (V - 1) / 2, nw = cfz::coord_words(T);
+  if (threadIdx.x < V) lens[threadIdx.x] = length ? length[(size_t)p * V + threadIdx.x] : T;
+  __syncthreads();
+  const size_t per = cfz::schedule_wave_words(V, T, H);
+  const uint32_t *dg = diag + cfz::coord_offset(npair, T, p, 0, 0);
+  const uint8_t *hd = hold + (size_t)p * V * T;
+  uint32_t *gbase = in_lds ? nullptr : ws + ((size_t)p * 4 + wave) * per;
+  int32_t *sm = small + (size_t)p * schedule_out_ints(V);
+  cfz::ScheduleBest best;
+  cfz::schedule_clear(best);
+  for (int pass = 0; pass < 2; ++pass) {
+    const bool found = best.makespan != INT32_MAX;  // (pass 1: the merged best, the same for every lane)
+    const int first = pass == 0 ? wave : (wave == 0 && found ? best.index : O), stride = pass == 0 ? 4 : O;
+    for (int o = first; o < O; o += stride) {
+      int mk, tot;
+      bool ok;
+      const uint16_t *sched;
+      if (in_lds) {
+        uint32_t *b = schedule_lds + (size_t)wave * per;
+        sched = (const uint16_t *)(b + (size_t)H * nw);
+        ok = schedule_order(V, T, H, r, orders[o], dg, lens, hd, b, (uint16_t *)(b + (size_t)H * nw), holdw[wave], arr[wave], mk, tot);
+        if (pass == 1 && ok)
+          for (int k = 0; k < V; ++k) {
+            int32_t *out = schedule + ((size_t)p * V + cfz::schedule_digit(orders[o], k)) * H;
+            for (int t = lane; t < H; t += 64) out[t] = sched[(size_t)k * H + t];
+          }
+      } else {
+        sched = (const uint16_t *)(gbase + (size_t)H * nw);
+        ok = schedule_order(V, T, H, r, orders[o], dg, lens, hd, gbase, (uint16_t *)(gbase + (size_t)H * nw), holdw[wave], arr[wave], mk, tot);
+        if (pass == 1 && ok)
+          for (int k = 0; k < V; ++k) {
+            int32_t *out = schedule + ((size_t)p * V + cfz::schedule_digit(orders[o], k)) * H;
+            for (int t = lane; t < H; t += 64) out[t] = sched[(size_t)k * H + t];
+          }
+      }
+      if (pass == 0 && ok) cfz::schedule_take(best, mk, tot, o);
+      if (pass == 1 && lane < V) { sm[lane] = arr[0][lane]; sm[V + lane] = arr[0][cfz::kScheduleMaxV + lane]; }
+    }
+    if (pass == 0) {
+      if (lane == 0) { xch[wave][0] = best.makespan; xch[wave][1] = best.total; xch[wave][2] = best.index; xch[wave][3] = best.feasible; }
+      __syncthreads();
+      cfz::schedule_clear(best);
+      for (int k = 0; k < 4; ++k) {
+        cfz::ScheduleBest b;
+        b.makespan = xch[k][0]; b.total = xch[k][1]; b.index = xch[k][2]; b.feasible = xch[k][3];
+        cfz::schedule_merge(best, b);
+      }
+    } else if (wave == 0) {
+      if (!found) {
+        for (int i = lane; i < V * H; i += 64) schedule[(size_t)p * V * H + i] = -1;
+        if (lane < V) { sm[lane] = -1; sm[V + lane] = -1; }
+      }
+      if (lane == 0) cfz::schedule_info(best, sm + 2 * V);
+    }
   }
 }
 
@@ -1637,6 +1801,119 @@ int plan_delays_launch(cfz_handle *h, int P, int V, int T, const double *d_table
   return delay_launch(h, P, V, D, di + 2, CFZ_CONFLICT_NINFO, dc, true, slack, cap, delays, info, rclear);
 }
 
+// what the coordination and the schedule entry points refuse of a pool's sizes, its margin and its lengths length[P][V] (NULL: T) before
+// they look at the handle
+int coord_args(int P, int V, int T, double margin, const int32_t *length) {
+  static_assert(cfz::kScheduleMaxT == CFZ_SCHEDULE_MAX_T && cfz::kScheduleMaxH == CFZ_SCHEDULE_MAX_H && cfz::kScheduleNInfo == CFZ_SCHEDULE_NINFO &&
+                    cfz::kScheduleMaxV == CFZ_MAX_NBR + 1, "cfz_schedule.inl and confrez_hip.h disagree");
+  if (!(margin >= 0.0) || !std::isfinite(margin)) return fail("margin must be finite and not negative");
+  if (P < 1 || T < 1) return fail("P, T must be positive");
+  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
+  if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
+  if ((size_t)P * (V * (V - 1) / 2) * 2 * T * cfz::coord_words(T) > ((size_t)1 << 31)) return fail("coordination diagram too large");
+  if (length)
+    for (size_t i = 0; i < (size_t)P * V; ++i)
+      if (length[i] < 1 || length[i] > T) return fail("a length lies outside [1, T]");
+  return 0;
+}
+
+// what both schedule entry points refuse next: the horizon, the slack, the orders orders[O][V], the hold mask and the outputs
+int schedule_args(int P, int V, int T, const uint8_t *hold, int H, int slack, int O, const int32_t *orders, const int32_t *schedule) {
+  if (H < 1 || O < 1) return fail("H, O must be positive");
+  if (T > CFZ_SCHEDULE_MAX_T) return fail("T must not exceed CFZ_SCHEDULE_MAX_T");
+  if (H > CFZ_SCHEDULE_MAX_H) return fail("H must not exceed CFZ_SCHEDULE_MAX_H");
+  if (H < T) return fail("H must not be below T");
+  if (slack < 0) return fail("slack must not be negative");
+  if (!hold) return fail("null hold");
+  if (!orders) return fail("null orders");
+  if (!schedule) return fail("null schedule");
+  for (int o = 0; o < O; ++o)
+    if (!cfz::schedule_is_permutation(V, orders + (size_t)o * V)) return fail("an order is not a permutation of the vehicles");
+  if ((size_t)P * V * H > ((size_t)1 << 31)) return fail("schedule too large");
+  if ((size_t)P * 4 * cfz::schedule_wave_words(V, T, H) > ((size_t)1 << 29)) return fail("schedule workspace too large");
+  return 0;
+}
+
+// the coordination diagrams of P plan sets x V vehicles x T samples (V > 1) that lie on the device (conflict_columns, coord_kernel), left
+// on the device: diag[P][npair][2][T][words], from the arena, which the caller has reset.  length: the caller's host array or NULL;
+// dlen its copy on the device.  Nothing is waited for.
+int coord_device(cfz_handle *h, int P, int V, int T, const double *d_tables, const int32_t *length, double margin, uint32_t *&diag,
+                 int32_t *&dlen) {
+  const int npair = V * (V - 1) / 2;
+  const double *g = h->ks.g;
+  const long n = (long)P * V * T;
+  double *dcol = nullptr;
+  dlen = nullptr;
+  ARENA_ALLOC(h->arena, dcol, (size_t)n * 4 * 8);
+  ARENA_ALLOC(h->arena, diag, (size_t)P * npair * 2 * T * cfz::coord_words(T) * 4);
+  if (length && arena_upload(h, dlen, length, (size_t)P * V)) return -1;
+  hipLaunchKernelGGL(conflict_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, T, d_tables, dcol);
+  HIP_OK(hipGetLastError());
+  const int staged = T <= cfz::kConflictLdsT;
+  hipLaunchKernelGGL(coord_kernel, dim3((unsigned)(P * npair), (unsigned)((T + kCoordRows - 1) / kCoordRows)), dim3(256), staged ? (size_t)T * 64 : 0,
+                     h->stream, h->kargs, V, T, staged, dcol, dlen, cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1), margin, margin * margin, diag);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// side 0 of the diagrams of a pool on the device into the caller's blocked[P][npair][T][words]: what cfz_plan_coordination returns.  The
+// arena is reset by the caller.  Ends synchronised.
+int coord_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, const int32_t *length, double margin, uint32_t *blocked) {
+  uint32_t *diag = nullptr;
+  int32_t *dlen = nullptr;
+  if (coord_device(h, P, V, T, d_tables, length, margin, diag, dlen)) return -1;
+  const size_t row = (size_t)T * cfz::coord_words(T) * 4;
+  HIP_OK(hipMemcpy2DAsync(blocked, row, diag, 2 * row, row, (size_t)P * (V * (V - 1) / 2), hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the answer of a set of one vehicle: nothing to avoid, it drives through; every order of the list is feasible and the first one wins
+void schedule_single(int P, int T, const int32_t *length, int H, int O, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info) {
+  for (int p = 0; p < P; ++p) {
+    const int g = (length ? length[p] : T) - 1;
+    for (int t = 0; t < H; ++t) schedule[(size_t)p * H + t] = t < g ? t : g;
+    if (arrival) arrival[p] = g;
+    if (waits) waits[p] = 0;
+    if (info) { int32_t *o = info + (size_t)p * CFZ_SCHEDULE_NINFO; o[0] = 1; o[1] = 0; o[2] = g; o[3] = g; o[4] = O; }
+  }
+}
+
+// the diagrams of a pool on the device, searched there by schedule_kernel (V > 1): what cfz_plan_schedule and cfz_loop_plan_schedule
+// share.  length, hold, orders and the outputs are the caller's host arrays (arrival, waits, info may be NULL).  The arena is reset by the
+// caller.  Ends synchronised.
+int schedule_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, const int32_t *length, const uint8_t *hold, int H, double margin,
+                    int slack, int O, const int32_t *orders, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info) {
+  uint32_t *diag = nullptr, *dord = nullptr, *ws = nullptr;
+  int32_t *dlen = nullptr, *dsched = nullptr, *dsmall = nullptr;
+  uint8_t *dhold = nullptr;
+  if (coord_device(h, P, V, T, d_tables, length, margin, diag, dlen)) return -1;
+  std::vector<uint32_t> packed((size_t)O);
+  for (int o = 0; o < O; ++o) packed[o] = cfz::schedule_pack(V, orders + (size_t)o * V);
+  const int no = schedule_out_ints(V);
+  const size_t per = cfz::schedule_wave_words(V, T, H), lds = 4 * per * 4;
+  const int in_lds = lds <= (size_t)cfz::kScheduleLdsBytes;
+  if (arena_upload(h, dhold, hold, (size_t)P * V * T) || arena_upload(h, dord, packed.data(), packed.size())) return -1;
+  ARENA_ALLOC(h->arena, dsched, (size_t)P * V * H * 4); ARENA_ALLOC(h->arena, dsmall, (size_t)P * no * 4);
+  if (!in_lds) ARENA_ALLOC(h->arena, ws, (size_t)P * 4 * per * 4);
+  if (in_lds)  // (beyond 64 KB of dynamic LDS a kernel has to be told)
+    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(schedule_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, cfz::kScheduleLdsBytes));
+  hipLaunchKernelGGL(schedule_kernel, dim3((unsigned)P), dim3(256), in_lds ? lds : 0, h->stream, V, T, H, slack, O, dord, diag, dlen, dhold, in_lds,
+                     ws, dsched, dsmall);
+  HIP_OK(hipGetLastError());
+  std::vector<int32_t> out((size_t)P * no);
+  HIP_OK(hipMemcpyAsync(schedule, dsched, (size_t)P * V * H * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipMemcpyAsync(out.data(), dsmall, out.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));  // (packed and out live until here)
+  for (int p = 0; p < P; ++p) {
+    const int32_t *o = out.data() + (size_t)p * no;
+    if (arrival) memcpy(arrival + (size_t)p * V, o, (size_t)V * 4);
+    if (waits) memcpy(waits + (size_t)p * V, o + V, (size_t)V * 4);
+    if (info) memcpy(info + (size_t)p * CFZ_SCHEDULE_NINFO, o + 2 * V, CFZ_SCHEDULE_NINFO * 4);
+  }
+  return 0;
+}
+
 // What the pool kernels take, composed from the two per-scenario settings: one KArgs block per (problem, map) pair that some scenario
 // uses, in the order of first use, and the block of every scenario.  probs[P], problem_of[S] as cfz_loop_set_problems fills them (probs
 // NULL: the handle's problem for every scenario); map_tab[M][n_obs][20] (device), map_of[S] as cfz_loop_set_maps does (map_tab NULL: the
@@ -1901,6 +2178,42 @@ int cfz_loop_plan_delays(cfz_handle *h, int D, double margin, int slack, const i
   if (V == 1) { delay_single(h->lp.P, true, delays, info, rclear); return 0; }
   if (arena_reset(h->arena)) return -1;
   return plan_delays_launch(h, h->lp.P, V, h->lp.T, h->lp.ref_table, D, margin, slack, cap, delays, info, rclear);
+}
+
+int cfz_plan_coordination(cfz_handle *h, int P, int V, int T, const double *tables, const int32_t *length, double margin, uint32_t *blocked) {
+  if (coord_args(P, V, T, margin, length)) return -1;
+  if (!tables) return fail("null tables");
+  if (!blocked) return fail("null blocked");
+  if (!h) return fail("null handle");
+  if (V == 1) return 0;  // no pairs: nothing to launch, nothing to write
+  double *dt_ = nullptr;
+  if (plan_pool_upload(h, P, V, T, tables, dt_)) return -1;
+  return coord_launch(h, P, V, T, dt_, length, margin, blocked);  // (ends synchronised)
+}
+
+int cfz_plan_schedule(cfz_handle *h, int P, int V, int T, const double *tables, const int32_t *length, const uint8_t *hold, int H, double margin,
+                      int slack, int O, const int32_t *orders, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info) {
+  if (coord_args(P, V, T, margin, length)) return -1;
+  if (!tables) return fail("null tables");
+  if (schedule_args(P, V, T, hold, H, slack, O, orders, schedule)) return -1;
+  if (!h) return fail("null handle");
+  if (V == 1) { schedule_single(P, T, length, H, O, schedule, arrival, waits, info); return 0; }  // no pairs: nothing to launch
+  double *dt_ = nullptr;
+  if (plan_pool_upload(h, P, V, T, tables, dt_)) return -1;
+  return schedule_launch(h, P, V, T, dt_, length, hold, H, margin, slack, O, orders, schedule, arrival, waits, info);  // (ends synchronised)
+}
+
+int cfz_loop_plan_schedule(cfz_handle *h, const int32_t *length, const uint8_t *hold, int H, double margin, int slack, int O,
+                           const int32_t *orders, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info) {
+  if (!(margin >= 0.0) || !std::isfinite(margin)) return fail("margin must be finite and not negative");
+  if (slack < 0) return fail("slack must not be negative");
+  if (loop_ready(h)) return -1;  // (the lengths, the mask, the orders and the outputs have the pool's sizes: checked below)
+  const int P = h->lp.P, V = h->ks.n_nbr + 1, T = h->lp.T;
+  if (coord_args(P, V, T, margin, length)) return -1;
+  if (schedule_args(P, V, T, hold, H, slack, O, orders, schedule)) return -1;
+  if (V == 1) { schedule_single(P, T, length, H, O, schedule, arrival, waits, info); return 0; }
+  if (arena_reset(h->arena)) return -1;
+  return schedule_launch(h, P, V, T, h->lp.ref_table, length, hold, H, margin, slack, O, orders, schedule, arrival, waits, info);
 }
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {

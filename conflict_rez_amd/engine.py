@@ -4,6 +4,7 @@ This is the only place the Python package touches the solver.  There is no CPU f
 if the HIP library is missing or no GPU is visible, construction raises.
 """
 import ctypes as C
+import itertools
 import os
 from dataclasses import dataclass, field
 
@@ -200,6 +201,10 @@ def load_library(path=None):
         lib.cfz_delay_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
         lib.cfz_plan_delays.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
         lib.cfz_loop_plan_delays.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
+    if hasattr(lib, "cfz_plan_schedule"):
+        lib.cfz_plan_coordination.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, vp]
+        lib.cfz_plan_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        lib.cfz_loop_plan_schedule.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -209,7 +214,8 @@ EXPORTS = (
     "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
     "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
     "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps "
-    "cfz_loop_score cfz_score cfz_plan_conflicts cfz_loop_plan_conflicts cfz_delay_search cfz_plan_delays cfz_loop_plan_delays"
+    "cfz_loop_score cfz_score cfz_plan_conflicts cfz_loop_plan_conflicts cfz_delay_search cfz_plan_delays cfz_loop_plan_delays "
+    "cfz_plan_coordination cfz_plan_schedule cfz_loop_plan_schedule"
 ).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
@@ -297,6 +303,52 @@ def _delay_out(P, V):
 
 def _delay_dict(delays, info, rclear):
     return dict(delays=delays, found=info[:, 0] == 1, span=info[:, 1], total=info[:, 2], clear=rclear)
+
+
+def _length_arg(length, P, V):
+    """length None, or [V] (every set's) or [P, V] whole numbers as a contiguous int32 [P, V] (the library checks the range)."""
+    if length is None:
+        return None
+    n = np.asarray(length)
+    if n.shape not in ((V,), (P, V)) or n.dtype.kind not in "iu":
+        raise ValueError(f"expected whole numbers length of shape [{V}] or [{P}, {V}], got {n.dtype} {n.shape}")
+    return np.ascontiguousarray(np.broadcast_to(n.astype(np.int32), (P, V)))
+
+
+def _schedule_args(hold, horizon, margin, slack, orders, length, P, V, T, spec):
+    """(hold, H, margin, slack, orders, length) of a schedule call on P sets x V vehicles x T samples: hold [V, T] (every set's) or
+    [P, V, T], non-zero where a vehicle may wait, as contiguous uint8; horizon None: T + 64; margin None: the problem's `dmin`; orders
+    None: every permutation in `itertools.permutations` order for V <= 4, else [O, V] or one order [V], as contiguous int32."""
+    hold = np.asarray(hold)
+    if hold.shape not in ((V, T), (P, V, T)):
+        raise ValueError(f"expected hold of shape [{V}, {T}] or [{P}, {V}, {T}], got {hold.shape}")
+    hold = np.ascontiguousarray(np.broadcast_to(hold != 0, (P, V, T)), dtype=np.uint8)
+    H = T + 64 if horizon is None else int(horizon)
+    if horizon is not None and H != horizon:
+        raise ValueError(f"horizon must be a whole number of samples, got {horizon!r}")
+    r = int(slack)
+    if r != slack or r < 0:
+        raise ValueError(f"slack must be a non-negative whole number of samples, got {slack!r}")
+    if orders is None:
+        if V > 4:
+            raise ValueError(f"orders is required for more than 4 vehicles ({V}! orders are not searched by default): pass a list [O, {V}]")
+        orders = list(itertools.permutations(range(V)))
+    o = np.asarray(orders)
+    if o.ndim == 1:
+        o = o[None]
+    if o.ndim != 2 or o.shape[1] != V or o.shape[0] == 0 or o.dtype.kind not in "iu":
+        raise ValueError(f"expected whole numbers orders of shape [O, {V}], got {o.dtype} {o.shape}")
+    return hold, H, float(spec.dmin if margin is None else margin), r, np.ascontiguousarray(o, dtype=np.int32), _length_arg(length, P, V)
+
+
+def _schedule_out(P, V, H):
+    """The raw arrays of the schedule entry points: schedule [P, V, H], arrival [P, V], waits [P, V], info [P, 5]."""
+    return np.full((P, V, H), -1, np.int32), np.full((P, V), -1, np.int32), np.full((P, V), -1, np.int32), np.full((P, 5), -1, np.int32)
+
+
+def _schedule_dict(schedule, arrival, waits, info):
+    return dict(schedule=schedule, arrival=arrival, waits=waits, found=info[:, 0] == 1, order=info[:, 1], makespan=info[:, 2], total=info[:, 3],
+                feasible_orders=info[:, 4])
 
 
 def conflict_summary(out):
@@ -645,7 +697,7 @@ class Engine:
         self.options = dict(options)  # (the base of the overrides of loop_set_problems)
         self._h = C.c_void_p()
         self._S = self._V = 0  # scenarios and vehicles of the closed loop; 0 until loop_init (the library refuses loop calls before it)
-        self._P = 0  # plan sets of the closed loop's pool
+        self._P = self._T = 0  # plan sets of the closed loop's pool and their samples
         self._rec_cap = self._rec_used = 0
         cs, co = spec.to_c(), default_options(**options)
         _ck(self.lib.cfz_create(C.byref(cs), C.byref(co), int(device), self.max_batch, C.byref(self._h)), "cfz_create")
@@ -775,7 +827,7 @@ class Engine:
             self._ck(self.lib.cfz_loop_init_tables(self._h, S, P, T, _ptr(ref_table), _ptr(tof), _ptr(k0), _ptr(noise)),
                      "cfz_loop_init_tables")
         self._S, self._V = S, V
-        self._P = 1 if ref_table.ndim == 3 else ref_table.shape[0]
+        self._P, self._T = (1 if ref_table.ndim == 3 else ref_table.shape[0]), T
         self._rec_cap, self._rec_used = 0, 0
 
     def loop_set_order(self, order):
@@ -1085,6 +1137,59 @@ class Engine:
         delays, info, rclear = _delay_out(self._P, self._V)
         self._ck(self.lib.cfz_loop_plan_delays(self._h, D, margin, slack, _ptr(cap), _ptr(delays), _ptr(info), _ptr(rclear)), "cfz_loop_plan_delays")
         return _delay_dict(delays, info, rclear)
+
+    def plan_coordination(self, tables, margin=None, length=None):
+        """`cfz_plan_coordination`: the coordination diagrams of the plan sets tables [P,V,T,7] (or one set [V,T,7]: P = 1) ->
+        dict(blocked [P, npair, T, T] bool, pairs [npair, 2] (u < w)).  blocked[p, q, i, j]: the body of u at its sample i and the body of
+        w at its sample j are closer than margin [m] (None: the problem's `dmin`); False beyond length [V] or [P, V] (None: T).  The
+        conflict map's count at lag tau is the sum of the diagram along the samples of that lag."""
+        tables = np.ascontiguousarray(tables, dtype=np.float64)
+        if tables.ndim == 3:
+            tables = tables[None]
+        if tables.ndim != 4 or tables.shape[3] != 7 or 0 in tables.shape:
+            raise ValueError(f"expected tables of shape [P, V, T, 7] or [V, T, 7], got {tables.shape}")
+        P, V, T = tables.shape[:3]
+        npair, nw = V * (V - 1) // 2, (T + 31) // 32
+        words = np.zeros((P, npair, T, nw), np.uint32)
+        self._ck(self.lib.cfz_plan_coordination(self._h, P, V, T, _ptr(tables), _ptr(_length_arg(length, P, V)),
+                                                float(self.spec.dmin if margin is None else margin), _ptr(words)), "cfz_plan_coordination")
+        bits = np.unpackbits(words.view(np.uint8), axis=-1, bitorder="little")[..., :T].astype(bool)  # (little-endian words)
+        pairs = np.array([(u, w) for u in range(V) for w in range(u + 1, V)], np.int32).reshape(-1, 2)
+        return dict(blocked=bits, pairs=pairs)
+
+    def plan_schedule(self, tables, hold, horizon=None, margin=None, slack=0, orders=None, length=None):
+        """`cfz_plan_schedule`: hold-point schedules that make every plan set of tables [P,V,T,7] (or one set [V,T,7]) conflict-free ->
+        dict(schedule [P, V, H] int32 (the sample of vehicle v at step t; -1: no order is feasible), arrival [P, V] (the first step at the
+        goal sample), waits [P, V] (steps spent waiting before it), found [P] bool, order [P] (the index of the winning order), makespan
+        [P] (the largest arrival), total [P] (their sum), feasible_orders [P]).  hold [V, T] or [P, V, T]: non-zero where a vehicle may
+        wait for any number of steps (`scenarios.hold_points`; the goal sample length - 1 always, `scenarios.plan_lengths`).  The vehicles
+        are scheduled one after the other in a priority order, each arriving as early as the earlier ones' schedules allow and waiting
+        as late as possible, with `slack` samples of timing error tolerated around every step; over `orders` (None: all V! for V <= 4)
+        the answer is the smallest under (makespan, total, index).  horizon None: T + 64 steps.  `scenarios.schedule_tables(tables,
+        schedule)` gives the tables `loop_init` takes."""
+        tables = np.ascontiguousarray(tables, dtype=np.float64)
+        if tables.ndim == 3:
+            tables = tables[None]
+        if tables.ndim != 4 or tables.shape[3] != 7 or 0 in tables.shape:
+            raise ValueError(f"expected tables of shape [P, V, T, 7] or [V, T, 7], got {tables.shape}")
+        P, V, T = tables.shape[:3]
+        hold, H, margin, slack, orders, length = _schedule_args(hold, horizon, margin, slack, orders, length, P, V, T, self.spec)
+        out = _schedule_out(P, V, max(H, 1))
+        self._ck(self.lib.cfz_plan_schedule(self._h, P, V, T, _ptr(tables), _ptr(length), _ptr(hold), H, margin, slack, len(orders), _ptr(orders),
+                                            *(_ptr(a) for a in out)), "cfz_plan_schedule")
+        return _schedule_dict(*out)
+
+    def loop_plan_schedule(self, hold, horizon=None, margin=None, slack=0, orders=None, length=None):
+        """`cfz_loop_plan_schedule`: `plan_schedule` of the pool that `loop_init` left on the device (nothing is uploaded but the hold
+        mask, the lengths and the orders; the loop is left as it is) -> the same dict, P the pool's."""
+        P, V, T = self._P, self._V, self._T
+        if not P:  # (the library refuses the call; it reads none of the arrays first)
+            self._ck(self.lib.cfz_loop_plan_schedule(self._h, None, None, 1, 0.0, 0, 1, None, None, None, None, None), "cfz_loop_plan_schedule")
+        hold, H, margin, slack, orders, length = _schedule_args(hold, horizon, margin, slack, orders, length, P, V, T, self.spec)
+        out = _schedule_out(P, V, max(H, 1))
+        self._ck(self.lib.cfz_loop_plan_schedule(self._h, _ptr(length), _ptr(hold), H, margin, slack, len(orders), _ptr(orders), *(_ptr(a) for a in out)),
+                 "cfz_loop_plan_schedule")
+        return _schedule_dict(*out)
 
     def loop_last_converged(self):
         """Solves of the last `loop_run` that converged (status 0)."""

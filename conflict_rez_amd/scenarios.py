@@ -371,6 +371,66 @@ def delay_tables(tables, delays):
     return out[0] if single else out
 
 
+def _plan_sets(tables):
+    """(tables as [P, V, T, 7], whether a single set [V, T, 7] was given)."""
+    tables = np.asarray(tables, dtype=np.float64)
+    single = tables.ndim == 3
+    tab = tables[None] if single else tables
+    if tab.ndim != 4 or tab.shape[3] != 7 or 0 in tab.shape:
+        raise ValueError(f"expected tables of shape [P, V, T, 7] or [V, T, 7], got {tables.shape}")
+    return tab, single
+
+
+def plan_lengths(tables):
+    """The length of every plan of tables [V,T,7] or [P,V,T,7] that are held at their last pose to a common T: the first sample from
+    which the pose (x, y, psi) no longer changes, plus one -> int32 [V] or [P,V], in [1, T].  What `Engine.plan_schedule` takes as
+    `length`: the goal sample is length - 1, what lies beyond is padding."""
+    tab, single = _plan_sets(tables)
+    T = tab.shape[2]
+    moved = (tab[:, :, :, :3] != tab[:, :, -1:, :3]).any(-1)  # [P, V, T]: the pose differs from the last one
+    last = np.where(moved.any(-1), T - 1 - np.argmax(moved[:, :, ::-1], axis=-1), -1)  # the last sample that differs, -1: none
+    out = (last + 2).astype(np.int32)
+    return out[0] if single else out
+
+
+def hold_points(tables, v_tol=0.1, length=None):
+    """Where the vehicles of tables [V,T,7] or [P,V,T,7] may wait: sample 0, every sample with |v| <= v_tol (a parking manoeuvre rests at
+    each change of direction) and everything from the goal sample length - 1 on (length None: `plan_lengths(tables)`) -> uint8 of shape
+    [V,T] or [P,V,T], what `Engine.plan_schedule` takes as `hold`."""
+    tab, single = _plan_sets(tables)
+    P, V, T = tab.shape[:3]
+    n = plan_lengths(tab) if length is None else np.broadcast_to(np.asarray(length), (P, V))
+    hold = np.abs(tab[..., 3]) <= v_tol
+    hold[:, :, 0] = True
+    hold |= np.arange(T)[None, None, :] >= (n[:, :, None] - 1)
+    hold = hold.astype(np.uint8)
+    return hold[0] if single else hold
+
+
+def schedule_tables(tables, schedule):
+    """Plan sets driven along a schedule of `Engine.plan_schedule`: tables [V,T,7] or [P,V,T,7], schedule whole samples [V,H] or [P,V,H],
+    non-decreasing in t.  Row t of vehicle v is its row schedule[v, t]; where the vehicle is held (the next row is the same sample, and
+    it is not the schedule's last sample, the goal) v = a = w = 0 with the pose and the steering angle kept; rows at the goal are
+    copies -> tables of length H, shaped as given: what `Engine.loop_init` takes.  For a schedule that is a start delay,
+    schedule[v, t] = clip(t - d[v], 0, T - 1), this is `delay_tables(tables, d)`."""
+    tab, single = _plan_sets(tables)
+    P, V, T = tab.shape[:3]
+    s = np.asarray(schedule)
+    if s.dtype.kind not in "iu":
+        raise ValueError(f"schedule must hold whole samples, got dtype {s.dtype}")
+    if single and s.ndim == 2:
+        s = s[None]
+    if s.ndim != 3 or s.shape[:2] != (P, V) or s.shape[2] == 0:
+        raise ValueError(f"schedule must have shape ({P}, {V}, H), got {np.asarray(schedule).shape}")
+    if (s < 0).any() or (s >= T).any() or (np.diff(s, axis=2) < 0).any():
+        raise ValueError("schedule must hold samples in [0, T) that do not decrease (a set without an answer has none)")
+    out = np.take_along_axis(tab, s[..., None].astype(np.int64), axis=2)
+    held = np.zeros(s.shape, bool)
+    held[:, :, :-1] = (s[:, :, 1:] == s[:, :, :-1]) & (s[:, :, :-1] < s[:, :, -1:])
+    out[..., [3, 5, 6]] = np.where(held[..., None], 0.0, out[..., [3, 5, 6]])
+    return out[0] if single else out
+
+
 def distinct_strategies(n_vehicles=4, delays=(0, 1, 2)):
     """The distinct strategies `strategy.generate_strategy` gives over every priority order x start delays in delays^n (infeasible
     combinations skipped), in the order first met.  Returns (strategies, combos): combos[i] lists the (order, delays) that give

@@ -40,15 +40,23 @@
    delayed plans; a closing line says how many of the strategies whose plans overlap were resolved and at which spans.  The closed loop
    is then run on the delayed plans (`scenarios.delay_tables`; starts sampled from them), so that the ranking answers which strategies
    are contact-free once resolved.  The same search as a numpy brute force over all (D+1)^V delay vectors of a set is timed next to it.
+9. --holds V_TOL (with --lags D --resolve R): one `Engine.loop_plan_schedule` call on the same pool: per strategy a prioritised schedule
+   in which a vehicle may wait wherever its plan rests (`scenarios.hold_points`: |v| <= V_TOL, the cusps of a parking manoeuvre), not
+   only at its start, over all priority orders and T + 64 steps, with R samples of slack.  The rows gain the order, the waits, where they
+   are taken ("vehicle@sample") and the makespan; the closed loop is run on the delayed plans for its contact count and then, for the
+   table, on the scheduled plans (`scenarios.schedule_tables`); a closing line says how many strategies start delays resolve, how many
+   holds resolve, and how many of each finish every sampled closed loop without contact.  The same search in numpy over the diagrams
+   read back (`Engine.plan_coordination`) and that read-back alone are timed next to it.
 
 usage: python examples/evaluate_strategies.py [--starts M] [--steps K] [--seed SEED] [--exchange {jacobi,sequential}]
                                               [--noise-levels L0,L1,...] [--noise-seed SEED]
                                               [--drop-rates P0,P1,...] [--max-age A] [--no-compensate] [--comm-seed SEED]
                                               [--dmin D0,D1,...] [--obstacle-margins M0,M1,...]
-                                              [--lags D [--resolve R]]
+                                              [--lags D [--resolve R [--holds V_TOL]]]
 """
 import argparse
 import dataclasses
+import itertools
 import os
 import sys
 import time
@@ -167,6 +175,15 @@ def host_conflicts(tables, D, margin, g):
     return {k: (v if k == "d" else np.stack(v, -1)) for k, v in out.items()}
 
 
+def held_at(hs, p, length):
+    """Where the vehicles of set p wait before their goals under the schedules hs: 'vehicle@sample' of every wait."""
+    at = []
+    for v, s in enumerate(hs["schedule"][p]):
+        rest = s[:-1][(np.diff(s) == 0) & (s[:-1] < length[p, v] - 1)]
+        at += [f"{v}@{i}" for i in sorted(set(rest.tolist()))]
+    return ",".join(at) if at else "-"
+
+
 def host_delays(count, clear, slack):
     """What a user computed on the host before `Engine.plan_delays`: the start delays that resolve the conflict map count, clear
     [P, npair, 2D+1], with numpy, all (D+1)^V delay vectors of one plan set at a time -> delays [P, V] (-1: none), span, total [P].
@@ -190,6 +207,68 @@ def host_delays(count, clear, slack):
         if ok.any():
             i = np.flatnonzero(ok)[key[ok].argmin()]
             out["delays"][p], out["span"][p], out["total"][p] = d[:, i], span[i], total[i]
+    return out
+
+
+def host_schedule(blocked, length, hold, H, slack, orders):
+    """What a user computed on the host before `Engine.plan_schedule`: the prioritised hold-point schedules over the coordination
+    diagrams blocked [P, npair, T, T] it already holds, with numpy, one plan set and one vehicle of one order at a time (a vehicle's
+    schedule is computed once per distinct prefix of the orders), a step being a few operations on rows of T booleans ->
+    dict(schedule [P, V, H], arrival, waits [P, V], found, order, makespan, total [P]).  Timed against the device in main() and compared
+    with it."""
+    P, npair, T, _ = blocked.shape
+    V = hold.shape[1]
+    pair = {(u, w): q for q, (u, w) in enumerate(zip(*np.triu_indices(V, 1)))}
+    out = dict(schedule=np.full((P, V, H), -1, np.int32), arrival=np.full((P, V), -1, np.int32), waits=np.full((P, V), -1, np.int32),
+               found=np.zeros(P, bool), order=np.full(P, -1, np.int32), makespan=np.full(P, -1, np.int32), total=np.full(P, -1, np.int32))
+    for p in range(P):
+        cache, best = {}, None
+        for oi, pi in enumerate(orders):
+            res = []
+            for k, v in enumerate(pi):
+                key = tuple(pi[: k + 1])
+                if key not in cache:
+                    g = length[p, v] - 1
+                    free = np.zeros((H, T), bool)
+                    free[:, : g + 1] = True
+                    for e, (_, se) in zip(pi[:k], res):
+                        rows = blocked[p, pair[(e, v)]] if e < v else blocked[p, pair[(v, e)]].T  # [e's sample, v's sample]
+                        for d in range(-slack, slack + 1):
+                            free &= ~rows[se[np.clip(np.arange(H) + d, 0, H - 1)]]
+                    hd = hold[p, v] != 0
+                    hd[g] = True
+                    R = np.zeros((H, T), bool)
+                    R[0, 0] = free[0, 0]
+                    for t in range(1, H):
+                        R[t, 1:] = R[t - 1, :-1]
+                        R[t] |= R[t - 1] & hd
+                        R[t] &= free[t]
+                    if not R[H - 1, g]:
+                        cache[key] = None
+                    else:
+                        sv, i = np.empty(H, np.int64), g
+                        sv[H - 1] = g
+                        for t in range(H - 1, 0, -1):
+                            if not (R[t - 1, i] and hd[i]):
+                                i -= 1
+                            sv[t - 1] = i
+                        cache[key] = (int(np.argmax(sv == g)), sv)
+                if cache[key] is None:
+                    res = None
+                    break
+                res.append(cache[key])
+            if res is None:
+                continue
+            arr = np.zeros(V, np.int64)
+            arr[list(pi)] = [r[0] for r in res]
+            cand = (int(arr.max()), int(arr.sum()), oi)
+            if best is None or cand < best[0]:
+                best = (cand, arr, {v: r[1] for v, r in zip(pi, res)})
+        if best is not None:
+            (mk, tot, oi), arr, sch = best
+            out["found"][p], out["order"][p], out["makespan"][p], out["total"][p] = True, oi, mk, tot
+            out["arrival"][p], out["waits"][p] = arr, arr - (length[p] - 1)
+            out["schedule"][p] = np.stack([sch[v] for v in range(V)])
     return out
 
 
@@ -219,9 +298,15 @@ def main():
     ap.add_argument("--resolve", type=int, default=None, metavar="R",
                     help="with --lags D: search the start delays (at most D samples each) that make every strategy's plans conflict-free with "
                          "R samples of slack, and run the closed loop on the delayed plans")
+    ap.add_argument("--holds", type=float, default=None, metavar="V_TOL",
+                    help="with --lags D --resolve R: also search hold-point schedules, in which a vehicle may wait wherever its plan rests "
+                         "(|v| <= V_TOL m/s, e.g. 0.1) and not only at its start, over all priority orders and a horizon of T + 64 steps, and run "
+                         "the closed loop on the scheduled plans")
     a = ap.parse_args()
     if a.resolve is not None and a.lags is None:
         ap.error("--resolve needs --lags")
+    if a.holds is not None and a.resolve is None:
+        ap.error("--holds needs --lags and --resolve")
 
     import torch
 
@@ -286,7 +371,8 @@ def main():
     run_tables = plan["tables"]
     k0, tof, lvl, drop, pof, mof = start_loop(run_tables)
     S = len(k0)
-    cs = dl = None
+    cs = dl = hs = None
+    delayed_free = None  # with --holds: the strategies whose closed loops on the DELAYED plans all finish without contact
     if a.lags is not None:
         t_dev, t_np = [], []
         for _ in range(3):  # (three repeats each: the spread is printed with the median)
@@ -329,6 +415,43 @@ def main():
         run_tables = scenarios.delay_tables(plan["tables"], np.maximum(dl["delays"], 0))  # (no delay where the window holds no answer)
         k0, tof, lvl, drop, pof, mof = start_loop(run_tables)
         print(f"the closed loop below runs on the delayed plans ({run_tables.shape[2]} samples), starts sampled from them")
+    if a.holds is not None:
+        # the closed loop on the delayed plans first, for its contact count alone; the tables below replace them
+        eng.loop_record(K)
+        eng.loop_run(K)
+        contact = eng.loop_audit()["first_contact"] >= 0
+        delayed_free = [int(p) for p in sets if not contact[tof == p].any()]
+        tabs = plan["tables"]
+        T = tabs.shape[2]
+        length = scenarios.plan_lengths(tabs)
+        hold = scenarios.hold_points(tabs, a.holds, length)
+        orders = np.array(list(itertools.permutations(range(V))), np.int32)
+        k0, tof, lvl, drop, pof, mof = start_loop(tabs)  # (the pool searched is the one the loop holds)
+        kw = dict(hold=hold, slack=a.resolve, length=length)
+        eng.loop_plan_schedule(**kw); eng.plan_coordination(tabs, length=length)  # (not timed: the first launches load the kernels)
+        t_dev, t_dg, t_np = [], [], []
+        for _ in range(3):
+            sync(); t0 = time.perf_counter()
+            hs = eng.loop_plan_schedule(**kw)
+            sync(); t_dev.append(time.perf_counter() - t0)
+        for _ in range(3):
+            sync(); t0 = time.perf_counter()
+            dg = eng.plan_coordination(tabs, length=length)
+            sync(); t_dg.append(time.perf_counter() - t0)
+        H = hs["schedule"].shape[2]
+        for _ in range(3):
+            t0 = time.perf_counter()
+            hhs = host_schedule(dg["blocked"], length, hold, H, a.resolve, orders)
+            t_np.append(time.perf_counter() - t0)
+        for n in ("schedule", "arrival", "waits", "found", "order", "makespan", "total"):  # the device against the host: equal integers
+            assert np.array_equal(hs[n][sets], hhs[n][sets]), n
+        print(f"hold-point schedules that resolve the plans: {P} sets x {len(orders)} orders x {V} vehicles x {H} steps, holds where |v| <= {a.holds:g} m/s "
+              f"({int(hold.sum())} of {hold.size} samples), slack {a.resolve}: {fmt(t_dev)} on the device (cfz_loop_plan_schedule: the diagrams and "
+              f"the search, the call with its read-back); the same search with numpy on the host over the diagrams it holds: {fmt(t_np)} "
+              f"(equal integers); the diagrams alone, {P} x {V * (V - 1) // 2} x {T} x {T} bits (cfz_plan_coordination with its read-back): {fmt(t_dg)}")
+        run_tables = scenarios.schedule_tables(tabs, np.where(hs["found"][:, None, None], hs["schedule"], np.minimum(np.arange(H), length[:, :, None] - 1)))
+        k0, tof, lvl, drop, pof, mof = start_loop(run_tables)  # (a set without an answer drives through, as planned)
+        print(f"the closed loop below runs on the scheduled plans ({run_tables.shape[2]} samples), starts sampled from them")
     eng.loop_record(K)
     sync(); t0 = time.perf_counter()
     eng.loop_run(K)
@@ -362,7 +485,8 @@ def main():
     print(f"{'strat':>5} {'combos':>6} {'plans':>5} {'conv':>6} {'min vv':>8} {'min vo':>8} {'contact':>7} {'arr p50':>7} {'arr max':>7} {'arrived':>7}"
           + "".join(f" {'c@%g' % l:>6}" for l in levels or [])
           + f" {'mksp s':>7} {'cost':>9} {'wait s':>7} {'revs':>5} {'near':>5}"
-          + (f" {'depth m':>7} {'crit':>5} {'slack':>5}" if cs else "") + (f" {'delays':>12} {'rclear':>7}" if dl else ""))
+          + (f" {'depth m':>7} {'crit':>5} {'slack':>5}" if cs else "") + (f" {'delays':>12} {'rclear':>7}" if dl else "")
+          + (f" {'order':>8} {'waits':>12} {'held at':>16} {'mksp':>5}" if hs else ""))
     no_contact = []
     for p in range(P):
         row = f"{p:5d} {len(combos[p]):6d} {int((plan['colloc_status'][p] == 0).sum()):3d}/{V}"
@@ -381,7 +505,9 @@ def main():
               + "".join(f" {float((aud['first_contact'][sel & (lvl == l)] >= 0).mean()):6.2f}" for l in levels or [])
               + f" {med(makespan, sel):7.1f} {med(cost, sel):9.1f} {med(wait, sel):7.1f} {med(revs, sel):5.0f} {med(near, sel):5.0f}"
               + (f" {cs['depth'][p]:7.3f} {'%d-%d' % tuple(cs['critical_pair'][p]):>5} {cs['slack'][p]:5d}" if cs else "")
-              + ((f" {','.join(str(x) for x in dl['delays'][p]):>12} {dl['clear'][p]:7.3f}" if dl["found"][p] else f" {'-':>12} {'-':>7}") if dl else ""))
+              + ((f" {','.join(str(x) for x in dl['delays'][p]):>12} {dl['clear'][p]:7.3f}" if dl["found"][p] else f" {'-':>12} {'-':>7}") if dl else "")
+              + ((f" {''.join(str(x) for x in orders[hs['order'][p]]):>8} {','.join(str(x) for x in hs['waits'][p]):>12} {held_at(hs, p, length):>16} {hs['makespan'][p]:5d}"
+                  if hs["found"][p] else f" {'-':>8} {'-':>12} {'-':>16} {'-':>5}") if hs else ""))
         if n_contact == 0:
             no_contact.append(p)
     for l in levels or []:
@@ -421,7 +547,16 @@ def main():
         print(f"resolved by start delays: {len(solved)} of the {len(deep)} strategies whose plans overlap at lag 0 have a solution inside the window of "
               f"{a.lags} samples with slack {a.resolve}, largest span {int(dl['span'][solved].max()) if len(solved) else -1} samples "
               f"(strategies per span: {', '.join(f'{m}: {n}' for m, n in enumerate(spans) if n)}); "
-              f"{sum(int(p) in no_contact for p in solved)} of them finish all their closed loops without contact on the delayed plans")
+              f"{sum(int(p) in (no_contact if delayed_free is None else delayed_free) for p in solved)} of them finish all their closed loops "
+              f"without contact on the delayed plans")
+    if hs:
+        ran = np.flatnonzero(ok)
+        deep = ran[cs["depth"][ran] > 0]
+        by_delay, by_hold = deep[dl["found"][deep]], deep[hs["found"][deep]]
+        print(f"resolved by hold-point schedules: {len(by_hold)} of the {len(deep)} strategies whose plans overlap at lag 0 have a prioritised schedule "
+              f"with waits at rest samples (|v| <= {a.holds:g}) within {hs['schedule'].shape[2]} steps and slack {a.resolve}, against {len(by_delay)} resolved by "
+              f"start delays; all sampled closed loops finish without contact for {sum(int(p) in no_contact for p in by_hold)} of the {len(by_hold)} on the "
+              f"scheduled plans and for {sum(int(p) in delayed_free for p in by_delay)} of the {len(by_delay)} on the delayed plans")
     print(f"wall time (each ended by a device synchronise): planning chain {t_plan:.2f} s, closed loop {t_loop:.2f} s, audit {t_audit * 1e3:.1f} ms, score {t_score * 1e3:.1f} ms")
     eng.close()
 

@@ -676,6 +676,51 @@ int cfz_plan_delays(cfz_handle *h, int P, int V, int T, const double *tables /* 
                     const int32_t *cap, int32_t *delays, int32_t *info, double *rclear);
 int cfz_loop_plan_delays(cfz_handle *h, int D, double margin, int slack, const int32_t *cap, int32_t *delays, int32_t *info, double *rclear);
 
+/* ---- coordination diagrams and hold-point schedules of a plan set ----------------------------------------------------------
+ * A start delay lets a vehicle wait at its first sample only.  A plan offers more places to wait: wherever it is at rest (a parking
+ * manoeuvre rests at every change of direction) the vehicle can stay as it can at the start.  These calls search, per plan set, for
+ * schedules with such waits under which no pair of plans comes within the margin.  Sample-wise only, as the conflict map is.
+ * Inputs: tables[P][V][T][7] as above; length[P][V] in [1, T] (NULL: T): vehicle v's plan is its samples 0 .. length-1, its goal sample
+ * g_v = length-1, what lies beyond is padding and is never read; hold[P][V][T], bytes, non-zero: the vehicle may stay at that sample
+ * for any number of steps.  g_v always counts as holdable; sample 0 only if the caller says so.
+ * Blocked.  For pair q = (u, w), u < w, in the audit's order, i < length_u, j < length_w: B_q[i][j] = 1 when the signed distance of the
+ * body of u at its sample i and the body of w at its sample j is below the margin (the conflict map's predicate, u's body the first
+ * argument everywhere); 0 outside the lengths.  The conflict map's count[p][q][tau] is the sum of B_q along the samples of lag tau.
+ * Schedule.  s_v(t), t in [0, H): s_v(0) = 0; s_v(t+1) - s_v(t) in {0, 1}; a step of 0 only where hold[s_v(t)] is set (or at g_v);
+ * s_v(H-1) = g_v.  Its arrival a_v is the first t with s_v(t) = g_v, its waits the number of steps of 0 before a_v (a_v - g_v).
+ * Conflict-free with slack r >= 0: for every pair, every t in [0, H) and every t' = clamp(t + d, 0, H-1), |d| <= r,
+ * B_q[s_u(t)][s_w(t')] = 0 and B_q[s_u(t')][s_w(t)] = 0: the conflict map of the scheduled tables has count 0 at every lag in [-r, r].
+ * Prioritised schedule of an order pi (a permutation of the vehicles): for k = 0 .. V-1 vehicle pi_k takes a schedule that is
+ * conflict-free with slack r against those of pi_0 .. pi_{k-1}; among those the smallest arrival; among those the pointwise largest one
+ * (every sample as early as possible, waits as late as possible; the pointwise maximum of two feasible schedules is feasible).  The
+ * order is infeasible if some vehicle has no such schedule within H.
+ * Answer per set: over orders[O][V], shared by all sets, the feasible order smallest under (makespan = max a_v, total = sum a_v, index).
+ *   schedule[p][V][H]  s_v(t) of the answer, all -1 if no order is feasible ("nothing feasible within the horizon" is a result)
+ *   arrival[p][V], waits[p][V]  -1 if not found
+ *   info[p][5]    found (1 or 0), order index, makespan, total (-1 if not found), number of feasible orders
+ * V = 1: found, arrival g_0, no waits, nothing is launched.
+ * cfz_plan_coordination returns the diagrams themselves: blocked[P][npair][T][words], words = (T + 31) / 32 of 32 bits, bit (j & 31) of
+ * word j >> 5 of row i is B_q[i][j] (V = 1: nothing is written).  cfz_plan_schedule computes them on the device and searches them there;
+ * cfz_loop_plan_schedule does so on the pool that cfz_loop_init* left on the device (P, V, T its own; only length, hold and orders are
+ * uploaded); the loop's state, clock and record are left untouched.  arrival, waits and info may be NULL.
+ * One workgroup of four wavefronts per set, a wavefront per order; the reachable samples of a vehicle are a row of T bits over the 64
+ * lanes, hence T <= CFZ_SCHEDULE_MAX_T; the rows of all H steps are kept for the walk back, in LDS up to 144 KB per workgroup and in
+ * global memory beyond.  Integers only: the same outputs on every run (conflict_rez_amd/csrc/cfz_coord.inl, cfz_schedule.inl).
+ * Refused before anything is launched: a margin that is negative or not finite, non-positive P, T, H or O, V outside 1..CFZ_MAX_NBR+1,
+ * a length outside [1, T], T > CFZ_SCHEDULE_MAX_T, H > CFZ_SCHEDULE_MAX_H, H < T (no room even for a plan without waits), slack < 0,
+ * an order that is not a permutation of 0..V-1, NULL tables, hold, orders, schedule or blocked, sizes beyond 2^31 elements (the pool,
+ * the diagrams, the schedule) or a workspace beyond 2 GiB.  What needs no handle is checked before the handle is looked at. */
+#define CFZ_SCHEDULE_NINFO 5 /* found, order, makespan, total, feasible orders */
+#define CFZ_SCHEDULE_MAX_T 2048
+#define CFZ_SCHEDULE_MAX_H 32768
+int cfz_plan_coordination(cfz_handle *h, int P, int V, int T, const double *tables /* [P][V][T][7] */, const int32_t *length /* [P][V] or NULL */,
+                          double margin, uint32_t *blocked /* [P][npair][T][words] */);
+int cfz_plan_schedule(cfz_handle *h, int P, int V, int T, const double *tables, const int32_t *length, const uint8_t *hold /* [P][V][T] */,
+                      int H, double margin, int slack, int O, const int32_t *orders /* [O][V] */, int32_t *schedule /* [P][V][H] */,
+                      int32_t *arrival /* [P][V] or NULL */, int32_t *waits /* [P][V] or NULL */, int32_t *info /* [P][5] or NULL */);
+int cfz_loop_plan_schedule(cfz_handle *h, const int32_t *length, const uint8_t *hold, int H, double margin, int slack, int O,
+                           const int32_t *orders, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info);
+
 const char *cfz_last_error(void);
 /* First 16 hex digits of the SHA-256 over the kernel sources this library was built from (__graft_entry__.source_hash; "unknown" for
  * a build made by hand).  bench.py quotes profiler counters from profiles/ only if they were taken on a library with the same hash. */
