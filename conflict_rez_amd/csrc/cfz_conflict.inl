@@ -33,6 +33,8 @@ CFZ_CALL void conflict_pair(int V, int q, int &u, int &w) {
   while (q >= V - 1 - u) { q -= V - 1 - u; ++u; }
   w = u + 1 + q;
 }
+// and back: the pair index of vehicles a < b
+CFZ_CALL int coord_pair_index(int V, int a, int b) { return a * (2 * V - a - 1) / 2 + (b - a - 1); }
 
 // What one lane has seen of one (set, pair, lag).  conflict_merge is a minimum under a total order, a minimum and an integer sum, so the
 // result does not depend on how the steps are dealt out or in which order the lanes are merged.

@@ -17,13 +17,11 @@
 #define CFZ_COORD_INL
 
 #include "cfz_conflict.inl"
+#include "cfz_wave.inl"  // bit_words, bit_test
 
 namespace cfz {
 
-CFZ_CALL int coord_words(int T) { return (T + 31) / 32; }
-
-// the pair index of vehicles a < b in the audit's order
-CFZ_CALL int coord_pair_index(int V, int a, int b) { return a * (2 * V - a - 1) / 2 + (b - a - 1); }
+CFZ_CALL int coord_words(int T) { return bit_words(T); }
 
 // where the rows of (set p, pair q, side) begin in diag, in words
 CFZ_CALL size_t coord_offset(int npair, int T, int p, int q, int side) {
@@ -52,8 +50,6 @@ CFZ_CALL void coord_store(uint32_t *row, int nw, int c, uint64_t ballot) {
   row[2 * c] = (uint32_t)ballot;
   if (2 * c + 1 < nw) row[2 * c + 1] = (uint32_t)(ballot >> 32);
 }
-
-CFZ_CALL bool coord_bit(const uint32_t *row, int c) { return (row[c >> 5] >> (c & 31)) & 1u; }
 
 }  // namespace cfz
 

@@ -22,13 +22,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#ifndef CFZ_CALL
-#if defined(__HIPCC__)
-#define CFZ_CALL __host__ __device__ __forceinline__
-#else
-#define CFZ_CALL static inline
-#endif
-#endif
+#include "cfz_wave.inl"  // CFZ_CALL, bit_words, bit_test
 
 namespace cfz {
 
@@ -36,7 +30,7 @@ constexpr int kDelayNInfo = 3;  // CFZ_DELAY_NINFO: found, span, total
 constexpr int kDelayMaxV = 8;   // CFZ_MAX_NBR + 1
 
 // words of one pair's row of the windowed free mask
-CFZ_CALL int delay_words(int D) { return (2 * D + 1 + 31) / 32; }
+CFZ_CALL int delay_words(int D) { return bit_words(2 * D + 1); }
 
 // lag index j of one pair's row is free
 CFZ_CALL bool delay_free(const int32_t *count, int cs, const double *clear, int j) {
@@ -51,9 +45,6 @@ CFZ_CALL bool delay_window_free(const int32_t *count, int cs, const double *clea
     if (!delay_free(count, cs, clear, t)) return false;
   return true;
 }
-
-// bit j of pair q's row of the mask (rows of nw words)
-CFZ_CALL bool delay_mask_bit(const uint32_t *mask, int nw, int q, int j) { return (mask[q * nw + (j >> 5)] >> (j & 31)) & 1u; }
 
 // Shell m of V digits: start[k] is the number of candidates in the blocks before block k, start[V] the size of the shell.
 struct DelayShell {
@@ -120,7 +111,7 @@ CFZ_CALL bool delay_feasible(int V, int D, const DelayVec &d, const DelayVec &ca
   for (int u = 0; u < V; ++u) {
     const int du = delay_digit(d, u);
     ok &= du <= delay_digit(cap, u);
-    for (int w = u + 1; w < V; ++w, ++q) ok &= delay_mask_bit(mask, nw, q, delay_digit(d, w) - du + D);
+    for (int w = u + 1; w < V; ++w, ++q) { const int j = delay_digit(d, w) - du + D; ok &= (mask[q * nw + (j >> 5)] >> (j & 31)) & 1u; }  // (bit j of row q, one index: measured)
   }
   return ok;
 }

@@ -699,9 +699,31 @@ __global__ void conflict_columns(long n, int T, const double *tables, double *co
   col[0] = tables[i * 7]; col[T] = tables[i * 7 + 1]; col[2 * (long)T] = c; col[3 * (long)T] = s;
 }
 
+// What conflict_kernel and coord_kernel do first: one workgroup of 256 lanes per (set p, pair q = (u, w)), blockIdx.x = p npair + q; U, W
+// the pair's columns in cols[P][V][4][T].  staged (T <= kConflictLdsT, 64 T bytes of dynamic LDS): copied into LDS once and read there,
+// else read from global memory.  body, an always_inline lambda, is invoked once per branch: each instantiation reads U, W where they lie.
+template <class Body>
+__device__ __forceinline__ void pair_columns(const KArgs *__restrict__ ka, int V, int T, int staged, const double *cols, double il0, double il1,
+                                             Body body) {
+  extern __shared__ __attribute__((aligned(16))) double pair_lds[];
+  const int npair = V * (V - 1) / 2, p = blockIdx.x / npair, q = blockIdx.x - p * npair;
+  int u, w;
+  cfz::conflict_pair(V, q, u, w);
+  const double *U = cols + ((size_t)p * V + u) * 4 * T, *W = cols + ((size_t)p * V + w) * 4 * T;
+  double g[4];
+  for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
+  const double il[2] = {il0, il1};
+  if (staged) {
+    for (int i = threadIdx.x; i < 4 * T; i += 256) { pair_lds[i] = U[i]; pair_lds[4 * T + i] = W[i]; }
+    __syncthreads();
+    body(p, q, u, w, pair_lds, pair_lds + 4 * T, g, il);
+  } else {
+    body(p, q, u, w, U, W, g, il);
+  }
+}
+
 // the lags of one wavefront: wave k of the workgroup's four takes lags k, k + 4, ... of the 2 D + 1, its lanes the steps lane, lane + 64, ...
-// of a lag; a __shfl_xor butterfly merges the lanes (conflict_merge: the same result however the steps are dealt out) and lane 0 stores
-// with plain stores.  Forced inline, so that each of its two calls reads U, W in the address space they lie in.
+// of a lag; wave_merge merges the lanes (conflict_merge: the same result however the steps are dealt out), lane 0 stores with plain stores.
 __device__ __forceinline__ void conflict_lags(int T, int D, const double *U, const double *W, const double g[4], const double il[2],
                                               double margin, double margin2, double *clear, int32_t *info) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -713,27 +735,13 @@ __device__ __forceinline__ void conflict_lags(int T, int D, const double *U, con
   }
 }
 
-// One workgroup of 256 lanes per (set, pair); blockIdx.x = p npair + q.  staged (T <= kConflictLdsT, 64 T bytes of dynamic LDS): the
-// workgroup copies the eight columns of its two vehicles into LDS once and every lag reads them there; else the same function reads
-// them from global memory (any T).  clear[P][npair][2D+1] as keys (the host takes the root), info[P][npair][2D+1][3].
+// A workgroup per (set, pair) over pair_columns.  clear[P][npair][2D+1] as keys (the host takes the root), info[P][npair][2D+1][3].
 __global__ __launch_bounds__(256) void conflict_kernel(const KArgs *__restrict__ ka, int V, int T, int D, int staged, const double *cols,
                                                        double il0, double il1, double margin, double margin2, double *clear, int32_t *info) {
-  extern __shared__ __attribute__((aligned(16))) double conflict_lds[];
-  const int npair = V * (V - 1) / 2, p = blockIdx.x / npair, q = blockIdx.x - p * npair;
-  int u, w;
-  cfz::conflict_pair(V, q, u, w);
-  const double *U = cols + ((size_t)p * V + u) * 4 * T, *W = cols + ((size_t)p * V + w) * 4 * T;
-  double g[4];
-  for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
-  const double il[2] = {il0, il1};
   const size_t out = (size_t)blockIdx.x * (2 * D + 1);
-  if (staged) {
-    for (int i = threadIdx.x; i < 4 * T; i += 256) { conflict_lds[i] = U[i]; conflict_lds[4 * T + i] = W[i]; }
-    __syncthreads();
-    conflict_lags(T, D, conflict_lds, conflict_lds + 4 * T, g, il, margin, margin2, clear + out, info + out * cfz::kConflictNInfo);
-  } else {
+  pair_columns(ka, V, T, staged, cols, il0, il1, [&](int, int, int, int, const double *U, const double *W, const double *g, const double *il) __attribute__((always_inline)) {
     conflict_lags(T, D, U, W, g, il, margin, margin2, clear + out, info + out * cfz::kConflictNInfo);
-  }
+  });
 }
 
 // ---- start delays that resolve a conflict map (cfz_delay.inl) ---------------------------------------------------------
@@ -744,15 +752,14 @@ __host__ __device__ constexpr int delay_out_ints(int V) { return ((V + cfz::kDel
 // pointer at column 2: conflict_kernel's info), clear[P][npair][2D+1] or NULL (as conflict_kernel leaves it or as the caller holds it: only
 // finiteness and order are read), cap[P][V] or NULL.  npair delay_words(D) words of dynamic LDS: under (D+1)^V <= 2^31 at most 11,588 B.
 //   staging  a lane per (pair, lag) evaluates the window of slack r, a __ballot packs 32 lanes into a word of the pair's row;
-//   shells   spans m = 0, 1, ... up to the largest cap, the candidates of a shell dealt round-robin over the lanes, merged by a
-//            __shfl_xor butterfly per wavefront and a four-entry exchange in LDS that every lane reads after a barrier: the decision to
-//            stop is workgroup-uniform, no barrier sits in divergent control flow;
+//   shells   spans m = 0, 1, ... up to the largest cap, the candidates of a shell dealt round-robin over the lanes, merged by
+//            wave_merge per wavefront and block_merge over the four (cfz_wave.inl): the decision to stop is workgroup-uniform;
 //   stores   lane 0, plain stores, into one block of outputs: out[P][delay_out_ints(V)], per set the delays, info[3], a pad where V is even
 //            and rclear as a double (an even number of ints per set: every rclear is aligned).
 __global__ __launch_bounds__(256) void delay_kernel(int V, int D, int r, const int32_t *count, int cs, const double *clear, const int32_t *cap,
                                                     int32_t *out) {
   extern __shared__ __attribute__((aligned(16))) uint32_t delay_lds[];
-  __shared__ int xch[2][4][2];  // (total, idx) of the four wavefronts, one buffer per parity of the shell
+  __shared__ int xch[2][4][sizeof(cfz::DelayAcc) / 4];  // block_merge's slots
   const int p = blockIdx.x, npair = V * (V - 1) / 2, L = 2 * D + 1, nw = cfz::delay_words(D), tid = threadIdx.x;
   const int32_t *cnt = count + (size_t)p * npair * L * cs;
   const double *clr = clear ? clear + (size_t)p * npair * L : nullptr;
@@ -777,14 +784,7 @@ __global__ __launch_bounds__(256) void delay_kernel(int V, int D, int r, const i
     cfz::DelayAcc acc;
     cfz::delay_lane(acc, tid, 256, V, D, m, sh, capv, delay_lds, nw);
     cfz::wave_merge<cfz::DelayAcc, cfz::delay_merge>(acc, 64);
-    int(*x)[2] = xch[m & 1];  // (the other buffer may still be read by a wavefront that has not left the previous shell)
-    if ((tid & 63) == 0) { x[tid >> 6][0] = acc.total; x[tid >> 6][1] = acc.idx; }
-    __syncthreads();
-    for (int k = 0; k < 4; ++k) {
-      cfz::DelayAcc o;
-      o.total = x[k][0]; o.idx = x[k][1];
-      cfz::delay_merge(best, o);
-    }
+    cfz::block_merge<cfz::DelayAcc, cfz::delay_merge, 4>(best, acc, xch, m);  // (one barrier per shell)
     if (best.total != INT32_MAX) break;  // (the same for every lane)
   }
   if (tid == 0) {
@@ -797,8 +797,7 @@ __global__ __launch_bounds__(256) void delay_kernel(int V, int D, int r, const i
 constexpr int kCoordRows = 32;  // rows of either side that one workgroup of coord_kernel writes
 
 // the rows blockIdx.y kCoordRows ... of both sides of one pair: a wavefront takes a row, a lane a column, a __ballot packs 64 predicates,
-// lane 0 stores the row's words with plain stores (every word of every row is written: out needs no clearing).  Forced inline, as
-// conflict_lags is.  out: the pair's [2][T][words].
+// lane 0 stores the row's words with plain stores (every word of every row is written: out, the pair's [2][T][words], needs no clearing).
 __device__ __forceinline__ void coord_rows(int T, int lu, int lw, const double *U, const double *W, const double g[4], const double il[2],
                                            double margin, double margin2, uint32_t *out) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = cfz::coord_words(T);
@@ -812,28 +811,14 @@ __device__ __forceinline__ void coord_rows(int T, int lu, int lw, const double *
       }
 }
 
-// One workgroup of 256 lanes per (set, pair, block of kCoordRows rows); blockIdx.x = p npair + q.  cols as conflict_kernel reads them,
-// staged in LDS alike; length[P][V] or NULL (T).  diag[P][npair][2][T][words].
+// A workgroup per (set, pair, block of kCoordRows rows) over pair_columns.  length[P][V] or NULL (T).  diag[P][npair][2][T][words].
 __global__ __launch_bounds__(256) void coord_kernel(const KArgs *__restrict__ ka, int V, int T, int staged, const double *cols,
                                                     const int32_t *length, double il0, double il1, double margin, double margin2,
                                                     uint32_t *diag) {
-  extern __shared__ __attribute__((aligned(16))) double coord_lds[];
-  const int npair = V * (V - 1) / 2, p = blockIdx.x / npair, q = blockIdx.x - p * npair;
-  int u, w;
-  cfz::conflict_pair(V, q, u, w);
-  const double *U = cols + ((size_t)p * V + u) * 4 * T, *W = cols + ((size_t)p * V + w) * 4 * T;
-  const int lu = length ? length[(size_t)p * V + u] : T, lw = length ? length[(size_t)p * V + w] : T;
-  double g[4];
-  for (int i = 0; i < 4; ++i) g[i] = ka->sp.g[i];
-  const double il[2] = {il0, il1};
-  uint32_t *out = diag + cfz::coord_offset(npair, T, p, q, 0);
-  if (staged) {
-    for (int i = threadIdx.x; i < 4 * T; i += 256) { coord_lds[i] = U[i]; coord_lds[4 * T + i] = W[i]; }
-    __syncthreads();
-    coord_rows(T, lu, lw, coord_lds, coord_lds + 4 * T, g, il, margin, margin2, out);
-  } else {
-    coord_rows(T, lu, lw, U, W, g, il, margin, margin2, out);
-  }
+  pair_columns(ka, V, T, staged, cols, il0, il1, [&](int p, int q, int u, int w, const double *U, const double *W, const double *g, const double *il) __attribute__((always_inline)) {
+    const int lu = length ? length[(size_t)p * V + u] : T, lw = length ? length[(size_t)p * V + w] : T;
+    coord_rows(T, lu, lw, U, W, g, il, margin, margin2, diag + cfz::coord_offset(V * (V - 1) / 2, T, p, q, 0));
+  });
 }
 
 // ---- hold-point schedules over the diagrams (cfz_schedule.inl) --------------------------------------------------------
@@ -884,8 +869,8 @@ __device__ __forceinline__ bool schedule_order(int V, int T, int H, int r, uint3
 __host__ __device__ constexpr int schedule_out_ints(int V) { return 2 * V + cfz::kScheduleNInfo; }
 
 // One workgroup of four wavefronts per plan set; blockIdx.x = p.  Pass 0: wavefront k takes orders k, k + 4, ... of orders[O] (packed,
-// schedule_pack) and keeps its best (makespan, total, index); the four are merged by a four-entry LDS exchange that every lane reads
-// after a barrier (schedule_merge, a total order: the decision is workgroup-uniform, the barrier sits in no divergent control flow).
+// schedule_pack) and keeps its best (makespan, total, index); the four are merged by block_merge (cfz_wave.inl; schedule_merge, a total
+// order: the decision is workgroup-uniform).
 // Pass 1: wavefront 0 runs the winning order once more and writes schedule[P][V][H] and small[P][schedule_out_ints(V)] with plain
 // stores.  in_lds: schedule_wave_words(V, T, H) words per wavefront of dynamic LDS; else ws[P][4][that many] in global memory.
 // No floating point.
@@ -894,7 +879,7 @@ __global__ __launch_bounds__(256) void schedule_kernel(int V, int T, int H, int 
                                                        int32_t *schedule, int32_t *small) {
   extern __shared__ __attribute__((aligned(16))) uint32_t schedule_lds[];
   __shared__ uint32_t holdw[4][64];
-  __shared__ int arr[4][2 * cfz::kScheduleMaxV], lens[cfz::kScheduleMaxV], xch[4][4];
+  __shared__ int arr[4][2 * cfz::kScheduleMaxV], lens[cfz::kScheduleMaxV], xch[2][4][sizeof(cfz::ScheduleBest) / 4];  // xch: block_merge's slots
   const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, npair = V * (V - 1) / 2, nw = cfz::coord_words(T);
   if (threadIdx.x < V) lens[threadIdx.x] = length ? length[(size_t)p * V + threadIdx.x] : T;
   __syncthreads();
@@ -910,38 +895,25 @@ __global__ __launch_bounds__(256) void schedule_kernel(int V, int T, int H, int 
     const int first = pass == 0 ? wave : (wave == 0 && found ? best.index : O), stride = pass == 0 ? 4 : O;
     for (int o = first; o < O; o += stride) {
       int mk, tot;
-      bool ok;
-      const uint16_t *sched;
-      if (in_lds) {
-        uint32_t *b = schedule_lds + (size_t)wave * per;
-        sched = (const uint16_t *)(b + (size_t)H * nw);
-        ok = schedule_order(V, T, H, r, orders[o], dg, lens, hd, b, (uint16_t *)(b + (size_t)H * nw), holdw[wave], arr[wave], mk, tot);
+      // one order over the wavefront's rows at b, written out in pass 1; forced inline, so that either call reads b where it lies
+      auto run = [&](uint32_t *b) __attribute__((always_inline)) {
+        uint16_t *sched = (uint16_t *)(b + (size_t)H * nw);
+        const bool ok = schedule_order(V, T, H, r, orders[o], dg, lens, hd, b, sched, holdw[wave], arr[wave], mk, tot);
         if (pass == 1 && ok)
           for (int k = 0; k < V; ++k) {
             int32_t *out = schedule + ((size_t)p * V + cfz::schedule_digit(orders[o], k)) * H;
             for (int t = lane; t < H; t += 64) out[t] = sched[(size_t)k * H + t];
           }
-      } else {
-        sched = (const uint16_t *)(gbase + (size_t)H * nw);
-        ok = schedule_order(V, T, H, r, orders[o], dg, lens, hd, gbase, (uint16_t *)(gbase + (size_t)H * nw), holdw[wave], arr[wave], mk, tot);
-        if (pass == 1 && ok)
-          for (int k = 0; k < V; ++k) {
-            int32_t *out = schedule + ((size_t)p * V + cfz::schedule_digit(orders[o], k)) * H;
-            for (int t = lane; t < H; t += 64) out[t] = sched[(size_t)k * H + t];
-          }
-      }
+        return ok;
+      };
+      const bool ok = in_lds ? run(schedule_lds + (size_t)wave * per) : run(gbase);
       if (pass == 0 && ok) cfz::schedule_take(best, mk, tot, o);
       if (pass == 1 && lane < V) { sm[lane] = arr[0][lane]; sm[V + lane] = arr[0][cfz::kScheduleMaxV + lane]; }
     }
     if (pass == 0) {
-      if (lane == 0) { xch[wave][0] = best.makespan; xch[wave][1] = best.total; xch[wave][2] = best.index; xch[wave][3] = best.feasible; }
-      __syncthreads();
+      const cfz::ScheduleBest mine = best;
       cfz::schedule_clear(best);
-      for (int k = 0; k < 4; ++k) {
-        cfz::ScheduleBest b;
-        b.makespan = xch[k][0]; b.total = xch[k][1]; b.index = xch[k][2]; b.feasible = xch[k][3];
-        cfz::schedule_merge(best, b);
-      }
+      cfz::block_merge<cfz::ScheduleBest, cfz::schedule_merge, 4>(best, mine, xch, 0);
     } else if (wave == 0) {
       if (!found) {
         for (int i = lane; i < V * H; i += 64) schedule[(size_t)p * V * H + i] = -1;
@@ -1675,21 +1647,28 @@ int score_args(double near, const double *val, const int32_t *cnt) {
   return 0;
 }
 
-// the conflict map of P plan sets x V vehicles x T samples (V > 1) that lie on the device (conflict_columns, conflict_kernel), left on the
-// device: dc[P][npair][2D+1] as keys, di[P][npair][2D+1][3], from the arena, which the caller has reset.  Nothing is waited for.
+// The columns of a pool on the device (conflict_columns, from the arena) and what a kernel over pair_columns is launched with.
+struct PairLaunch { double *cols; size_t lds; double il0, il1; };  // lds: bytes of dynamic LDS, 0: not staged
+int pair_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, PairLaunch &pl) {
+  const long n = (long)P * V * T;
+  pl = {nullptr, T <= cfz::kConflictLdsT ? (size_t)T * 64 : 0, cfz::audit_body_il(h->ks.g, 0), cfz::audit_body_il(h->ks.g, 1)};
+  ARENA_ALLOC(h->arena, pl.cols, (size_t)n * 4 * 8);
+  hipLaunchKernelGGL(conflict_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, T, d_tables, pl.cols);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// the conflict map of P plan sets x V vehicles x T samples (V > 1) that lie on the device (conflict_kernel), left on the device:
+// dc[P][npair][2D+1] as keys, di[P][npair][2D+1][3], from the arena, which the caller has reset.  Nothing is waited for.
 int conflict_device(cfz_handle *h, int P, int V, int T, const double *d_tables, int D, double margin, double *&dc, int32_t *&di) {
   static_assert(cfz::kConflictNInfo == CFZ_CONFLICT_NINFO, "cfz_conflict.inl and confrez_hip.h disagree");
   const int npair = V * (V - 1) / 2;
-  const double *g = h->ks.g;
-  const long n = (long)P * V * T;
   const size_t no = (size_t)P * npair * (2 * (size_t)D + 1);
-  double *dcol = nullptr;
-  ARENA_ALLOC(h->arena, dcol, (size_t)n * 4 * 8); ARENA_ALLOC(h->arena, dc, no * 8); ARENA_ALLOC(h->arena, di, no * CFZ_CONFLICT_NINFO * 4);
-  hipLaunchKernelGGL(conflict_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, T, d_tables, dcol);
-  HIP_OK(hipGetLastError());
-  const int staged = T <= cfz::kConflictLdsT;
-  hipLaunchKernelGGL(conflict_kernel, dim3((unsigned)(P * npair)), dim3(256), staged ? (size_t)T * 64 : 0, h->stream, h->kargs, V, T, D, staged,
-                     dcol, cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1), margin, margin * margin, dc, di);
+  PairLaunch pl;
+  if (pair_launch(h, P, V, T, d_tables, pl)) return -1;
+  ARENA_ALLOC(h->arena, dc, no * 8); ARENA_ALLOC(h->arena, di, no * CFZ_CONFLICT_NINFO * 4);
+  hipLaunchKernelGGL(conflict_kernel, dim3((unsigned)(P * npair)), dim3(256), pl.lds, h->stream, h->kargs, V, T, D, pl.lds != 0, pl.cols, pl.il0,
+                     pl.il1, margin, margin * margin, dc, di);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1711,28 +1690,27 @@ int conflict_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, 
   return 0;
 }
 
-// what both conflict entry points refuse before they look at the handle
-int conflict_args(int D, double margin) {
-  if (D < 0) return fail("D must not be negative");
-  if (!(margin >= 0.0) || !std::isfinite(margin)) return fail("margin must be finite and not negative");
-  return 0;
+// What the plan-set entry points refuse of a margin and of a pool tables[P][V][T][7]; separate: they refuse other things in between.
+int margin_arg(double margin) { return !(margin >= 0.0) || !std::isfinite(margin) ? fail("margin must be finite and not negative") : 0; }
+int pool_dims(int P, int V, int T) {
+  return P < 1 || T < 1 ? fail("P, T must be positive") : V < 1 || V > CFZ_MAX_NBR + 1 ? fail("V must be in 1..CFZ_MAX_NBR+1") : 0;
 }
+int pool_tables(const double *tables) { return tables ? 0 : fail("null tables"); }
+int pool_fits(int P, int V, int T) { return (size_t)P * V * T * 7 > ((size_t)1 << 31) ? fail("pool of plan sets too large") : 0; }
 
-// the sizes of a conflict map: every index of the kernels fits an int
+// what both conflict entry points refuse before they look at the handle
+int conflict_args(int D, double margin) { return D < 0 ? fail("D must not be negative") : margin_arg(margin); }
+
+// the sizes of a conflict map
 int conflict_sizes(int P, int V, int T, int D) {
-  if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
-  if ((size_t)P * (V * (V - 1) / 2) * (2 * (size_t)D + 1) * CFZ_CONFLICT_NINFO > ((size_t)1 << 31)) return fail("conflict map too large");
-  return 0;
+  if (pool_fits(P, V, T)) return -1;
+  return (size_t)P * (V * (V - 1) / 2) * (2 * (size_t)D + 1) * CFZ_CONFLICT_NINFO > ((size_t)1 << 31) ? fail("conflict map too large") : 0;
 }
 
 // a caller's pool of plan sets tables[P][V][T][7] with the map asked of it (cfz_plan_conflicts, cfz_plan_delays): what both refuse first,
 // in this order, and its upload once the call has got as far as the device
 int plan_pool_args(int P, int V, int T, const double *tables, int D, double margin) {
-  if (conflict_args(D, margin)) return -1;
-  if (P < 1 || T < 1) return fail("P, T must be positive");
-  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
-  if (!tables) return fail("null tables");
-  return conflict_sizes(P, V, T, D);
+  return conflict_args(D, margin) || pool_dims(P, V, T) || pool_tables(tables) || conflict_sizes(P, V, T, D) ? -1 : 0;
 }
 int plan_pool_upload(cfz_handle *h, int P, int V, int T, const double *tables, double *&d_tables) {
   HIP_OK(hipSetDevice(h->device));
@@ -1764,31 +1742,33 @@ void delay_single(int P, bool with_clear, int32_t *delays, int32_t *info, double
   }
 }
 
+// A kernel's block of small outputs rows[P][no] ints read back on the handle's stream, and slices of every row copied into the caller's
+// arrays: ints [at, at + n) of row p to dst + p n ints; a dst that is NULL is not wanted.  Ends synchronised.
+struct RowSlice { void *dst; int at, n; };
+int read_rows(cfz_handle *h, const int32_t *d_rows, int P, int no, std::initializer_list<RowSlice> slices) {
+  std::vector<int32_t> rows((size_t)P * no);
+  HIP_OK(hipMemcpyAsync(rows.data(), d_rows, rows.size() * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_OK(hipStreamSynchronize(h->stream));
+  for (const RowSlice &s : slices)
+    for (int p = 0; s.dst && p < P; ++p) memcpy((int32_t *)s.dst + (size_t)p * s.n, rows.data() + (size_t)p * no + s.at, (size_t)s.n * 4);
+  return 0;
+}
+
 // delay_kernel over a map on the device (V > 1): d_count with entries cs ints apart, d_clear or NULL (keys: the caller's rclear is
 // converted to a signed distance as conflict_launch converts the map), cap the caller's host array or NULL; the outputs are the caller's
 // host arrays (info, rclear may be NULL).  The arena is reset by the caller.  Ends synchronised.
 int delay_launch(cfz_handle *h, int P, int V, int D, const int32_t *d_count, int cs, const double *d_clear, bool keys, int slack,
                  const int32_t *cap, int32_t *delays, int32_t *info, double *rclear) {
-  const int npair = V * (V - 1) / 2;
-  const int no = delay_out_ints(V);
+  const int npair = V * (V - 1) / 2, no = delay_out_ints(V);
   int32_t *dcap = nullptr, *dout = nullptr;
   ARENA_ALLOC(h->arena, dout, (size_t)P * no * 4);
   if (cap && arena_upload(h, dcap, cap, (size_t)P * V)) return -1;
   hipLaunchKernelGGL(delay_kernel, dim3((unsigned)P), dim3(256), (size_t)npair * cfz::delay_words(D) * 4, h->stream, V, D, slack, d_count, cs,
                      d_clear, dcap, dout);
   HIP_OK(hipGetLastError());
-  std::vector<int32_t> out((size_t)P * no);
-  HIP_OK(hipMemcpyAsync(out.data(), dout, out.size() * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));
-  for (int p = 0; p < P; ++p) {
-    const int32_t *o = out.data() + (size_t)p * no;
-    memcpy(delays + (size_t)p * V, o, (size_t)V * 4);
-    if (info) memcpy(info + (size_t)p * CFZ_DELAY_NINFO, o + V, CFZ_DELAY_NINFO * 4);
-    if (d_clear && rclear) {
-      memcpy(rclear + p, o + no - 2, 8);
-      if (keys) rclear[p] = cfz::audit_key_distance(rclear[p]);
-    }
-  }
+  if (!d_clear) rclear = nullptr;  // (written only where a map of clearances is given)
+  if (read_rows(h, dout, P, no, {{delays, 0, V}, {info, V, CFZ_DELAY_NINFO}, {rclear, no - 2, 2}})) return -1;  // (rclear: a double as two ints)
+  for (int p = 0; rclear && keys && p < P; ++p) rclear[p] = cfz::audit_key_distance(rclear[p]);
   return 0;
 }
 
@@ -1801,15 +1781,11 @@ int plan_delays_launch(cfz_handle *h, int P, int V, int T, const double *d_table
   return delay_launch(h, P, V, D, di + 2, CFZ_CONFLICT_NINFO, dc, true, slack, cap, delays, info, rclear);
 }
 
-// what the coordination and the schedule entry points refuse of a pool's sizes, its margin and its lengths length[P][V] (NULL: T) before
-// they look at the handle
-int coord_args(int P, int V, int T, double margin, const int32_t *length) {
+// what the coordination and the schedule entry points refuse, after the margin, of a pool's sizes and its lengths length[P][V] (NULL: T)
+int coord_args(int P, int V, int T, const int32_t *length) {
   static_assert(cfz::kScheduleMaxT == CFZ_SCHEDULE_MAX_T && cfz::kScheduleMaxH == CFZ_SCHEDULE_MAX_H && cfz::kScheduleNInfo == CFZ_SCHEDULE_NINFO &&
                     cfz::kScheduleMaxV == CFZ_MAX_NBR + 1, "cfz_schedule.inl and confrez_hip.h disagree");
-  if (!(margin >= 0.0) || !std::isfinite(margin)) return fail("margin must be finite and not negative");
-  if (P < 1 || T < 1) return fail("P, T must be positive");
-  if (V < 1 || V > CFZ_MAX_NBR + 1) return fail("V must be in 1..CFZ_MAX_NBR+1");
-  if ((size_t)P * V * T * 7 > ((size_t)1 << 31)) return fail("pool of plan sets too large");
+  if (pool_dims(P, V, T) || pool_fits(P, V, T)) return -1;
   if ((size_t)P * (V * (V - 1) / 2) * 2 * T * cfz::coord_words(T) > ((size_t)1 << 31)) return fail("coordination diagram too large");
   if (length)
     for (size_t i = 0; i < (size_t)P * V; ++i)
@@ -1834,24 +1810,19 @@ int schedule_args(int P, int V, int T, const uint8_t *hold, int H, int slack, in
   return 0;
 }
 
-// the coordination diagrams of P plan sets x V vehicles x T samples (V > 1) that lie on the device (conflict_columns, coord_kernel), left
-// on the device: diag[P][npair][2][T][words], from the arena, which the caller has reset.  length: the caller's host array or NULL;
-// dlen its copy on the device.  Nothing is waited for.
+// the coordination diagrams of P plan sets x V vehicles x T samples (V > 1) that lie on the device (coord_kernel), left on the device:
+// diag[P][npair][2][T][words], from the arena, which the caller has reset.  length: the caller's host array or NULL; dlen its copy on
+// the device.  Nothing is waited for.
 int coord_device(cfz_handle *h, int P, int V, int T, const double *d_tables, const int32_t *length, double margin, uint32_t *&diag,
                  int32_t *&dlen) {
   const int npair = V * (V - 1) / 2;
-  const double *g = h->ks.g;
-  const long n = (long)P * V * T;
-  double *dcol = nullptr;
   dlen = nullptr;
-  ARENA_ALLOC(h->arena, dcol, (size_t)n * 4 * 8);
+  PairLaunch pl;
+  if (pair_launch(h, P, V, T, d_tables, pl)) return -1;
   ARENA_ALLOC(h->arena, diag, (size_t)P * npair * 2 * T * cfz::coord_words(T) * 4);
   if (length && arena_upload(h, dlen, length, (size_t)P * V)) return -1;
-  hipLaunchKernelGGL(conflict_columns, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, T, d_tables, dcol);
-  HIP_OK(hipGetLastError());
-  const int staged = T <= cfz::kConflictLdsT;
-  hipLaunchKernelGGL(coord_kernel, dim3((unsigned)(P * npair), (unsigned)((T + kCoordRows - 1) / kCoordRows)), dim3(256), staged ? (size_t)T * 64 : 0,
-                     h->stream, h->kargs, V, T, staged, dcol, dlen, cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1), margin, margin * margin, diag);
+  hipLaunchKernelGGL(coord_kernel, dim3((unsigned)(P * npair), (unsigned)((T + kCoordRows - 1) / kCoordRows)), dim3(256), pl.lds, h->stream,
+                     h->kargs, V, T, pl.lds != 0, pl.cols, dlen, pl.il0, pl.il1, margin, margin * margin, diag);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1901,17 +1872,8 @@ int schedule_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, 
   hipLaunchKernelGGL(schedule_kernel, dim3((unsigned)P), dim3(256), in_lds ? lds : 0, h->stream, V, T, H, slack, O, dord, diag, dlen, dhold, in_lds,
                      ws, dsched, dsmall);
   HIP_OK(hipGetLastError());
-  std::vector<int32_t> out((size_t)P * no);
   HIP_OK(hipMemcpyAsync(schedule, dsched, (size_t)P * V * H * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipMemcpyAsync(out.data(), dsmall, out.size() * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_OK(hipStreamSynchronize(h->stream));  // (packed and out live until here)
-  for (int p = 0; p < P; ++p) {
-    const int32_t *o = out.data() + (size_t)p * no;
-    if (arrival) memcpy(arrival + (size_t)p * V, o, (size_t)V * 4);
-    if (waits) memcpy(waits + (size_t)p * V, o + V, (size_t)V * 4);
-    if (info) memcpy(info + (size_t)p * CFZ_SCHEDULE_NINFO, o + 2 * V, CFZ_SCHEDULE_NINFO * 4);
-  }
-  return 0;
+  return read_rows(h, dsmall, P, no, {{arrival, 0, V}, {waits, V, V}, {info, 2 * V, CFZ_SCHEDULE_NINFO}});  // (packed lives until it has synchronised)
 }
 
 // What the pool kernels take, composed from the two per-scenario settings: one KArgs block per (problem, map) pair that some scenario
@@ -2181,8 +2143,7 @@ int cfz_loop_plan_delays(cfz_handle *h, int D, double margin, int slack, const i
 }
 
 int cfz_plan_coordination(cfz_handle *h, int P, int V, int T, const double *tables, const int32_t *length, double margin, uint32_t *blocked) {
-  if (coord_args(P, V, T, margin, length)) return -1;
-  if (!tables) return fail("null tables");
+  if (margin_arg(margin) || coord_args(P, V, T, length) || pool_tables(tables)) return -1;
   if (!blocked) return fail("null blocked");
   if (!h) return fail("null handle");
   if (V == 1) return 0;  // no pairs: nothing to launch, nothing to write
@@ -2193,8 +2154,7 @@ int cfz_plan_coordination(cfz_handle *h, int P, int V, int T, const double *tabl
 
 int cfz_plan_schedule(cfz_handle *h, int P, int V, int T, const double *tables, const int32_t *length, const uint8_t *hold, int H, double margin,
                       int slack, int O, const int32_t *orders, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info) {
-  if (coord_args(P, V, T, margin, length)) return -1;
-  if (!tables) return fail("null tables");
+  if (margin_arg(margin) || coord_args(P, V, T, length) || pool_tables(tables)) return -1;
   if (schedule_args(P, V, T, hold, H, slack, O, orders, schedule)) return -1;
   if (!h) return fail("null handle");
   if (V == 1) { schedule_single(P, T, length, H, O, schedule, arrival, waits, info); return 0; }  // no pairs: nothing to launch
@@ -2205,11 +2165,11 @@ int cfz_plan_schedule(cfz_handle *h, int P, int V, int T, const double *tables, 
 
 int cfz_loop_plan_schedule(cfz_handle *h, const int32_t *length, const uint8_t *hold, int H, double margin, int slack, int O,
                            const int32_t *orders, int32_t *schedule, int32_t *arrival, int32_t *waits, int32_t *info) {
-  if (!(margin >= 0.0) || !std::isfinite(margin)) return fail("margin must be finite and not negative");
+  if (margin_arg(margin)) return -1;
   if (slack < 0) return fail("slack must not be negative");
   if (loop_ready(h)) return -1;  // (the lengths, the mask, the orders and the outputs have the pool's sizes: checked below)
   const int P = h->lp.P, V = h->ks.n_nbr + 1, T = h->lp.T;
-  if (coord_args(P, V, T, margin, length)) return -1;
+  if (coord_args(P, V, T, length)) return -1;
   if (schedule_args(P, V, T, hold, H, slack, O, orders, schedule)) return -1;
   if (V == 1) { schedule_single(P, T, length, H, O, schedule, arrival, waits, info); return 0; }
   if (arena_reset(h->arena)) return -1;

@@ -98,11 +98,11 @@ CFZ_CALL uint32_t schedule_step(uint32_t r, uint32_t prev, uint32_t hold, uint32
 // The walk back over the rows hist[H][nw] of one vehicle, hold[nw] its hold words, g its goal sample: s[0..H-1] and the arrival, or -1
 // (s unwritten) if bit g of the last row is not set.  The same for every lane: every read is of an address all lanes share.
 CFZ_CALL int schedule_walk(const uint32_t *hist, int nw, const uint32_t *hold, int g, int H, uint16_t *s, bool write) {
-  if (!coord_bit(hist + (size_t)(H - 1) * nw, g)) return -1;
+  if (!bit_test(hist + (size_t)(H - 1) * nw, g)) return -1;
   int i = g, arrival = 0;
   if (write) s[H - 1] = (uint16_t)g;
   for (int t = H - 1; t > 0; --t) {
-    const bool stay = coord_bit(hist + (size_t)(t - 1) * nw, i) && coord_bit(hold, i);
+    const bool stay = bit_test(hist + (size_t)(t - 1) * nw, i) && bit_test(hold, i);
     if (!stay) {
       if (i == g) arrival = t;
       if (i > 0) --i;

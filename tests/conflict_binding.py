@@ -28,7 +28,7 @@ INTS = ("when", "first", "count")
 
 def build(force=False):
     csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_conflict_emu.cpp"), os.path.join(csrc, "cfz_conflict.inl"), os.path.join(csrc, "cfz_audit.inl"), os.path.join(csrc, "cfz_wave.inl")]
+    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_conflict_emu.cpp"), os.path.join(csrc, "cfz_conflict.inl"), os.path.join(csrc, "cfz_audit.inl"), os.path.join(csrc, "cfz_wave.inl"), os.path.join(ROOT, "tests", "emu", "emu_columns.h")]
     return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 

@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+from conflict_binding import pairs
 from emu_build import build_shared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,10 +43,6 @@ def vehicles(npair):
     V = int(round((1 + (1 + 8 * npair) ** 0.5) / 2))
     assert V * (V - 1) // 2 == npair
     return V
-
-
-def pairs(V):
-    return [(u, w) for u in range(V) for w in range(u + 1, V)]
 
 
 def _caps(cap, P, V, D):

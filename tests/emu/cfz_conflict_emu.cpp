@@ -4,6 +4,7 @@
 
 #include "../../conflict_rez_amd/csrc/cfz_conflict.inl"
 #include "../../conflict_rez_amd/csrc/cfz_wave.inl"
+#include "emu_columns.h"
 
 extern "C" {
 
@@ -15,13 +16,7 @@ int cfz_emu_plan_conflicts(int P, int V, int T, const double *tables, const doub
   if (P < 1 || V < 1 || V > cfz::kAuditMaxV || T < 1 || D < 0 || !(margin >= 0.0) || nl < 1 || nl > 64 || (nl & (nl - 1))) return -1;
   const int npair = V * (V - 1) / 2;
   const double il[2] = {cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1)};
-  std::vector<double> cols((size_t)P * V * 4 * T);  // as conflict_columns
-  for (size_t v = 0; v < (size_t)P * V; ++v)
-    for (int t = 0; t < T; ++t) {
-      const double *z = tables + (v * T + t) * 7;
-      double *col = cols.data() + v * 4 * T + t;
-      col[0] = z[0]; col[T] = z[1]; col[2 * (size_t)T] = cos(z[2]); col[3 * (size_t)T] = sin(z[2]);
-    }
+  const std::vector<double> cols = emu_columns((size_t)P * V, T, tables);
   for (int p = 0; p < P; ++p)
     for (int q = 0; q < npair; ++q) {
       int u, w;

@@ -1,5 +1,5 @@
-// Test-only CPU build of the delay search over a conflict map: conflict_rez_amd/csrc/cfz_delay.inl compiled with g++, the lanes that
-// delay_kernel deals a shell's candidates to executed as a loop and merged by the butterfly of cfz_wave.inl.  Never shipped, never loaded by the package.
+// Test-only CPU build of the delay search over a conflict map (conflict_rez_amd/csrc/cfz_delay.inl with g++): delay_kernel's lanes as a loop,
+// merged as there by wave_merge_host per min(nl, 64) lanes, then block_merge_host.  Never shipped, never loaded by the package.
 #include <algorithm>
 #include <vector>
 
@@ -16,7 +16,7 @@ int cfz_emu_delay_search(int P, int V, int D, const int32_t *count, const double
   double box = 1.0;
   for (int v = 0; v < V; ++v) box *= D + 1.0;
   if (box > 2147483648.0) return -1;
-  const int npair = V * (V - 1) / 2, L = 2 * D + 1, nw = cfz::delay_words(D);
+  const int npair = V * (V - 1) / 2, L = 2 * D + 1, nw = cfz::delay_words(D), width = std::min(nl, 64);
   std::vector<uint32_t> mask((size_t)(npair ? npair : 1) * nw);
   std::vector<cfz::DelayAcc> acc(nl);
   for (int p = 0; p < P; ++p) {
@@ -39,8 +39,8 @@ int cfz_emu_delay_search(int P, int V, int D, const int32_t *count, const double
       cfz::DelayShell sh;
       cfz::delay_shell(V, m, sh);
       for (int l = 0; l < nl; ++l) cfz::delay_lane(acc[l], l, nl, V, D, m, sh, capv, mask.data(), nw);
-      cfz::wave_merge_host<cfz::DelayAcc, cfz::delay_merge>(acc.data(), nl, nl);
-      best = acc[0];
+      cfz::wave_merge_host<cfz::DelayAcc, cfz::delay_merge>(acc.data(), nl, width);
+      cfz::block_merge_host<cfz::DelayAcc, cfz::delay_merge>(best, acc.data(), nl / width, width);
       if (best.total != INT32_MAX) break;
     }
     cfz::delay_store(best, V, D, m, clr, delays + (size_t)p * V, info + (size_t)p * cfz::kDelayNInfo, rclear ? rclear + p : nullptr);

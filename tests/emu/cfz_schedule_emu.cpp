@@ -1,9 +1,10 @@
 // Test-only CPU build of the coordination diagrams and the hold-point schedules: conflict_rez_amd/csrc/cfz_coord.inl and cfz_schedule.inl
 // compiled with g++ (-ffp-contract=off), the lanes of coord_kernel and schedule_kernel executed as loops, the __shfl_up carry as an index,
-// the wavefronts that take the orders as a loop merged as the kernel's LDS exchange does.  Never shipped, never loaded by the package.
+// the wavefronts that take the orders as a loop merged by the host form of block_merge (cfz_wave.inl).  Never shipped, never loaded by the package.
 #include <vector>
 
 #include "../../conflict_rez_amd/csrc/cfz_schedule.inl"
+#include "emu_columns.h"
 
 namespace {
 
@@ -50,13 +51,7 @@ int cfz_emu_plan_coordination(int P, int V, int T, const double *tables, const i
   if (P < 1 || V < 1 || V > cfz::kScheduleMaxV || T < 1 || !(margin >= 0.0) || !diag) return -1;
   const int npair = V * (V - 1) / 2, nw = cfz::coord_words(T);
   const double il[2] = {cfz::audit_body_il(g, 0), cfz::audit_body_il(g, 1)};
-  std::vector<double> cols((size_t)P * V * 4 * T);  // as conflict_columns
-  for (size_t v = 0; v < (size_t)P * V; ++v)
-    for (int t = 0; t < T; ++t) {
-      const double *z = tables + (v * T + t) * 7;
-      double *col = cols.data() + v * 4 * T + t;
-      col[0] = z[0]; col[T] = z[1]; col[2 * (size_t)T] = cos(z[2]); col[3 * (size_t)T] = sin(z[2]);
-    }
+  const std::vector<double> cols = emu_columns((size_t)P * V, T, tables);
   for (int p = 0; p < P; ++p)
     for (int q = 0; q < npair; ++q) {
       int u, w;
@@ -106,7 +101,7 @@ int cfz_emu_plan_schedule(int P, int V, int T, const uint32_t *diag, const int32
           cfz::schedule_take(best[w], mk, tot, o);
     }
     cfz::schedule_clear(all);
-    for (int w = 0; w < nwave; ++w) cfz::schedule_merge(all, best[w]);
+    cfz::block_merge_host<cfz::ScheduleBest, cfz::schedule_merge>(all, best, nwave);
     int32_t *s = schedule + (size_t)p * V * H;
     if (all.makespan != INT32_MAX) {
       const uint32_t order = cfz::schedule_pack(V, orders + (size_t)all.index * V);

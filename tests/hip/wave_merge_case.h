@@ -1,6 +1,7 @@
-// The accumulators and merges of tests/test_wave_merge_gpu.py, shared by the device program (tests/hip/wave_merge.hip) and the g++ build
-// of the host forms (tests/emu/wave_merge_emu.cpp).  Nothing of the product but cfz_wave.inl is involved.
+// The accumulators and merges of tests/test_wave_merge_gpu.py and tests/test_block_merge_gpu.py, shared by the device programs
+// (tests/hip/wave_merge.hip, block_merge.hip) and the g++ build of the host forms (tests/hip/wave_merge_host.cpp).  Nothing of the product but cfz_wave.inl is involved.
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -40,4 +41,18 @@ WAVE_CASE_CALL void span_concat(WaveSpan &p, const WaveSpan &q) {
   p.last = q.last;
   p.count += q.count;
   p.sum = p.sum + q.sum;
+}
+
+// 8 bytes: an integer sum and the number of accumulators that went into it, so that a slot lost or read twice shows
+struct WaveSum {
+  int sum, n;
+};
+
+// the identities of case_min and sum_add: what block_merge's caller clears its total to
+WAVE_CASE_CALL void case_clear(WaveCase &p) { p.x = INFINITY; p.a = p.b[0] = p.b[1] = p.b[2] = INT32_MAX; }
+WAVE_CASE_CALL void sum_clear(WaveSum &p) { p.sum = p.n = 0; }
+
+WAVE_CASE_CALL void sum_add(WaveSum &p, const WaveSum &q) {
+  p.sum += q.sum;
+  p.n += q.n;
 }

@@ -13,6 +13,7 @@ import numpy as np
 
 import audit_binding as ab
 import conflict_binding as cb
+from conflict_binding import pairs
 from emu_build import build_shared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +26,7 @@ OUT = ("schedule", "arrival", "waits", "found", "order", "makespan", "total", "f
 
 def build(force=False):
     csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_schedule_emu.cpp")] + [os.path.join(csrc, f) for f in ("cfz_schedule.inl", "cfz_coord.inl", "cfz_conflict.inl", "cfz_audit.inl")]
+    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_schedule_emu.cpp")] + [os.path.join(csrc, f) for f in ("cfz_schedule.inl", "cfz_coord.inl", "cfz_conflict.inl", "cfz_audit.inl", "cfz_wave.inl")] + [os.path.join(ROOT, "tests", "emu", "emu_columns.h")]
     return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
 
 
@@ -42,10 +43,6 @@ def lib():
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def pairs(V):
-    return [(u, w) for u in range(V) for w in range(u + 1, V)]
 
 
 def all_orders(V):

@@ -12,11 +12,10 @@ import numpy as np
 import pytest
 
 from emu_build import build_shared
+from wave_case import CASE, ROOT, key as _key, same as _same
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CASE = np.dtype([("a", "<i4"), ("x", "<f8"), ("b", "<i4", (3,))], align=True)
 SPAN = np.dtype([("first", "<i4"), ("last", "<i4"), ("count", "<i4"), ("sum", "<f8")], align=True)
-assert CASE.itemsize == 32 and SPAN.itemsize == 24  # as the static_asserts of wave_merge_case.h
+assert SPAN.itemsize == 24  # as the static_asserts of wave_merge_case.h
 LANES = 64
 OFFS = (1, 2, 4, 8, 16, 32)
 WIDTHS = (1, 2, 4, 8, 16, 32, 64)
@@ -37,12 +36,6 @@ def _inputs():
     return c, s
 
 
-def _same(a, b):
-    """Every field equal, doubles by their bits."""
-    return all(np.array_equal(np.ascontiguousarray(a[n]).view(np.int64 if a.dtype[n] == np.float64 else np.int32),
-                              np.ascontiguousarray(b[n]).view(np.int64 if a.dtype[n] == np.float64 else np.int32)) for n in a.dtype.names)
-
-
 @pytest.fixture(scope="module")
 def host():
     """The header's host forms: (acc, width) -> the lanes after the butterfly, a new array."""
@@ -55,10 +48,6 @@ def host():
         return out
 
     return (lambda acc, width: run(lib.wave_host_min, acc, width)), (lambda acc, width: run(lib.wave_host_concat, acc, width))
-
-
-def _key(c):
-    return (float(c["x"]), int(c["a"]), *(int(v) for v in c["b"]))
 
 
 def test_host_forms_against_plain_folds(host):

@@ -5,7 +5,9 @@ tests/disturbance_binding.SIGMA); a lossy exchange (p_drop 0.3), Jacobi and sequ
 tests/problem_pool_binding.py under noise, run of 4 and stepped 3 times; and runs of 4 through the remaining persistent kernels
 (sequential + noise, sequential + pool, pool + loss, sequential + pool + loss), so that all ten and both stepwise solve kernels are
 compared; and, where both builds have cfz_loop_set_maps, the four maps of tests/map_pool_binding.py under noise, run of 4 and stepped 3
-times, and together with the problems, the sequential order and loss, each with its audit.  Every loop is compared at its end point and
+times, and together with the problems, the sequential order and loss, each with its audit; and the plan-set entry points
+(plan_conflicts, plan_delays, delay_search, plan_coordination, plan_schedule on the cases of tests/conflict_binding.py, delay_binding.py
+and schedule_binding.py; loop_plan_conflicts / _delays / _schedule on the packaged pool).  Every loop is compared at its end point and
 over its record; the exit status is 1 when anything differs.  A key that only the second build has is listed, not compared.
 usage: python tools/gpu_lib_compare.py <libA.so> <libB.so> [scenarios]     (each library runs in a process of its own)"""
 import os, subprocess, sys, tempfile
@@ -77,6 +79,31 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
         loop("mapsstep", setting(noise=True, maps=True), three_steps)
         loop("seqpoolmapscomm", setting(seq=True, comm=True, pool=True, maps=True), lambda: e.loop_run(4))
         res.update({"seqpoolmapscomm_audit_" + k: v for k, v in e.loop_audit().items()})
+    # the plan-set entry points: the cases of the binding modules of tests/, and the packaged pool from the loop's copy on the device
+    import conflict_binding as cb, delay_binding as db, schedule_binding as sb
+
+    def keep(tag, d):
+        res.update({f"{tag}_{k}": np.asarray(v) for k, v in d.items()})
+
+    for V_, T_, D_ in cb.SHAPES:
+        for P_ in cb.PS:
+            tab = cb.synthetic(P_, V_, T_)
+            keep(f"conf_{P_}_{V_}_{T_}_{D_}", e.plan_conflicts(tab, D_))
+            keep(f"pdel_{P_}_{V_}_{T_}_{D_}", e.plan_delays(tab, D_, slack=1))
+    for name in db.CASES:
+        count, clear, slack, cap, _ = db.case(name)
+        keep("dsearch_" + name, e.delay_search(dict(count=count, clear=clear), slack=slack, cap=cap))
+    for name in sb.CASES:
+        tables, hold, length, H, slack, orders, *_ = sb.case(name)
+        keep("coord_" + name, e.plan_coordination(tables, length=length))
+        keep("sched_" + name, e.plan_schedule(tables, hold, horizon=H, slack=slack, orders=orders, length=length))
+    pool = cb.packaged_pool()
+    length = scenarios.plan_lengths(pool)
+    k0p, noisep = scenarios.sample_scenarios(6, pool[1], seed=5, spec=spec)
+    e.loop_init(pool, k0p, noisep, table_of=(np.arange(6) % 3).astype(np.int32))
+    keep("loopconf", e.loop_plan_conflicts(40))
+    keep("loopdel", e.loop_plan_delays(40, slack=1))
+    keep("loopsched", e.loop_plan_schedule(hold=scenarios.hold_points(pool, 0.1, length), slack=1, length=length))
     np.savez(out, **res)
     sys.exit(0)
 S = int(sys.argv[3]) if len(sys.argv) > 3 else 256
@@ -103,5 +130,6 @@ only_b = sorted(k for k in b if k not in a)
 if only_b:
     print(f"only in the second build, not compared: {len(only_b)} keys ({', '.join(sorted({k.split('_')[0] for k in only_b}))})")
 print("closed loop iterations", int(a["loop_its"]), int(b["loop_its"]))
+print(f"{sum(k in b for k in a)} arrays compared")
 print("ALL EQUAL" if not differ else f"{differ} DIFFERENCES")
 sys.exit(1 if differ else 0)
