@@ -1,5 +1,5 @@
 // cfz_common.h -- shared by the two translation units of libconfrez_hip.so (cfz_engine.hip: the MPC step and its closed
-// loop; cfz_planning.hip: state_ws and the collocation plans): error reporting of the C ABI and small host helpers.
+// loop; cfz_planning.hip: state_ws and the collocation plans): error reporting of the C ABI, the memory policies and small host helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,8 @@
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "cfz_devmem.h"
 
 extern thread_local std::string cfz_g_err;  // defined in cfz_engine.hip; what cfz_last_error() returns
 
@@ -45,50 +47,16 @@ inline bool quad_vertices(const double A[4][2], const double b[4], double V[4][2
   return true;
 }
 
-
-// Device memory of one caller, kept between calls: a bump allocator over blocks that are released by arena_destroy, merged
-// into one larger block at the next reset, or given back when the calls have become much smaller than the block (a 256-plan
-// four-vehicle joint launch takes 25 GB; the next reset after a call that used less than a quarter of a block above 256 MB
-// frees it).  Replaces hipMalloc/hipFree per call in the planning entry points (each of those is a device-wide synchronisation).
-struct CfzArena {
-  struct Block { char *base; size_t cap, off; };
-  std::vector<Block> blocks;
-  size_t used_last = 0;
+// The library's memory policies for DevBuf and Arena (cfz_devmem.h): hipMalloc / hipFree and their pinned-host pair stand here alone.
+struct HipMem {
+  static int alloc(void **p, size_t bytes) { const hipError_t e = hipMalloc(p, bytes); return e == hipSuccess ? 0 : fail("hipMalloc", e); }
+  static void free(void *p) { (void)hipFree(p); }
 };
-
-inline int arena_reset(CfzArena &a) {  // start of a call: everything handed out before is free again
-  size_t used = 0, cap = 0;
-  for (auto &b : a.blocks) { used += b.off; cap += b.cap; b.off = 0; }
-  a.used_last = used;
-  if (a.blocks.size() > 1) {  // the last call spilled into extra blocks: one block of the total size from now on
-    for (auto &b : a.blocks) (void)hipFree(b.base);
-    a.blocks.clear();
-    char *p = nullptr;
-    HIP_OK(hipMalloc(&p, cap));
-    a.blocks.push_back({p, cap, 0});
-  } else if (a.blocks.size() == 1 && cap > ((size_t)1 << 28) && used < cap / 4) {
-    (void)hipFree(a.blocks[0].base);  // the previous call needed a fraction of what an earlier one left behind
-    a.blocks.clear();
-  }
-  return 0;
-}
-
-inline int arena_alloc(CfzArena &a, void **out, size_t bytes) {
-  bytes = (bytes + 255) & ~(size_t)255;
-  for (auto &b : a.blocks)
-    if (b.cap - b.off >= bytes) { *out = b.base + b.off; b.off += bytes; return 0; }
-  const size_t cap = bytes > ((size_t)1 << 20) ? bytes : ((size_t)1 << 20);
-  char *p = nullptr;
-  HIP_OK(hipMalloc(&p, cap));
-  a.blocks.push_back({p, cap, bytes});
-  *out = p;
-  return 0;
-}
-
-inline void arena_destroy(CfzArena &a) {
-  for (auto &b : a.blocks) (void)hipFree(b.base);
-  a.blocks.clear();
-}
+struct HipHostMem {
+  static int alloc(void **p, size_t bytes) { const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault); return e == hipSuccess ? 0 : fail("hipHostMalloc", e); }
+  static void free(void *p) { (void)hipHostFree(p); }
+};
+typedef Arena<HipMem> CfzArena;
 #define ARENA_ALLOC(arena, ptr, bytes) do { void *p_ = nullptr; if (arena_alloc((arena), &p_, (bytes))) return -1; (ptr) = (decltype(ptr))p_; } while (0)
 
 }  // namespace

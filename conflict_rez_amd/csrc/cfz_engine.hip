@@ -35,8 +35,8 @@
 //                  priority order, the reachable samples of a vehicle as one row of bits over the lanes
 // The planning kernels (state_ws, collocation plans) and their entry points live in cfz_planning.hip, a translation unit
 // of its own (two units compile in parallel; both at -O3 since round 3, see __graft_entry__.build).
-// Host side: a handle owns all device buffers, one stream and two events; the closed loop's are cfz_handle::Loop, freed in one place
-// (loop_release).  cfz_loop_step is loop_round (prep, solve, post) once for Jacobi or V times for the sequential exchange;
+// Host side: a handle owns all device buffers (DevBuf, cfz_devmem.h), one stream and its events; the closed loop's are cfz_handle::Loop,
+// released by assigning a fresh one.  cfz_loop_step is loop_round (prep, solve, post) once for Jacobi or V times for the sequential exchange;
 // cfz_loop_run picks its kernel from kLoopVariants, the one list of the persistent kernels (loop_variant maps the setting in force
 // to its row).  A setting is stated once on the host side: its fields in cfz_handle::Loop, its device block through upload_setting,
 // its kernel arguments through disturb_args / comm_args, its kernels as rows of kLoopVariants and lines of cfz_loop_run's chain.
@@ -926,6 +926,11 @@ __global__ __launch_bounds__(256) void schedule_kernel(int V, int T, int H, int 
 
 }  // namespace
 
+// Ownership and the commit rule.  Every device block is a DevBuf member: it goes with its owner, and a handle or a Loop that is assigned
+// from a fresh one has released everything.  An entry point that allocates follows one rule:
+//   Build into locals, check every step, move into the handle last.  A refused or failed call leaves the handle as it was.
+// (cfz_loop_init_tables releases the old loop first, to keep peak memory: a failed init leaves no loop.  cfz_loop_run's buffers are
+// work space without contents between calls: each is reserved on its own, and a call after a failure completes the set.)
 struct cfz_handle {
   int device = 0, max_batch = 0;
   cfz::KSpec ks;
@@ -937,49 +942,48 @@ struct cfz_handle {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float last_ms = 0.f;
-  double *obs_tab = nullptr;  // n_obs x 20: A[4][2], b[4], V[4][2] (KSpec::obs_tab)
-  KArgs *kargs = nullptr;     // device copy of {ks, derive(ks), lay}
+  DevBuf<double> obs_tab;  // n_obs x 20: A[4][2], b[4], V[4][2] (KSpec::obs_tab)
+  DevBuf<KArgs> kargs;     // device copy of {ks, derive(ks), lay}
   // carry records (multipliers handed from one MPC iteration to the next), one per slot; per-solve flags
-  double *wst = nullptr;
-  int32_t *carry = nullptr, *slots = nullptr;   // device: per-solve flags and slot ids
-  int32_t *stage_host = nullptr;                // pinned staging for both (2 x max_batch): no blocking copy per solve
+  DevBuf<double> wst;
+  DevBuf<int32_t> carry, slots;                 // device: per-solve flags and slot ids
+  DevBuf<int32_t, HipHostMem> stage_host;       // pinned staging for both (2 x max_batch): no blocking copy per solve
   hipEvent_t ev_stage = nullptr;                // the staged copy, for solves launched on a caller's stream
   int wst_stride = 0, carry_duals = 1;
   bool carry_set = false, slots_set = false, ms_pending = false;
   const int32_t *carry_ext = nullptr;           // cfz_mpc_set_carry_device: the caller's device array, for one solve
   // per-instance buffers
-  double *x0 = nullptr, *ref = nullptr, *nbr = nullptr, *zu = nullptr, *stats = nullptr;
-  int32_t *status = nullptr, *iters = nullptr;
-  double *l = nullptr, *m = nullptr, *lam_ij = nullptr, *lam_ji = nullptr, *s = nullptr;
-  // closed loop: everything cfz_loop_init_tables sets up; loop_release frees it and returns it to these defaults
+  DevBuf<double> x0, ref, nbr, zu, stats;
+  DevBuf<int32_t> status, iters;
+  DevBuf<double> l, m, lam_ij, lam_ji, s;
+  // closed loop: everything cfz_loop_init_tables sets up; loop_release returns it to these defaults
   struct Loop {
     // ref_table[P][V][T][7] the pool of plan sets, table_of[S] the set of each scenario
     int S = 0, T = 0, P = 0;
-    double *ref_table = nullptr, *pred = nullptr, *state = nullptr;
-    int32_t *kidx = nullptr, *order = nullptr, *table_of = nullptr;
+    DevBuf<double> ref_table, pred, state;
+    DevBuf<int32_t> kidx, order, table_of;
     bool have_order = false;
     // exchange order (cfz_loop_set_order; NULL: Jacobi): xperm[S][V] the order of every scenario, xrank[S][V] its inverse,
     // xlist[V][S] the instance ids s * V + xperm[s][r] of round r (the dispatch list of a stepwise round)
-    int32_t *xperm = nullptr, *xrank = nullptr, *xlist = nullptr;
+    DevBuf<int32_t> xperm, xrank, xlist;
     std::vector<int32_t> xperm_host;
     // record of the realised trajectory (cfz_loop_record): rec[rec_cap][S][V][7], rec_si[rec_cap][2][S][V]; rec_used steps written
-    double *rec = nullptr;
-    int32_t *rec_si = nullptr;
-    int rec_cap = 0, rec_used = 0;
+    DevBuf<double> rec;
+    DevBuf<int32_t> rec_si;
+    int rec_cap = 0, rec_used = 0;  // (steps; rec_cap is set once both buffers exist)
     // disturbances (cfz_loop_set_disturbance; dz_on false: none): one device buffer dz_buf = sigma[12] | level[S] | stream[S] (uint32);
     // steps_done below is the step count of the streams.  dz_zero: the same block, all zero, from cfz_loop_init_tables on: what the kernels
     // compiled with kDist take for dz while no disturbance is set (disturb_args).  Zero sigma and level make every d a signed zero
     // whatever the stream id, and x + (+-0) is x for every x (only the sign of a zero x can follow the stream), so one block with
     // zero ids serves the comm and the pool kernels alike.
-    void *dz_buf = nullptr, *dz_zero = nullptr;
+    DevBuf<double> dz_buf, dz_zero;
     uint64_t dz_seed = 0;
     bool dz_on = false;
     // lossy exchange (cfz_loop_set_comm; cm_on false: none): one device buffer cm_buf = p_drop[S] | stream[S] (uint32);
     // cm_ring[D][S][V][7][N] the ring of messages, D = cm_max_age + 2; cm_tau_on the message history starts at
-    void *cm_buf = nullptr;
-    double *cm_ring = nullptr;
+    DevBuf<double> cm_buf, cm_ring;
     uint64_t cm_seed = 0;
-    int cm_max_age = 0, cm_compensate = 0, cm_tau_on = 0, cm_ring_slots = 0;
+    int cm_max_age = 0, cm_compensate = 0, cm_tau_on = 0;
     bool cm_on = false;
     // problem pool (cfz_loop_set_problems; pb_on false: none) as the user gave it: pb_user[P] the block {ks_p, derive(ks_p), lay} of every
     // problem (obs_tab the handle's), pb_user_of[S] the problem of each scenario
@@ -988,21 +992,20 @@ struct cfz_handle {
     bool pb_on = false;
     // map pool (cfz_loop_set_maps; mp_on false: none): mp_tab[mp_M][n_obs][20] the maps' tables in the layout of cfz_handle::obs_tab,
     // mp_poly[mp_M][n_obs] their polygons as the audit reads them, mp_of[S] the map of each scenario (device), mp_user_of the same (host)
-    double *mp_tab = nullptr;
-    cfz::AuditPoly *mp_poly = nullptr;
-    int32_t *mp_of = nullptr;
+    DevBuf<double> mp_tab;
+    DevBuf<cfz::AuditPoly> mp_poly;
+    DevBuf<int32_t> mp_of;
     std::vector<int32_t> mp_user_of;
     int mp_M = 0;
     bool mp_on = false;
-    // what the pool kernels take while either setting is on (compose_pool): pb_pool[pb_cap] one block per (problem, map) pair that some
+    // what the pool kernels take while either setting is on (compose_pool): pb_pool one block per (problem, map) pair that some
     // scenario uses, its obs_tab that map's table; pb_of[S] the block of each scenario
-    KArgs *pb_pool = nullptr;
-    int32_t *pb_of = nullptr;
-    int pb_cap = 0;
+    DevBuf<KArgs> pb_pool;
+    DevBuf<int32_t> pb_of;
     // persistent loop
-    double *pred2 = nullptr, *scratch = nullptr;
-    int32_t *queue = nullptr, *ctrl = nullptr, *done = nullptr, *iter_sum = nullptr;
-    int queue_cap = 0, grid_blocks = 0, steps_done = 0;
+    DevBuf<double> pred2, scratch;
+    DevBuf<int32_t> queue, ctrl, done, iter_sum;
+    int steps_done = 0;
   } lp;
   long last_iter_sum = 0, last_converged = 0, last_status[6] = {0, 0, 0, 0, 0, 0};
   CfzArena arena;  // device buffers of cfz_dual_ws / cfz_joint_dual_ws, kept between calls
@@ -1024,7 +1027,7 @@ int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, cons
                        order, h->carry_duals ? h->wst : nullptr, h->wst_stride, carry, carry_all, h->slots_set ? h->slots : nullptr, tail...);
   };
   if (pool)  // the stepwise closed loop under cfz_loop_set_problems / cfz_loop_set_maps: instance b solves the block of scenario b / V
-    launch(solve_kernel_pool, h->lp.pb_pool, h->lp.pb_of, h->ks.n_nbr + 1);
+    launch(solve_kernel_pool, h->lp.pb_pool.get(), h->lp.pb_of.get(), h->ks.n_nbr + 1);
   else
     launch(solve_kernel);
   h->carry_set = false; h->slots_set = false; h->carry_ext = nullptr;  // the flags of cfz_mpc_set_carry / cfz_mpc_set_slots hold for one solve
@@ -1035,7 +1038,6 @@ int launch_solve(cfz_handle *h, int B, const double *x0, const double *ref, cons
 }
 
 int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt);
-void loop_release(cfz_handle *h);
 
 // the value checks of cfz_create on a spec's sizes and on the options (cfz_problem_check makes the same ones)
 int spec_shape_ok(const cfz_spec *spec) {
@@ -1197,27 +1199,23 @@ int create_fill(cfz_handle *h, const cfz_spec *spec, const cfz_options *opt) {
   {
     std::vector<double> tab((size_t)std::max(k.n_obs, 1) * 20, 0.0);
     for (int j = 0; j < k.n_obs; ++j) obs_tab_entry(tab.data() + (size_t)j * 20, k.A_obs[j], k.b_obs[j], k.V_obs[j]);
-    HIP_OK(hipMalloc(&h->obs_tab, tab.size() * 8));
+    if (h->obs_tab.alloc(tab.size()) || h->kargs.alloc(1)) return -1;
     HIP_OK(hipMemcpy(h->obs_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
     h->ks.obs_tab = h->obs_tab;
     KArgs host_args = {h->ks, cfz::derive(h->ks), h->lay};
-    HIP_OK(hipMalloc(&h->kargs, sizeof(KArgs)));
     HIP_OK(hipMemcpy(h->kargs, &host_args, sizeof(KArgs), hipMemcpyHostToDevice));
   }
   h->carry_duals = opt->carry_duals;
   h->wst_stride = cfz::carry_layout(k.N, k.n_obs + k.n_nbr).stride;
-  HIP_OK(hipMalloc(&h->wst, (size_t)max_batch * h->wst_stride * 8));
+  if (h->wst.alloc((size_t)max_batch * h->wst_stride)) return -1;
   HIP_OK(hipMemset(h->wst, 0, (size_t)max_batch * h->wst_stride * 8));
-  HIP_OK(hipMalloc(&h->carry, (size_t)max_batch * 4)); HIP_OK(hipMalloc(&h->slots, (size_t)max_batch * 4));
-  HIP_OK(hipHostMalloc(&h->stage_host, (size_t)max_batch * 2 * 4, hipHostMallocDefault));
+  if (h->carry.alloc(B) || h->slots.alloc(B) || h->stage_host.alloc(B * 2)) return -1;
   HIP_OK(hipEventCreate(&h->ev0)); HIP_OK(hipEventCreate(&h->ev1)); HIP_OK(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-  HIP_OK(hipMalloc(&h->x0, B * 5 * 8)); HIP_OK(hipMalloc(&h->ref, B * 3 * N * 8));
-  HIP_OK(hipMalloc(&h->nbr, (B * nn * 3 * N + 1) * 8)); HIP_OK(hipMalloc(&h->zu, B * 7 * N * 8));
+  if (h->x0.alloc(B * 5) || h->ref.alloc(B * 3 * N) || h->nbr.alloc(B * nn * 3 * N + 1) || h->zu.alloc(B * 7 * N)) return -1;
   // stats: 3 doubles per instance (+ 24 phase counters per instance for the -DCFZ_STAMPS diagnostic build)
-  HIP_OK(hipMalloc(&h->stats, B * (3 + 24) * 8)); HIP_OK(hipMalloc(&h->status, B * 4)); HIP_OK(hipMalloc(&h->iters, B * 4));
-  HIP_OK(hipMalloc(&h->l, (B * N * 4 * no + 1) * 8)); HIP_OK(hipMalloc(&h->m, (B * N * 4 * no + 1) * 8));
-  HIP_OK(hipMalloc(&h->lam_ij, (B * nn * N * 4 + 1) * 8)); HIP_OK(hipMalloc(&h->lam_ji, (B * nn * N * 4 + 1) * 8));
-  HIP_OK(hipMalloc(&h->s, (B * nn * N * 2 + 1) * 8));
+  if (h->stats.alloc(B * (3 + 24)) || h->status.alloc(B) || h->iters.alloc(B)) return -1;
+  if (h->l.alloc(B * N * 4 * no + 1) || h->m.alloc(B * N * 4 * no + 1)) return -1;
+  if (h->lam_ij.alloc(B * nn * N * 4 + 1) || h->lam_ji.alloc(B * nn * N * 4 + 1) || h->s.alloc(B * nn * N * 2 + 1)) return -1;
   HIP_OK(hipMemset(h->status, 0, B * 4)); HIP_OK(hipMemset(h->iters, 0, B * 4));
   return 0;
 }
@@ -1228,17 +1226,11 @@ extern "C" {
 int cfz_destroy(cfz_handle *h) {
   if (!h) return 0;
   hipSetDevice(h->device);
-  loop_release(h);
-  void *bufs[] = {h->x0, h->ref, h->nbr, h->zu, h->stats, h->status, h->iters, h->l, h->m, h->lam_ij, h->lam_ji, h->s,
-                  h->obs_tab, h->wst, h->carry, h->slots, h->kargs};
-  for (void *p : bufs) if (p) hipFree(p);
-  arena_destroy(h->arena);
-  if (h->stage_host) hipHostFree(h->stage_host);
   if (h->ev0) hipEventDestroy(h->ev0);
   if (h->ev1) hipEventDestroy(h->ev1);
   if (h->ev_stage) hipEventDestroy(h->ev_stage);
   if (h->stream) hipStreamDestroy(h->stream);
-  delete h;
+  delete h;  // (the buffers, the loop's and the arena's go with it)
   return 0;
 }
 
@@ -1438,68 +1430,24 @@ int cfz_joint_dual_ws(cfz_handle *h, int n, const double *poses_this, const doub
 }  // extern "C"
 
 namespace {
-template <class T> void dev_free(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-void record_free(cfz_handle *h) {
-  dev_free(h->lp.rec); dev_free(h->lp.rec_si);
-  h->lp.rec_cap = h->lp.rec_used = 0;
-}
-
-void exchange_free(cfz_handle *h) {
-  dev_free(h->lp.xperm); dev_free(h->lp.xrank); dev_free(h->lp.xlist);
-  h->lp.xperm_host.clear();
-}
-
-void disturb_free(cfz_handle *h) {
-  dev_free(h->lp.dz_buf);
-  h->lp.dz_on = false; h->lp.dz_seed = 0;
-}
-
-void comm_free(cfz_handle *h) {
-  dev_free(h->lp.cm_buf); dev_free(h->lp.cm_ring);
-  h->lp.cm_on = false; h->lp.cm_ring_slots = 0;
-}
-
-void problems_free(cfz_handle *h) {
-  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
-  h->lp.pb_user.clear(); h->lp.pb_user_of.clear();
-  h->lp.pb_on = false; h->lp.pb_cap = 0;
-}
-
-void maps_free(cfz_handle *h) {
-  dev_free(h->lp.mp_tab); dev_free(h->lp.mp_poly); dev_free(h->lp.mp_of);
-  h->lp.mp_user_of.clear();
-  h->lp.mp_on = false; h->lp.mp_M = 0;
-}
-
 // the pool kernels run (solve_kernel_pool, the pool rows of kLoopVariants, loop_post on the pool) whenever either setting is on
 bool pool_on(const cfz_handle *h) { return h->lp.pb_on || h->lp.mp_on; }
 
-// every closed-loop buffer: tables, predictions, state, clock and dispatch order, record, exchange order, disturbance and comm setting, problem pool, map pool
-// and the persistent loop's buffers; their sizes and counters go back to the defaults of cfz_handle::Loop
-void loop_release(cfz_handle *h) {
-  record_free(h); exchange_free(h); disturb_free(h); comm_free(h); problems_free(h); maps_free(h);
-  dev_free(h->lp.dz_zero);
-  dev_free(h->lp.ref_table); dev_free(h->lp.table_of); dev_free(h->lp.pred); dev_free(h->lp.state); dev_free(h->lp.kidx); dev_free(h->lp.order);
-  dev_free(h->lp.pred2); dev_free(h->lp.scratch); dev_free(h->lp.queue); dev_free(h->lp.ctrl); dev_free(h->lp.done); dev_free(h->lp.iter_sum);
-  h->lp = cfz_handle::Loop();
-}
+// every closed-loop buffer, setting, size and counter goes back to the defaults of cfz_handle::Loop
+void loop_release(cfz_handle *h) { h->lp = cfz_handle::Loop(); }
 
 // the disturbance in force as the kernels take it (sigma NULL: none).  zero_if_off: for a kernel compiled with kDist that stands in
 // for one without (the comm and the pool kernels): the all-zero block instead of none
 cfz::DisturbArgs disturb_args(const cfz_handle *h, bool zero_if_off = false) {
   if (!h->lp.dz_on && !zero_if_off) return cfz::disturb_none();
-  const double *f = static_cast<const double *>(h->lp.dz_on ? h->lp.dz_buf : h->lp.dz_zero);
+  const double *f = h->lp.dz_on ? h->lp.dz_buf : h->lp.dz_zero;
   return {h->lp.dz_on ? h->lp.dz_seed : 0, f, f + cfz::kDisturbN, reinterpret_cast<const uint32_t *>(f + cfz::kDisturbN + h->lp.S)};
 }
 
 // the comm setting in force as the kernels take it (p_drop NULL: none)
 cfz::CommArgs comm_args(const cfz_handle *h) {
   if (!h->lp.cm_on) return cfz::comm_none();
-  const double *f = static_cast<const double *>(h->lp.cm_buf);
+  const double *f = h->lp.cm_buf;
   const size_t S = (size_t)h->lp.S;
   return {h->lp.cm_seed, f, reinterpret_cast<const uint32_t *>(f + S), h->lp.cm_ring, h->lp.cm_max_age, h->lp.cm_compensate, h->lp.cm_tau_on,
           S * (h->ks.n_nbr + 1) * 7 * h->ks.N};
@@ -1513,13 +1461,14 @@ int loop_ready(cfz_handle *h, bool drain = false) {
   return 0;
 }
 
-// the device block of a setting, f | stream[S] (uint32; NULL: scenario s draws from stream s), allocated at its first upload
-int upload_setting(cfz_handle *h, void *&buf, const std::vector<double> &f, const uint32_t *stream) {
+// the device block of a setting, f | stream[S] (uint32; NULL: scenario s draws from stream s), in a block of its own: the caller moves
+// it into the handle once its call is complete
+int upload_setting(const cfz_handle *h, DevBuf<double> &buf, const std::vector<double> &f, const uint32_t *stream) {
   std::vector<uint32_t> id((size_t)h->lp.S);
   for (size_t s = 0; s < id.size(); ++s) id[s] = stream ? stream[s] : (uint32_t)s;
-  if (!buf) HIP_OK(hipMalloc(&buf, f.size() * 8 + id.size() * 4));
+  if (buf.alloc(f.size() + (id.size() + 1) / 2)) return -1;
   HIP_OK(hipMemcpy(buf, f.data(), f.size() * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(static_cast<char *>(buf) + f.size() * 8, id.data(), id.size() * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(buf + f.size(), id.data(), id.size() * 4, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -1881,11 +1830,11 @@ int schedule_launch(cfz_handle *h, int P, int V, int T, const double *d_tables, 
 // NULL: the handle's problem for every scenario); map_tab[M][n_obs][20] (device), map_of[S] as cfz_loop_set_maps does (map_tab NULL: the
 // handle's map).  A block is its problem's {sp, dv, L} with sp.obs_tab pointing at its map's table; dv and L do not depend on the
 // obstacles, and the obstacle arrays inside sp stay the handle's (no loop kernel reads them).  The blocks are device allocations of
-// their own, handed back in pool, of, cap (both settings off: none): the caller swaps them in (pool_swap) once its call can no longer
-// fail, so that a refused or failed call leaves the setting in force as it was.
+// their own, handed back in out (both settings off: none): the caller swaps them in (pool_swap) once its call can no longer fail.
+struct PoolBufs { DevBuf<KArgs> pool; DevBuf<int32_t> of; };
 int compose_pool(const cfz_handle *h, const std::vector<KArgs> *probs, const int32_t *problem_of, const double *map_tab, const int32_t *map_of,
-                 KArgs *&pool, int32_t *&of, int &cap) {
-  pool = nullptr; of = nullptr; cap = 0;
+                 PoolBufs &out) {
+  out = PoolBufs();
   if (!probs && !map_tab) return 0;
   const int S = h->lp.S;
   const size_t tab = (size_t)std::max(h->ks.n_obs, 1) * 20;
@@ -1904,19 +1853,13 @@ int compose_pool(const cfz_handle *h, const std::vector<KArgs> *probs, const int
     }
     block_of[s] = it->second;
   }
-  hipError_t e = hipMalloc(&pool, blocks.size() * sizeof(KArgs));
-  if (e == hipSuccess) e = hipMalloc(&of, (size_t)S * 4);
-  if (e == hipSuccess) e = hipMemcpy(pool, blocks.data(), blocks.size() * sizeof(KArgs), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(of, block_of.data(), (size_t)S * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { dev_free(pool); dev_free(of); return fail("device copy of the composed pool", e); }
-  cap = (int)blocks.size();
+  if (out.pool.alloc(blocks.size()) || out.of.alloc((size_t)S)) return -1;
+  HIP_OK(hipMemcpy(out.pool, blocks.data(), blocks.size() * sizeof(KArgs), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(out.of, block_of.data(), (size_t)S * 4, hipMemcpyHostToDevice));
   return 0;
 }
 
-void pool_swap(cfz_handle *h, KArgs *pool, int32_t *of, int cap) {
-  dev_free(h->lp.pb_pool); dev_free(h->lp.pb_of);
-  h->lp.pb_pool = pool; h->lp.pb_of = of; h->lp.pb_cap = cap;
-}
+void pool_swap(cfz_handle *h, PoolBufs &p) { h->lp.pb_pool = std::move(p.pool); h->lp.pb_of = std::move(p.of); }
 }  // namespace
 
 extern "C" {
@@ -1937,24 +1880,25 @@ int cfz_loop_init_tables(cfz_handle *h, int S, int P, int T, const double *table
   }
   HIP_OK(hipSetDevice(h->device));
   loop_release(h);  // record, exchange order, disturbance and comm setting included: back to the undisturbed, lossless Jacobi loop at step 0
-  h->lp.S = S; h->lp.T = T; h->lp.P = P;
+  cfz_handle::Loop lp;  // the new loop, the handle's once it is seeded
+  lp.S = S; lp.T = T; lp.P = P;
   const size_t B = (size_t)S * V;
-  HIP_OK(hipMalloc(&h->lp.ref_table, (size_t)P * V * T * 7 * 8)); HIP_OK(hipMalloc(&h->lp.pred, B * 7 * N * 8));
-  HIP_OK(hipMalloc(&h->lp.state, B * 5 * 8)); HIP_OK(hipMalloc(&h->lp.kidx, (size_t)S * 4));
-  HIP_OK(hipMalloc(&h->lp.order, B * 4)); HIP_OK(hipMalloc(&h->lp.table_of, (size_t)S * 4));
-  const size_t nz = ((size_t)cfz::kDisturbN + S) * 8 + (size_t)S * 4;  // zero sigma[12] | zero level[S] | zero stream[S]
-  HIP_OK(hipMalloc(&h->lp.dz_zero, nz)); HIP_OK(hipMemset(h->lp.dz_zero, 0, nz));
+  if (lp.ref_table.alloc((size_t)P * V * T * 7) || lp.pred.alloc(B * 7 * N) || lp.state.alloc(B * 5)) return -1;
+  if (lp.kidx.alloc((size_t)S) || lp.order.alloc(B) || lp.table_of.alloc((size_t)S)) return -1;
+  if (lp.dz_zero.alloc((size_t)cfz::kDisturbN + S + ((size_t)S + 1) / 2)) return -1;  // zero sigma[12] | zero level[S] | zero stream[S]
+  HIP_OK(hipMemset(lp.dz_zero, 0, lp.dz_zero.size() * 8));
   HIP_OK(hipMemset(h->wst, 0, (size_t)h->max_batch * h->wst_stride * 8));  // first iteration: cold multipliers
-  HIP_OK(hipMemcpy(h->lp.ref_table, tables, (size_t)P * V * T * 7 * 8, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->lp.table_of, tof.data(), (size_t)S * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->lp.kidx, k0, (size_t)S * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(lp.ref_table, tables, (size_t)P * V * T * 7 * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(lp.table_of, tof.data(), (size_t)S * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(lp.kidx, k0, (size_t)S * 4, hipMemcpyHostToDevice));
   double *dn = nullptr;
   if (noise) { if (arena_reset(h->arena)) return -1; ARENA_ALLOC(h->arena, dn, B * 5 * 8); HIP_OK(hipMemcpy(dn, noise, B * 5 * 8, hipMemcpyHostToDevice)); }
   const long nt = (long)B * N;
-  hipLaunchKernelGGL(loop_seed, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, T, h->lp.ref_table,
-                     h->lp.table_of, h->lp.kidx, dn, h->lp.pred, h->lp.state);
+  hipLaunchKernelGGL(loop_seed, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream, S, V, N, T, lp.ref_table,
+                     lp.table_of, lp.kidx, dn, lp.pred, lp.state);
   HIP_OK(hipGetLastError());
   HIP_OK(hipStreamSynchronize(h->stream));
+  h->lp = std::move(lp);
   return 0;
 }
 
@@ -1968,12 +1912,13 @@ int cfz_loop_init(cfz_handle *h, int S, int T, const double *ref_table, const in
 int cfz_loop_record(cfz_handle *h, int K) {
   if (loop_ready(h, true)) return -1;
   if (K < 0) return fail("K must not be negative");
-  record_free(h);
-  if (K == 0) return 0;
   const size_t B = (size_t)h->lp.S * (h->ks.n_nbr + 1);
   if ((size_t)K * B * 7 > ((size_t)1 << 31)) return fail("record too large");
-  HIP_OK(hipMalloc(&h->lp.rec, (size_t)K * B * 7 * 8)); HIP_OK(hipMalloc(&h->lp.rec_si, (size_t)K * 2 * B * 4));
-  h->lp.rec_cap = K;
+  DevBuf<double> rec;
+  DevBuf<int32_t> rec_si;
+  if (rec.alloc((size_t)K * B * 7) || rec_si.alloc((size_t)K * 2 * B)) return -1;  // (K = 0: none)
+  h->lp.rec = std::move(rec); h->lp.rec_si = std::move(rec_si);
+  h->lp.rec_cap = K; h->lp.rec_used = 0;
   return 0;
 }
 
@@ -2178,7 +2123,7 @@ int cfz_loop_plan_schedule(cfz_handle *h, const int32_t *length, const uint8_t *
 
 int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
   if (loop_ready(h, true)) return -1;
-  if (!order) { exchange_free(h); return 0; }
+  if (!order) { h->lp.xperm.reset(); h->lp.xrank.reset(); h->lp.xlist.reset(); h->lp.xperm_host.clear(); return 0; }
   const int S = h->lp.S, V = h->ks.n_nbr + 1;
   std::vector<int32_t> rank((size_t)S * V), list((size_t)V * S);
   for (int s = 0; s < S; ++s) {
@@ -2190,14 +2135,14 @@ int cfz_loop_set_order(cfz_handle *h, const int32_t *order) {
       rank[(size_t)s * V + v] = r; list[(size_t)r * S + s] = s * V + v;
     }
   }
-  if (!h->lp.xperm) {
-    HIP_OK(hipMalloc(&h->lp.xperm, (size_t)S * V * 4)); HIP_OK(hipMalloc(&h->lp.xrank, (size_t)S * V * 4));
-    HIP_OK(hipMalloc(&h->lp.xlist, (size_t)S * V * 4));
-  }
-  HIP_OK(hipMemcpy(h->lp.xperm, order, (size_t)S * V * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->lp.xrank, rank.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
-  HIP_OK(hipMemcpy(h->lp.xlist, list.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
-  h->lp.xperm_host.assign(order, order + (size_t)S * V);
+  DevBuf<int32_t> xperm, xrank, xlist;
+  if (xperm.alloc((size_t)S * V) || xrank.alloc((size_t)S * V) || xlist.alloc((size_t)S * V)) return -1;
+  HIP_OK(hipMemcpy(xperm, order, (size_t)S * V * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(xrank, rank.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(xlist, list.data(), (size_t)S * V * 4, hipMemcpyHostToDevice));
+  std::vector<int32_t> host(order, order + (size_t)S * V);
+  h->lp.xperm = std::move(xperm); h->lp.xrank = std::move(xrank); h->lp.xlist = std::move(xlist);
+  h->lp.xperm_host.swap(host);
   return 0;
 }
 
@@ -2215,8 +2160,9 @@ int cfz_loop_set_disturbance(cfz_handle *h, uint64_t seed, const double sigma_me
     f[cfz::kDisturbN + s] = level ? level[s] : 1.0;
     if (!(f[cfz::kDisturbN + s] >= 0.0) || !std::isfinite(f[cfz::kDisturbN + s])) return fail("a level is negative or not finite");
   }
-  if (upload_setting(h, h->lp.dz_buf, f, stream)) return -1;
-  h->lp.dz_seed = seed; h->lp.dz_on = true;
+  DevBuf<double> buf;
+  if (upload_setting(h, buf, f, stream)) return -1;
+  h->lp.dz_buf = std::move(buf); h->lp.dz_seed = seed; h->lp.dz_on = true;
   return 0;
 }
 
@@ -2246,17 +2192,14 @@ int cfz_loop_set_comm(cfz_handle *h, uint64_t seed, const double *p_drop, int ma
   for (int s = 0; s < S; ++s)
     if (!(p_drop[s] >= 0.0 && p_drop[s] <= 1.0)) return fail("a p_drop is outside [0, 1] or not finite");
   const size_t slot = (size_t)S * V * 7 * N;
-  if (h->lp.cm_ring_slots != max_age + 2) {
-    double *ring = nullptr;
-    HIP_OK(hipMalloc(&ring, (size_t)(max_age + 2) * slot * 8));
-    dev_free(h->lp.cm_ring);
-    h->lp.cm_ring = ring; h->lp.cm_ring_slots = max_age + 2;
-  }
-  if (upload_setting(h, h->lp.cm_buf, std::vector<double>(p_drop, p_drop + S), stream)) return -1;  // p_drop[S] | stream[S]
-  h->lp.cm_seed = seed; h->lp.cm_max_age = max_age; h->lp.cm_compensate = compensate; h->lp.cm_on = true;
+  DevBuf<double> ring, buf;
+  if (ring.alloc((size_t)(max_age + 2) * slot)) return -1;
+  if (upload_setting(h, buf, std::vector<double>(p_drop, p_drop + S), stream)) return -1;  // p_drop[S] | stream[S]
   // history restarts at the message standing in pred, that of the last iteration done
-  h->lp.cm_tau_on = h->lp.steps_done - 1;
-  HIP_OK(hipMemcpy(comm_message(h, h->lp.cm_tau_on), h->lp.pred, slot * 8, hipMemcpyDeviceToDevice));
+  const int tau_on = h->lp.steps_done - 1;
+  HIP_OK(hipMemcpy(ring + (size_t)cfz::comm_slot(tau_on, max_age) * slot, h->lp.pred, slot * 8, hipMemcpyDeviceToDevice));
+  h->lp.cm_ring = std::move(ring); h->lp.cm_buf = std::move(buf);
+  h->lp.cm_seed = seed; h->lp.cm_max_age = max_age; h->lp.cm_compensate = compensate; h->lp.cm_tau_on = tau_on; h->lp.cm_on = true;
   return 0;
 }
 
@@ -2310,11 +2253,9 @@ int cfz_loop_set_problems(cfz_handle *h, int P, const cfz_spec *specs, const cfz
   }
   // the new setting, composed with the map pool in force, is written into blocks of its own and swapped in once it is complete: a
   // failure leaves the one in force as it was
-  KArgs *d = nullptr;
-  int32_t *of = nullptr;
-  int cap = 0;
-  if (compose_pool(h, off ? nullptr : &pool, pool_of.data(), h->lp.mp_on ? h->lp.mp_tab : nullptr, h->lp.mp_user_of.data(), d, of, cap)) return -1;
-  pool_swap(h, d, of, cap);
+  PoolBufs d;
+  if (compose_pool(h, off ? nullptr : &pool, pool_of.data(), h->lp.mp_on ? h->lp.mp_tab.get() : nullptr, h->lp.mp_user_of.data(), d)) return -1;
+  pool_swap(h, d);
   h->lp.pb_user.swap(pool); h->lp.pb_user_of.swap(pool_of);
   h->lp.pb_on = !off;
   return 0;
@@ -2333,13 +2274,12 @@ int cfz_loop_set_maps(cfz_handle *h, int M, const double *A_obs, const double *b
   if (M < 0) return fail("M must not be negative");
   const int S = h->lp.S, no = h->ks.n_obs;
   const std::vector<KArgs> *probs = h->lp.pb_on ? &h->lp.pb_user : nullptr;
-  KArgs *d = nullptr;
-  int32_t *of = nullptr;
-  int cap = 0;
+  PoolBufs d;
   if (M == 0 || !A_obs) {  // off: the kernels without it (the problem pool's, if one is set)
-    if (compose_pool(h, probs, h->lp.pb_user_of.data(), nullptr, nullptr, d, of, cap)) return -1;
-    pool_swap(h, d, of, cap);
-    maps_free(h);
+    if (compose_pool(h, probs, h->lp.pb_user_of.data(), nullptr, nullptr, d)) return -1;
+    pool_swap(h, d);
+    h->lp.mp_tab.reset(); h->lp.mp_poly.reset(); h->lp.mp_of.reset();
+    h->lp.mp_user_of.clear(); h->lp.mp_on = false; h->lp.mp_M = 0;
     return 0;
   }
   if (!b_obs || !map_of) return fail("null b_obs or map_of");
@@ -2357,24 +2297,18 @@ int cfz_loop_set_maps(cfz_handle *h, int M, const double *A_obs, const double *b
     audit_polys(no, V, poly.data() + (size_t)m * no);
   }
   // as in cfz_loop_set_problems: blocks of its own, swapped in once the new setting is complete
-  double *dtab = nullptr;
-  cfz::AuditPoly *dpoly = nullptr;
-  int32_t *dof = nullptr;
-  hipError_t e = hipMalloc(&dtab, tab.size() * 8);
-  if (e == hipSuccess) e = hipMalloc(&dpoly, poly.size() * sizeof(cfz::AuditPoly));
-  if (e == hipSuccess) e = hipMalloc(&dof, (size_t)S * 4);
-  if (e == hipSuccess) e = hipMemcpy(dtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dpoly, poly.data(), poly.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dof, map_of, (size_t)S * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) fail("cfz_loop_set_maps: device copy of the maps", e);
-  if (e != hipSuccess || compose_pool(h, probs, h->lp.pb_user_of.data(), dtab, map_of, d, of, cap)) {
-    dev_free(dtab); dev_free(dpoly); dev_free(dof);
-    return -1;
-  }
-  pool_swap(h, d, of, cap);
-  maps_free(h);
-  h->lp.mp_tab = dtab; h->lp.mp_poly = dpoly; h->lp.mp_of = dof; h->lp.mp_M = M;
-  h->lp.mp_user_of.assign(map_of, map_of + S);
+  DevBuf<double> dtab;
+  DevBuf<cfz::AuditPoly> dpoly;
+  DevBuf<int32_t> dof;
+  if (dtab.alloc(tab.size()) || dpoly.alloc(poly.size()) || dof.alloc((size_t)S)) return -1;
+  HIP_OK(hipMemcpy(dtab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(dpoly, poly.data(), poly.size() * sizeof(cfz::AuditPoly), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(dof, map_of, (size_t)S * 4, hipMemcpyHostToDevice));
+  if (compose_pool(h, probs, h->lp.pb_user_of.data(), dtab, map_of, d)) return -1;
+  std::vector<int32_t> of_host(map_of, map_of + S);
+  pool_swap(h, d);
+  h->lp.mp_tab = std::move(dtab); h->lp.mp_poly = std::move(dpoly); h->lp.mp_of = std::move(dof); h->lp.mp_M = M;
+  h->lp.mp_user_of.swap(of_host);
   h->lp.mp_on = true;
   return 0;
 }
@@ -2453,19 +2387,9 @@ int cfz_loop_run(cfz_handle *h, int K) {
   // would end the launch through the idle give-up
   const int grid = std::min(seq ? S : B, per_cu * ncu);
   const size_t per_block = 5 + 3 * (size_t)N + (size_t)h->ks.n_nbr * 3 * N + 7 * (size_t)N;
-  if (!h->lp.pred2) {
-    HIP_OK(hipMalloc(&h->lp.pred2, (size_t)2 * B * 7 * N * 8)); HIP_OK(hipMalloc(&h->lp.ctrl, (4 + 1024) * 4));
-    HIP_OK(hipMalloc(&h->lp.done, (size_t)S * 4)); HIP_OK(hipMalloc(&h->lp.iter_sum, 32));
-  }
-  if (h->lp.grid_blocks < grid) {
-    if (h->lp.scratch) (void)hipFree(h->lp.scratch);
-    HIP_OK(hipMalloc(&h->lp.scratch, (size_t)grid * per_block * 8)); h->lp.grid_blocks = grid;
-  }
   const size_t qwords = 2 * (size_t)K + total;  // [head K][tail K][slots K x B]
-  if ((size_t)h->lp.queue_cap < qwords) {
-    if (h->lp.queue) (void)hipFree(h->lp.queue);
-    HIP_OK(hipMalloc(&h->lp.queue, qwords * 4)); h->lp.queue_cap = (int)qwords;
-  }
+  if (h->lp.pred2.reserve((size_t)2 * B * 7 * N) || h->lp.ctrl.reserve(4 + 1024) || h->lp.done.reserve((size_t)S) || h->lp.iter_sum.reserve(8)) return -1;
+  if (h->lp.scratch.reserve((size_t)grid * per_block) || h->lp.queue.reserve(qwords)) return -1;
   // parity 0 of the double buffer <- current predictions (the ring of messages already holds them); queue <- all items of iteration 0
   if (!comm) HIP_OK(hipMemcpyAsync(h->lp.pred2, h->lp.pred, (size_t)B * 7 * N * 8, hipMemcpyDeviceToDevice, h->stream));
   HIP_OK(hipMemsetAsync(h->lp.queue, 0, 2 * (size_t)K * 4, h->stream));
@@ -2495,11 +2419,11 @@ int cfz_loop_run(cfz_handle *h, int K) {
                                                           : (kLoopPrioTailDiv > 0 ? std::max(V, B / kLoopPrioTailDiv) : 0);
 #ifdef CFZ_LOOP_TRACE
   {
-    static long long *trace_dev = nullptr; static size_t trace_cap = 0;
-    if (trace_cap < total) {
-      if (trace_dev) (void)hipFree(trace_dev);
-      HIP_OK(hipMalloc(&trace_dev, total * kLoopTraceWords * 8)); trace_cap = total;
-      HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(cfz_loop_trace_buf), &trace_dev, sizeof trace_dev));
+    static DevBuf<long long> trace_dev;
+    if (trace_dev.size() < total * kLoopTraceWords) {
+      if (trace_dev.reserve(total * kLoopTraceWords)) return -1;
+      long long *const p = trace_dev;
+      HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(cfz_loop_trace_buf), &p, sizeof p));
     }
     HIP_OK(hipMemsetAsync(trace_dev, 0, total * kLoopTraceWords * 8, h->stream));
     g_loop_trace_dev = trace_dev; g_loop_trace_items = total; g_loop_trace_grid = grid;

@@ -164,9 +164,8 @@ int cfz_plan_ws_trim(cfz_plan_ws *w) {
 int cfz_plan_ws_destroy(cfz_plan_ws *w) {
   if (!w) return 0;
   (void)hipSetDevice(w->device);
-  arena_destroy(w->arena);
   if (w->stream) (void)hipStreamDestroy(w->stream);
-  delete w;
+  delete w;  // (the arena's blocks go with it)
   return 0;
 }
 
