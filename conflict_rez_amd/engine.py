@@ -105,118 +105,117 @@ class ProblemSpec:
 
 _lib = None
 
-
 ABI_VERSION = 6  # CFZ_ABI_VERSION of include/confrez_hip.h
+
+_i, _d, _vp, _P = C.c_int, C.c_double, C.c_void_p, C.POINTER
+_h = _ws = _vp  # cfz_handle *, cfz_plan_ws *: opaque
+_spec, _opt, _popt, _copt = _P(_CSpec), _P(_COptions), _P(_CPlanOptions), _P(_CCollocOptions)
+
+# The binding's one statement of include/confrez_hip.h: every function of the header, in its order, name -> (restype, argtypes).
+# tests/test_abi.py parses the header and holds each row to its prototype (count and type of every parameter).
+PROTOTYPES = {
+    "cfz_default_spec": (None, [_spec]),
+    "cfz_default_options": (None, [_opt]),
+    "cfz_create": (_i, [_spec, _opt, _i, _i, _P(_vp)]),
+    "cfz_destroy": (_i, [_h]),
+    "cfz_max_batch": (_i, [_h]),
+    "cfz_kernel_info": (_i, [_h, _vp, _vp]),
+    "cfz_mpc_set_params": (_i, [_h, _i, _vp, _vp, _vp]),
+    "cfz_mpc_set_warm": (_i, [_h, _i, _vp]),
+    "cfz_mpc_set_carry": (_i, [_h, _i, _vp]),
+    "cfz_mpc_set_carry_device": (_i, [_h, _i, _vp]),
+    "cfz_mpc_set_slots": (_i, [_h, _i, _vp]),
+    "cfz_mpc_solve": (_i, [_h, _i]),
+    "cfz_mpc_get": (_i, [_h, _i] + [_vp] * 6),
+    "cfz_mpc_stats": (_i, [_h, _i] + [_vp] * 5),
+    "cfz_last_solve_ms": (_d, [_h]),
+    "cfz_mpc_solve_device": (_i, [_h, _i] + [_vp] * 8),
+    "cfz_vsl_step": (_i, [_h, _i, _i, _i, _vp, _i, _vp, _vp, _i] + [_vp] * 8),
+    "cfz_dual_ws": (_i, [_h, _i] + [_vp] * 4),
+    "cfz_joint_dual_ws": (_i, [_h, _i] + [_vp] * 6),
+    "cfz_default_plan_options": (None, [_popt]),
+    "cfz_plan_ws_create": (_i, [_i, _P(_vp)]),
+    "cfz_plan_ws_destroy": (_i, [_ws]),
+    "cfz_plan_ws_trim": (_i, [_ws]),
+    "cfz_state_ws_w": (_i, [_ws, _i, _popt] + [_vp] * 9),
+    "cfz_state_ws": (_i, [_i, _i, _popt] + [_vp] * 9),
+    "cfz_state_ws_default_guess": (_i, [C.c_int32, C.c_int32, _vp, _d, _vp, _vp]),
+    "cfz_default_colloc_options": (None, [_copt]),
+    "cfz_colloc_w": (_i, [_ws, _i, _spec, _copt] + [_vp] * 11),
+    "cfz_colloc": (_i, [_i, _i, _spec, _copt] + [_vp] * 11),
+    "cfz_joint_colloc_w": (_i, [_ws, _i, _i, _spec, _copt] + [_vp] * 6 + [_i] + [_vp] * 6),
+    "cfz_joint_colloc": (_i, [_i, _i, _i, _spec, _copt] + [_vp] * 6 + [_i] + [_vp] * 6),
+    "cfz_colloc_band_info": (_i, [_i, _vp, _vp, _i, _i, _i] + [_vp] * 4),
+    "cfz_colloc_elimination_info": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _i] + [_vp] * 5),
+    "cfz_abi_version": (_i, []),
+    "cfz_loop_init": (_i, [_h, _i, _i, _vp, _vp, _vp]),
+    "cfz_loop_step": (_i, [_h]),
+    "cfz_loop_run": (_i, [_h, _i]),
+    "cfz_loop_last_iterations": (C.c_long, [_h]),
+    "cfz_loop_last_converged": (C.c_long, [_h]),
+    "cfz_loop_last_status_counts": (_i, [_h, _vp]),
+    "cfz_loop_get": (_i, [_h] + [_vp] * 4),
+    "cfz_loop_set_order": (_i, [_h, _vp]),
+    "cfz_loop_set_disturbance": (_i, [_h, C.c_uint64] + [_vp] * 5),
+    "cfz_loop_disturbance": (_i, [_h, _i, _i, _vp]),
+    "cfz_loop_set_comm": (_i, [_h, C.c_uint64, _vp, _i, _i, _vp]),
+    "cfz_loop_comm": (_i, [_h, _i, _i, _vp]),
+    "cfz_problem_check": (_i, [_spec, _opt, _spec, _opt]),
+    "cfz_loop_set_problems": (_i, [_h, _i, _vp, _vp, _vp]),  # (arrays of cfz_spec and cfz_options, passed raw)
+    "cfz_map_check": (_i, [_spec, _vp, _vp]),
+    "cfz_loop_set_maps": (_i, [_h, _i, _vp, _vp, _vp]),
+    "cfz_loop_init_tables": (_i, [_h, _i, _i, _i] + [_vp] * 4),
+    "cfz_loop_record": (_i, [_h, _i]),
+    "cfz_loop_history": (_i, [_h, _i, _i, _vp, _vp, _vp]),
+    "cfz_loop_audit": (_i, [_h, _i, _i, _d, _d, _d] + [_vp] * 4),
+    "cfz_audit": (_i, [_h, _i, _i, _i, _vp, _vp, _d, _d, _d] + [_vp] * 4),
+    "cfz_audit_maps": (_i, [_h, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _d, _d, _d] + [_vp] * 4),
+    "cfz_loop_score": (_i, [_h, _i, _i, _d, _d, _d, _d, _vp, _vp]),
+    "cfz_score": (_i, [_h, _i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _d, _d, _d, _d, _vp, _vp]),
+    "cfz_plan_conflicts": (_i, [_h, _i, _i, _i, _vp, _i, _d, _vp, _vp]),
+    "cfz_loop_plan_conflicts": (_i, [_h, _i, _d, _vp, _vp]),
+    "cfz_delay_search": (_i, [_h, _i, _i, _i, _vp, _vp, _i] + [_vp] * 4),
+    "cfz_plan_delays": (_i, [_h, _i, _i, _i, _vp, _i, _d, _i] + [_vp] * 4),
+    "cfz_loop_plan_delays": (_i, [_h, _i, _d, _i] + [_vp] * 4),
+    "cfz_plan_coordination": (_i, [_h, _i, _i, _i, _vp, _vp, _d, _vp]),
+    "cfz_plan_schedule": (_i, [_h, _i, _i, _i, _vp, _vp, _vp, _i, _d, _i, _i] + [_vp] * 5),
+    "cfz_loop_plan_schedule": (_i, [_h, _vp, _vp, _i, _d, _i, _i] + [_vp] * 5),
+    "cfz_last_error": (C.c_char_p, []),
+    "cfz_source_hash": (C.c_char_p, []),
+}
+EXPORTS = tuple(PROTOTYPES)
 
 
 def load_library(path=None):
-    """Loads libconfrez_hip.so and declares the prototypes of include/confrez_hip.h."""
+    """Loads libconfrez_hip.so and binds every row of PROTOTYPES.  The package's own library must export them all; one named by `path`
+    or CFZ_LIBRARY (a diagnostic build, another commit's build: tools/) may lack some, which then stay unbound."""
     global _lib
     if _lib is not None and path is None:
         return _lib
-    path = path or os.environ.get("CFZ_LIBRARY") or LIB_PATH  # CFZ_LIBRARY: diagnostic builds (tools/)
+    own = not (path or os.environ.get("CFZ_LIBRARY"))
+    path = path or os.environ.get("CFZ_LIBRARY") or LIB_PATH
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). conflict_rez_amd has no CPU solver."
         )
     lib = C.CDLL(path)
-    vp, i32p = C.c_void_p, C.c_void_p
-    # the structs below mirror include/confrez_hip.h at this layout version (ADVICE r4: a caller compiled against another round's header
-    # would hand over shorter structs)
-    if not hasattr(lib, "cfz_abi_version") or lib.cfz_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"{path}: struct layout version {lib.cfz_abi_version() if hasattr(lib, 'cfz_abi_version') else 'none'}, this binding is written against {ABI_VERSION}: rebuild the library")
-    lib.cfz_last_error.restype = C.c_char_p
-    lib.cfz_source_hash.restype = C.c_char_p
-    lib.cfz_colloc_band_info.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.cfz_colloc_elimination_info.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int] + [vp] * 5
-    lib.cfz_default_spec.argtypes = [C.POINTER(_CSpec)]
-    lib.cfz_default_options.argtypes = [C.POINTER(_COptions)]
-    lib.cfz_create.argtypes = [C.POINTER(_CSpec), C.POINTER(_COptions), C.c_int, C.c_int, C.POINTER(vp)]
-    lib.cfz_destroy.argtypes = [vp]
-    lib.cfz_max_batch.argtypes = [vp]
-    lib.cfz_kernel_info.argtypes = [vp, vp, vp]
-    lib.cfz_mpc_set_params.argtypes = [vp, C.c_int, vp, vp, vp]
-    lib.cfz_mpc_set_warm.argtypes = [vp, C.c_int, vp]
-    lib.cfz_joint_dual_ws.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.cfz_default_plan_options.argtypes = [C.POINTER(_CPlanOptions)]
-    lib.cfz_state_ws.argtypes = [C.c_int, C.c_int, C.POINTER(_CPlanOptions)] + [vp] * 9
-    lib.cfz_state_ws_w.argtypes = [vp, C.c_int, C.POINTER(_CPlanOptions)] + [vp] * 9
-    lib.cfz_state_ws_default_guess.argtypes = [C.c_int32, C.c_int32, vp, C.c_double, vp, vp]
-    lib.cfz_plan_ws_create.argtypes = [C.c_int, C.POINTER(vp)]
-    lib.cfz_plan_ws_destroy.argtypes = [vp]
-    lib.cfz_plan_ws_trim.argtypes = [vp]
-    lib.cfz_default_colloc_options.argtypes = [C.POINTER(_CCollocOptions)]
-    lib.cfz_colloc.argtypes = [C.c_int, C.c_int, C.POINTER(_CSpec), C.POINTER(_CCollocOptions)] + [vp] * 11
-    lib.cfz_colloc_w.argtypes = [vp, C.c_int, C.POINTER(_CSpec), C.POINTER(_CCollocOptions)] + [vp] * 11
-    lib.cfz_joint_colloc.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(_CSpec), C.POINTER(_CCollocOptions)] + [vp] * 6 + [C.c_int] + [vp] * 6
-    lib.cfz_joint_colloc_w.argtypes = [vp, C.c_int, C.c_int, C.POINTER(_CSpec), C.POINTER(_CCollocOptions)] + [vp] * 6 + [C.c_int] + [vp] * 6
-    lib.cfz_mpc_set_carry.argtypes = [vp, C.c_int, vp]
-    lib.cfz_mpc_set_carry_device.argtypes = [vp, C.c_int, vp]
-    lib.cfz_mpc_set_slots.argtypes = [vp, C.c_int, vp]
-    lib.cfz_mpc_solve.argtypes = [vp, C.c_int]
-    lib.cfz_mpc_get.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.cfz_mpc_stats.argtypes = [vp, C.c_int, i32p, i32p, vp, vp, vp]
-    lib.cfz_last_solve_ms.argtypes = [vp]
-    lib.cfz_last_solve_ms.restype = C.c_double
-    lib.cfz_mpc_solve_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.cfz_dual_ws.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    lib.cfz_loop_init.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-    lib.cfz_loop_step.argtypes = [vp]
-    lib.cfz_loop_run.argtypes = [vp, C.c_int]
-    lib.cfz_loop_last_iterations.argtypes = [vp]
-    lib.cfz_loop_last_iterations.restype = C.c_long
-    lib.cfz_vsl_step.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.cfz_loop_last_converged.argtypes = [vp]
-    lib.cfz_loop_last_converged.restype = C.c_long
-    lib.cfz_loop_last_status_counts.argtypes = [vp, vp]
-    lib.cfz_loop_get.argtypes = [vp, vp, vp, vp, vp]
-    lib.cfz_loop_set_order.argtypes = [vp, vp]
-    if hasattr(lib, "cfz_loop_set_disturbance"):  # (tools/gpu_lib_compare.py loads the build before this export through `path`)
-        lib.cfz_loop_set_disturbance.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, vp]
-        lib.cfz_loop_disturbance.argtypes = [vp, C.c_int, C.c_int, vp]
-    if hasattr(lib, "cfz_loop_set_comm"):
-        lib.cfz_loop_set_comm.argtypes = [vp, C.c_uint64, vp, C.c_int, C.c_int, vp]
-        lib.cfz_loop_comm.argtypes = [vp, C.c_int, C.c_int, vp]
-    if hasattr(lib, "cfz_loop_set_problems"):
-        lib.cfz_problem_check.argtypes = [C.POINTER(_CSpec), C.POINTER(_COptions), C.POINTER(_CSpec), C.POINTER(_COptions)]
-        lib.cfz_loop_set_problems.argtypes = [vp, C.c_int, vp, vp, vp]
-    if hasattr(lib, "cfz_loop_set_maps"):
-        lib.cfz_map_check.argtypes = [C.POINTER(_CSpec), vp, vp]
-        lib.cfz_loop_set_maps.argtypes = [vp, C.c_int, vp, vp, vp]
-        lib.cfz_audit_maps.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
-    lib.cfz_loop_init_tables.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.cfz_loop_record.argtypes = [vp, C.c_int]
-    lib.cfz_loop_history.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-    lib.cfz_loop_audit.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
-    lib.cfz_audit.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
-    if hasattr(lib, "cfz_loop_score"):
-        lib.cfz_loop_score.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
-        lib.cfz_score.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_double, C.c_double, C.c_double,
-                                  C.c_double, vp, vp]
-    if hasattr(lib, "cfz_plan_conflicts"):
-        lib.cfz_plan_conflicts.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, vp, vp]
-        lib.cfz_loop_plan_conflicts.argtypes = [vp, C.c_int, C.c_double, vp, vp]
-    if hasattr(lib, "cfz_delay_search"):
-        lib.cfz_delay_search.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp, vp]
-        lib.cfz_plan_delays.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
-        lib.cfz_loop_plan_delays.argtypes = [vp, C.c_int, C.c_double, C.c_int, vp, vp, vp, vp]
-    if hasattr(lib, "cfz_plan_schedule"):
-        lib.cfz_plan_coordination.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, vp]
-        lib.cfz_plan_schedule.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-        lib.cfz_loop_plan_schedule.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    # the struct mirrors above have the layout of this version of the header: a library of another version would read shorter structs
+    version = lib.cfz_abi_version() if hasattr(lib, "cfz_abi_version") else "none"
+    if version != ABI_VERSION:
+        raise RuntimeError(f"{path}: struct layout version {version}, this binding is written against {ABI_VERSION}: rebuild the library")
+    missing = []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            missing.append(name)
+        else:
+            fn.restype, fn.argtypes = restype, argtypes
+    if missing and own:
+        raise RuntimeError(f"{path} lacks symbols {missing}")
     _lib = lib
     return lib
 
-
-EXPORTS = (
-    "cfz_default_spec cfz_default_options cfz_create cfz_destroy cfz_max_batch cfz_kernel_info cfz_mpc_set_params cfz_mpc_set_warm "
-    "cfz_source_hash cfz_abi_version cfz_colloc_elimination_info cfz_colloc_band_info cfz_joint_dual_ws cfz_default_plan_options cfz_state_ws cfz_state_ws_default_guess cfz_default_colloc_options cfz_colloc cfz_joint_colloc cfz_plan_ws_create cfz_plan_ws_destroy cfz_plan_ws_trim cfz_state_ws_w cfz_colloc_w cfz_joint_colloc_w cfz_mpc_set_carry cfz_mpc_set_carry_device cfz_mpc_set_slots cfz_mpc_solve cfz_mpc_get cfz_mpc_stats cfz_last_solve_ms cfz_mpc_solve_device cfz_dual_ws cfz_loop_init cfz_loop_step cfz_loop_run cfz_loop_last_iterations cfz_loop_last_converged cfz_loop_last_status_counts cfz_vsl_step "
-    "cfz_loop_get cfz_last_error cfz_loop_init_tables cfz_loop_record cfz_loop_history cfz_loop_audit cfz_audit cfz_loop_set_order "
-    "cfz_loop_set_disturbance cfz_loop_disturbance cfz_loop_set_comm cfz_loop_comm cfz_problem_check cfz_loop_set_problems cfz_map_check cfz_loop_set_maps cfz_audit_maps "
-    "cfz_loop_score cfz_score cfz_plan_conflicts cfz_loop_plan_conflicts cfz_delay_search cfz_plan_delays cfz_loop_plan_delays "
-    "cfz_plan_coordination cfz_plan_schedule cfz_loop_plan_schedule"
-).split()
 
 # tolerances of the audit's arrival test (`Engine.loop_audit`, `Engine.audit`): position [m], heading [rad], speed [m/s]
 ARRIVE_TOL = dict(pos_tol=0.3, psi_tol=0.1, v_tol=0.1)

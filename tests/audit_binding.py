@@ -2,42 +2,25 @@
 (tests/emu/cfz_audit_emu.cpp over conflict_rez_amd/csrc/cfz_audit.inl), and an independent numpy statement of the same
 definitions (vertex-edge distances, separating-axis overlaps) that both the CPU build and the GPU kernel are checked against."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from emu_build import build_shared
+from emu_build import load, ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_audit_emu.so")
-_lib = None
-
-
-def build(force=False):
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_audit_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_audit.inl"),
-            os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_wave.inl")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
+_i, _d, _vp = C.c_int, C.c_double, C.c_void_p
+PROTOTYPES = {  # of tests/emu/cfz_audit_emu.cpp
+    "cfz_emu_signed_distance": (_d, [_vp, _vp]),
+    "cfz_emu_audit": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _d, _d, _d, _i, _vp, _vp, _vp, _vp]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp = C.c_void_p
-        _lib.cfz_emu_signed_distance.argtypes = [vp, vp]
-        _lib.cfz_emu_signed_distance.restype = C.c_double
-        _lib.cfz_emu_audit.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, C.c_int,
-                                       vp, vp, vp, vp]
-    return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return load("cfz_audit_emu", ("tests/emu/cfz_audit_emu.cpp", "conflict_rez_amd/csrc/cfz_audit.inl", "conflict_rez_amd/csrc/cfz_wave.inl"), PROTOTYPES)
 
 
 def emu_signed_distance(P, Q):
     P = np.ascontiguousarray(P, float).reshape(4, 2); Q = np.ascontiguousarray(Q, float).reshape(4, 2)
-    return float(lib().cfz_emu_signed_distance(_p(P), _p(Q)))
+    return float(lib().cfz_emu_signed_distance(ptr(P), ptr(Q)))
 
 
 def emu_audit(traj, goal, obs, g, pos_tol, psi_tol, v_tol, lanes=64):
@@ -45,8 +28,8 @@ def emu_audit(traj, goal, obs, g, pos_tol, psi_tol, v_tol, lanes=64):
     obs = np.ascontiguousarray(np.asarray(obs, float).reshape(-1, 4, 2)); g = np.ascontiguousarray(g, float)
     K, S, V = traj.shape[:3]
     out = dict(clear=np.empty((S, 2)), where=np.empty((S, 6), np.int32), first_contact=np.empty(S, np.int32), arrive=np.empty((S, V), np.int32))
-    rc = lib().cfz_emu_audit(K, S, V, _p(traj), _p(goal), len(obs), _p(obs) if len(obs) else None, _p(g), pos_tol, psi_tol, v_tol, lanes,
-                             _p(out["clear"]), _p(out["where"]), _p(out["first_contact"]), _p(out["arrive"]))
+    rc = lib().cfz_emu_audit(K, S, V, ptr(traj), ptr(goal), len(obs), ptr(obs) if len(obs) else None, ptr(g), pos_tol, psi_tol, v_tol, lanes,
+                             ptr(out["clear"]), ptr(out["where"]), ptr(out["first_contact"]), ptr(out["arrive"]))
     assert rc == 0
     return out
 

@@ -10,37 +10,24 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from disturbance_binding import philox4x32_10  # noqa: E402
-from emu_build import build_shared  # noqa: E402
+from emu_build import load, ptr  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_comm_emu.so")
-_lib = None
 MAX_AGE = 6  # CFZ_MAX_AGE
-
-
-def build(force=False):
-    csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_comm_emu.cpp"), os.path.join(csrc, "cfz_comm.inl"), os.path.join(csrc, "cfz_disturb.inl")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
+_i, _vp = C.c_int, C.c_void_p
+PROTOTYPES = {  # of tests/emu/cfz_comm_emu.cpp
+    "cfz_emu_max_age": (_i, []),
+    "cfz_emu_delivered": (None, [C.c_long] + [_vp] * 8),
+    "cfz_emu_comm": (None, [C.c_uint64, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "cfz_emu_age": (_i, [_vp, _i, _i, _i, _i]),
+    "cfz_emu_age_drawn": (_i, [C.c_uint64, _vp, _vp] + [_i] * 6),
+    "cfz_emu_want": (_i, [_i, _i]),
+    "cfz_emu_slot": (_i, [_i, _i]),
+    "cfz_emu_row": (_i, [_i] * 5),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp, i = C.c_void_p, C.c_int
-        _lib.cfz_emu_delivered.argtypes = [C.c_long] + [vp] * 8
-        _lib.cfz_emu_comm.argtypes = [C.c_uint64, vp, vp, i, i, i, i, vp]
-        _lib.cfz_emu_age.argtypes = [vp, i, i, i, i]
-        _lib.cfz_emu_age_drawn.argtypes = [C.c_uint64, vp, vp, i, i, i, i, i, i]
-        _lib.cfz_emu_want.argtypes = [i, i]
-        _lib.cfz_emu_slot.argtypes = [i, i]
-        _lib.cfz_emu_row.argtypes = [i] * 5
-    return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return load("cfz_comm_emu", ("tests/emu/cfz_comm_emu.cpp", "conflict_rez_amd/csrc/cfz_comm.inl", "conflict_rez_amd/csrc/cfz_disturb.inl"), PROTOTYPES)
 
 
 def emu_delivered(seed, stream, v, u, tau, p):
@@ -50,25 +37,25 @@ def emu_delivered(seed, stream, v, u, tau, p):
     v, u, tau = (np.ascontiguousarray(np.broadcast_to(a, n), np.int32) for a in (v, u, tau))
     p = np.ascontiguousarray(np.broadcast_to(p, n), float)
     bit, ctr = np.empty(n, np.int32), np.empty((n, 4), np.uint32)
-    lib().cfz_emu_delivered(n, _p(seed), _p(stream), _p(v), _p(u), _p(tau), _p(p), _p(bit), _p(ctr))
+    lib().cfz_emu_delivered(n, ptr(seed), ptr(stream), ptr(v), ptr(u), ptr(tau), ptr(p), ptr(bit), ptr(ctr))
     return bit.astype(bool), ctr
 
 
 def emu_comm(seed, p_drop, stream, V, tau0, K):
     p_drop = np.ascontiguousarray(p_drop, float); stream = np.ascontiguousarray(stream, np.uint32)
     out = np.empty((K, len(p_drop), V, V), np.int32)
-    lib().cfz_emu_comm(C.c_uint64(int(seed)), _p(p_drop), _p(stream), len(p_drop), V, int(tau0), int(K), _p(out))
+    lib().cfz_emu_comm(C.c_uint64(int(seed)), ptr(p_drop), ptr(stream), len(p_drop), V, int(tau0), int(K), ptr(out))
     return out.astype(bool)
 
 
 def emu_age(bits, base, tau_star, max_age, tau_on):
     bits = np.ascontiguousarray(bits, np.int32)
-    return lib().cfz_emu_age(_p(bits), int(base), int(tau_star), int(max_age), int(tau_on))
+    return lib().cfz_emu_age(ptr(bits), int(base), int(tau_star), int(max_age), int(tau_on))
 
 
 def emu_age_drawn(seed, p_drop, stream, max_age, tau_on, s, v, u, tau_star):
     p_drop = np.ascontiguousarray(p_drop, float); stream = np.ascontiguousarray(stream, np.uint32)
-    return lib().cfz_emu_age_drawn(C.c_uint64(int(seed)), _p(p_drop), _p(stream), int(max_age), int(tau_on), int(s), int(v), int(u), int(tau_star))
+    return lib().cfz_emu_age_drawn(C.c_uint64(int(seed)), ptr(p_drop), ptr(stream), int(max_age), int(tau_on), int(s), int(v), int(u), int(tau_star))
 
 
 # ---- numpy statement of the delivery bits ------------------------------------------------------------------------------------------

@@ -5,16 +5,17 @@ statement of the definitions of include/confrez_hip.h ("conflict map of a set of
 synthetic plans and the comparison rule both test modules use."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 
 import audit_binding as ab
-from emu_build import build_shared
+from emu_build import load, ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_conflict_emu.so")
-_lib = None
+_i, _d, _vp = C.c_int, C.c_double, C.c_void_p
+PROTOTYPES = {  # of tests/emu/cfz_conflict_emu.cpp
+    "cfz_emu_conflict_lds_t": (_i, []),
+    "cfz_emu_plan_conflicts": (_i, [_i, _i, _i, _vp, _vp, _i, _d, _i, _vp, _vp]),
+}
 
 G = (3.3, 0.9, 0.6, 0.9)  # the default body (front, left, rear, right)
 MARGIN = 0.05             # the default dmin
@@ -26,24 +27,9 @@ PS = (1, 3)
 INTS = ("when", "first", "count")
 
 
-def build(force=False):
-    csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_conflict_emu.cpp"), os.path.join(csrc, "cfz_conflict.inl"), os.path.join(csrc, "cfz_audit.inl"), os.path.join(csrc, "cfz_wave.inl"), os.path.join(ROOT, "tests", "emu", "emu_columns.h")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp = C.c_void_p
-        _lib.cfz_emu_plan_conflicts.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_double, C.c_int, vp, vp]
-        _lib.cfz_emu_conflict_lds_t.argtypes = []
-    return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return load("cfz_conflict_emu", ["tests/emu/cfz_conflict_emu.cpp", "tests/emu/emu_columns.h"] + ["conflict_rez_amd/csrc/" + f for f in ("cfz_conflict.inl", "cfz_audit.inl", "cfz_wave.inl")],
+                PROTOTYPES)
 
 
 def lds_t():
@@ -64,7 +50,7 @@ def emu_conflicts(tables, D, margin=MARGIN, g=G, lanes=64):
     g = np.ascontiguousarray(g, float)
     npair = V * (V - 1) // 2
     clear, info = np.empty((P, npair, 2 * D + 1)), np.empty((P, npair, 2 * D + 1, 3), np.int32)
-    assert lib().cfz_emu_plan_conflicts(P, V, T, _p(tables), _p(g), D, margin, lanes, _p(clear), _p(info)) == 0
+    assert lib().cfz_emu_plan_conflicts(P, V, T, ptr(tables), ptr(g), D, margin, lanes, ptr(clear), ptr(info)) == 0
     return dict(clear=clear, when=info[..., 0], first=info[..., 1], count=info[..., 2])
 
 

@@ -6,37 +6,19 @@ the GPU kernel are checked against.  Also the synthetic maps and the cases both 
 import ctypes as C
 import functools
 import itertools
-import os
 
 import numpy as np
 
 from conflict_binding import pairs
-from emu_build import build_shared
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_delay_emu.so")
-_lib = None
+from emu_build import load, ptr
 
 OUT = ("delays", "found", "span", "total")
-
-
-def build(force=False):
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_delay_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_delay.inl"),
-            os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_wave.inl")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
+_i, _vp = C.c_int, C.c_void_p
+PROTOTYPES = {"cfz_emu_delay_search": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp])}  # of tests/emu/cfz_delay_emu.cpp
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp = C.c_void_p
-        _lib.cfz_emu_delay_search.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp]
-    return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return load("cfz_delay_emu", ("tests/emu/cfz_delay_emu.cpp", "conflict_rez_amd/csrc/cfz_delay.inl", "conflict_rez_amd/csrc/cfz_wave.inl"), PROTOTYPES)
 
 
 def vehicles(npair):
@@ -57,7 +39,7 @@ def emu_delays(count, clear=None, slack=0, cap=None, lanes=64):
     clear = None if clear is None else np.ascontiguousarray(clear, float)
     cap = None if cap is None else _caps(cap, P, V, D)
     delays, info, rclear = np.full((P, V), -7, np.int32), np.full((P, 3), -7, np.int32), np.full(P, np.nan)
-    assert lib().cfz_emu_delay_search(P, V, D, _p(count), _p(clear), slack, _p(cap), lanes, _p(delays), _p(info), _p(rclear)) == 0
+    assert lib().cfz_emu_delay_search(P, V, D, ptr(count), ptr(clear), slack, ptr(cap), lanes, ptr(delays), ptr(info), ptr(rclear)) == 0
     return dict(delays=delays, found=info[:, 0] == 1, span=info[:, 1], total=info[:, 2], clear=rclear)
 
 
@@ -154,22 +136,22 @@ def check_refusals(lib, h):
     count, tab = np.zeros((2, 6, 9), np.int32), np.ascontiguousarray(cb.synthetic(2, 4, 64))
     delays, info, rclear = np.full((2, 4), 7, np.int32), np.full((2, 3), 7, np.int32), np.full(2, 7.0)
     cap_bad, cap_neg = np.array([[4, 4, 4, 4], [4, 5, 4, 4]], np.int32), np.array([[0, -1, 0, 0]] * 2, np.int32)
-    o = (_p(delays), _p(info), _p(rclear))
-    search = lambda P=2, V=4, D=4, c=_p(count), r=0, cap=None, out=o: lib.cfz_delay_search(h, P, V, D, c, None, r, cap, *out)  # noqa: E731
-    plan = lambda P=2, V=4, T=64, t=_p(tab), D=4, m=0.05, r=0, cap=None, out=o: lib.cfz_plan_delays(h, P, V, T, t, D, m, r, cap, *out)  # noqa: E731
+    o = (ptr(delays), ptr(info), ptr(rclear))
+    search = lambda P=2, V=4, D=4, c=ptr(count), r=0, cap=None, out=o: lib.cfz_delay_search(h, P, V, D, c, None, r, cap, *out)  # noqa: E731
+    plan = lambda P=2, V=4, T=64, t=ptr(tab), D=4, m=0.05, r=0, cap=None, out=o: lib.cfz_plan_delays(h, P, V, T, t, D, m, r, cap, *out)  # noqa: E731
     loop = lambda D=4, m=0.05, r=0: lib.cfz_loop_plan_delays(h, D, m, r, None, *o)  # noqa: E731
     # (D+1)^V against 2^31: 215^4 and 46340^2 are below it, 216^4, 15^8 and 46341^2 above
     for call, text in ((lambda: search(P=0), "P, V must be positive"), (lambda: search(V=0), "P, V must be positive"),
                        (lambda: search(V=9), "V must be in 1..CFZ_MAX_NBR"), (lambda: search(D=-1), "D must not be negative"),
                        (lambda: search(r=-1), "slack must not be negative"), (lambda: search(c=None), "null count"),
-                       (lambda: search(out=(None, _p(info), _p(rclear))), "null delays"), (lambda: search(cap=_p(cap_bad)), "a cap lies outside"),
-                       (lambda: search(cap=_p(cap_neg)), "a cap lies outside"), (lambda: search(D=215), "search space too large"),
+                       (lambda: search(out=(None, ptr(info), ptr(rclear))), "null delays"), (lambda: search(cap=ptr(cap_bad)), "a cap lies outside"),
+                       (lambda: search(cap=ptr(cap_neg)), "a cap lies outside"), (lambda: search(D=215), "search space too large"),
                        (lambda: search(V=8, D=14), "search space too large"), (lambda: search(V=2, D=46340), "search space too large"),
                        (lambda: plan(P=0), "P, T must be positive"), (lambda: plan(T=0), "P, T must be positive"),
                        (lambda: plan(V=9), "V must be in 1..CFZ_MAX_NBR"), (lambda: plan(D=-1), "D must not be negative"),
                        (lambda: plan(m=-1.0), "margin must be finite"), (lambda: plan(t=None), "null tables"),
                        (lambda: plan(r=-1), "slack must not be negative"), (lambda: plan(out=(None, None, None)), "null delays"),
-                       (lambda: plan(cap=_p(cap_bad)), "a cap lies outside"), (lambda: plan(D=215), "search space too large"),
+                       (lambda: plan(cap=ptr(cap_bad)), "a cap lies outside"), (lambda: plan(D=215), "search space too large"),
                        (lambda: loop(D=-1), "D must not be negative"), (lambda: loop(m=float("nan")), "margin must be finite"),
                        (lambda: loop(r=-1), "slack must not be negative")):
         assert call() == -1 and text in lib.cfz_last_error().decode(), (text, lib.cfz_last_error().decode())

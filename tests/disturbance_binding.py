@@ -2,15 +2,10 @@
 (tests/emu/cfz_disturb_emu.cpp over conflict_rez_amd/csrc/cfz_disturb.inl), and an independent numpy statement of the same definition
 (Philox4x32-10, 53-bit uniforms, Box-Muller) that both the CPU build and the GPU kernels are checked against."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from emu_build import build_shared
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_disturb_emu.so")
-_lib = None
+from emu_build import load, ptr
 
 # the base sigma set of the tests: measurement (x, y, psi, v, delta), actuator (a, w), process (x, y, psi, v, delta)
 SIGMA = dict(meas=(0.02, 0.02, 0.005, 0.02, 0.0), act=(0.05, 0.02), proc=(0.005, 0.005, 0.002, 0.01, 0.0))
@@ -21,40 +16,31 @@ def sigma12(meas=None, act=None, proc=None):
                            np.zeros(5) if proc is None else np.asarray(proc, float)])
 
 
-def build(force=False):
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_disturb_emu.cpp"), os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_disturb.inl")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
+_i, _d, _vp = C.c_int, C.c_double, C.c_void_p
+PROTOTYPES = {  # of tests/emu/cfz_disturb_emu.cpp
+    "cfz_emu_philox": (None, [_vp, _vp, _vp]),
+    "cfz_emu_box_muller": (None, [_vp, _vp]),
+    "cfz_emu_normals": (None, [C.c_long] + [_vp] * 6),
+    "cfz_emu_disturbance": (None, [C.c_uint64, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "cfz_emu_disturb_add": (_d, [_d, _d]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp = C.c_void_p
-        _lib.cfz_emu_philox.argtypes = [vp, vp, vp]
-        _lib.cfz_emu_box_muller.argtypes = [vp, vp]
-        _lib.cfz_emu_normals.argtypes = [C.c_long, vp, vp, vp, vp, vp, vp]
-        _lib.cfz_emu_disturbance.argtypes = [C.c_uint64, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-        _lib.cfz_emu_disturb_add.argtypes = [C.c_double, C.c_double]
-        _lib.cfz_emu_disturb_add.restype = C.c_double
-    return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+    return load("cfz_disturb_emu", ("tests/emu/cfz_disturb_emu.cpp", "conflict_rez_amd/csrc/cfz_disturb.inl"), PROTOTYPES)
 
 
 def emu_philox(ctr, key):
     ctr = np.ascontiguousarray(ctr, np.uint32); key = np.ascontiguousarray(key, np.uint32)
     out = np.empty(4, np.uint32)
-    lib().cfz_emu_philox(_p(ctr), _p(key), _p(out))
+    lib().cfz_emu_philox(ptr(ctr), ptr(key), ptr(out))
     return out
 
 
 def emu_box_muller(words):
     w = np.ascontiguousarray(words, np.uint32)
     z = np.empty(2)
-    lib().cfz_emu_box_muller(_p(w), _p(z))
+    lib().cfz_emu_box_muller(ptr(w), ptr(z))
     return z
 
 
@@ -63,7 +49,7 @@ def emu_normals(seed, stream, v, step):
     seed = np.ascontiguousarray(seed, np.uint64); n = len(seed)
     stream, v, step = (np.ascontiguousarray(np.broadcast_to(a, n), np.uint32) for a in (stream, v, step))
     words, z = np.empty((n, 6, 4), np.uint32), np.empty((n, 12))
-    lib().cfz_emu_normals(n, _p(seed), _p(stream), _p(v), _p(step), _p(words), _p(z))
+    lib().cfz_emu_normals(n, ptr(seed), ptr(stream), ptr(v), ptr(step), ptr(words), ptr(z))
     return words, z
 
 
@@ -71,7 +57,7 @@ def emu_disturbance(seed, sigma, level, stream, V, t0, K):
     sigma = np.ascontiguousarray(sigma, float); level = np.ascontiguousarray(level, float); stream = np.ascontiguousarray(stream, np.uint32)
     S = len(level)
     d = np.empty((K, S, V, 12))
-    lib().cfz_emu_disturbance(C.c_uint64(int(seed)), _p(sigma), _p(level), _p(stream), S, V, int(t0), int(K), _p(d))
+    lib().cfz_emu_disturbance(C.c_uint64(int(seed)), ptr(sigma), ptr(level), ptr(stream), S, V, int(t0), int(K), ptr(d))
     return d
 
 

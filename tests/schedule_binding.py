@@ -7,42 +7,30 @@ no walk back -- that both the CPU build and the GPU kernels are checked against.
 import ctypes as C
 import functools
 import itertools
-import os
 
 import numpy as np
 
 import audit_binding as ab
 import conflict_binding as cb
 from conflict_binding import pairs
-from emu_build import build_shared
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_schedule_emu.so")
-_lib = None
+from emu_build import load, ptr
 
 G, MARGIN, TIE = cb.G, cb.MARGIN, 1e-12
 OUT = ("schedule", "arrival", "waits", "found", "order", "makespan", "total", "feasible_orders")
 
 
-def build(force=False):
-    csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_schedule_emu.cpp")] + [os.path.join(csrc, f) for f in ("cfz_schedule.inl", "cfz_coord.inl", "cfz_conflict.inl", "cfz_audit.inl", "cfz_wave.inl")] + [os.path.join(ROOT, "tests", "emu", "emu_columns.h")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
+_i, _vp = C.c_int, C.c_void_p
+PROTOTYPES = {  # of tests/emu/cfz_schedule_emu.cpp
+    "cfz_emu_schedule_lds_bytes": (_i, []),
+    "cfz_emu_schedule_wave_words": (_i, [_i, _i, _i]),
+    "cfz_emu_plan_coordination": (_i, [_i, _i, _i, _vp, _vp, _vp, C.c_double, _vp]),
+    "cfz_emu_plan_schedule": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp, ci = C.c_void_p, C.c_int
-        _lib.cfz_emu_plan_coordination.argtypes = [ci, ci, ci, vp, vp, vp, C.c_double, vp]
-        _lib.cfz_emu_plan_schedule.argtypes = [ci, ci, ci, vp, vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp]
-        _lib.cfz_emu_schedule_wave_words.argtypes = [ci, ci, ci]
-    return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return load("cfz_schedule_emu", ["tests/emu/cfz_schedule_emu.cpp", "tests/emu/emu_columns.h"]
+                + ["conflict_rez_amd/csrc/" + f for f in ("cfz_schedule.inl", "cfz_coord.inl", "cfz_conflict.inl", "cfz_audit.inl", "cfz_wave.inl")], PROTOTYPES)
 
 
 def all_orders(V):
@@ -86,7 +74,7 @@ def emu_diagram(tables, margin=MARGIN, length=None, g=G):
     P, V, T = tables.shape[:3]
     length = None if length is None else _lengths(length, P, V, T)
     words = np.full((P, V * (V - 1) // 2, 2, T, (T + 31) // 32), 0xDEADBEEF, np.uint32)
-    assert lib().cfz_emu_plan_coordination(P, V, T, _p(tables), _p(length), _p(np.ascontiguousarray(g, float)), margin, _p(words)) == 0
+    assert lib().cfz_emu_plan_coordination(P, V, T, ptr(tables), ptr(length), ptr(np.ascontiguousarray(g, float)), margin, ptr(words)) == 0
     return unpack(words, T)
 
 
@@ -99,7 +87,7 @@ def emu_schedule_diagram(sides, hold, H, slack=0, orders=None, length=None, wave
     orders = all_orders(V) if orders is None else np.ascontiguousarray(np.atleast_2d(orders), dtype=np.int32)
     length = None if length is None else _lengths(length, P, V, T)
     sch, arr, wts, info = np.full((P, V, H), -7, np.int32), np.full((P, V), -7, np.int32), np.full((P, V), -7, np.int32), np.full((P, 5), -7, np.int32)
-    rc = lib().cfz_emu_plan_schedule(P, V, T, _p(words), _p(length), _p(hold), H, slack, len(orders), _p(orders), waves, _p(sch), _p(arr), _p(wts), _p(info))
+    rc = lib().cfz_emu_plan_schedule(P, V, T, ptr(words), ptr(length), ptr(hold), H, slack, len(orders), ptr(orders), waves, ptr(sch), ptr(arr), ptr(wts), ptr(info))
     assert rc == 0, rc
     return dict(schedule=sch, arrival=arr, waits=wts, found=info[:, 0] == 1, order=info[:, 1], makespan=info[:, 2], total=info[:, 3], feasible_orders=info[:, 4])
 
@@ -346,30 +334,30 @@ def check_refusals(lib, h):
     bad_len, bad_len0 = np.array([[40, 41, 40]] * 2, np.int32), np.array([[40, 0, 40]] * 2, np.int32)
     bad_ord, bad_ord2 = np.array([[0, 1, 1]], np.int32), np.array([[0, 1, 3]], np.int32)
 
-    def plan(P=P, V=V, T=T, t=_p(tab), n=None, hd=_p(hold), H=H, m=0.05, r=0, O=6, o=_p(orders), s=_p(sch)):
-        return lib.cfz_plan_schedule(h, P, V, T, t, n, hd, H, m, r, O, o, s, _p(arr), _p(wts), _p(info))
+    def plan(P=P, V=V, T=T, t=ptr(tab), n=None, hd=ptr(hold), H=H, m=0.05, r=0, O=6, o=ptr(orders), s=ptr(sch)):
+        return lib.cfz_plan_schedule(h, P, V, T, t, n, hd, H, m, r, O, o, s, ptr(arr), ptr(wts), ptr(info))
 
-    def coord(P=P, V=V, T=T, t=_p(tab), n=None, m=0.05, b=_p(blk)):
+    def coord(P=P, V=V, T=T, t=ptr(tab), n=None, m=0.05, b=ptr(blk)):
         return lib.cfz_plan_coordination(h, P, V, T, t, n, m, b)
 
     def loop(m=0.05, r=0):
-        return lib.cfz_loop_plan_schedule(h, None, _p(hold), H, m, r, 6, _p(orders), _p(sch), _p(arr), _p(wts), _p(info))
+        return lib.cfz_loop_plan_schedule(h, None, ptr(hold), H, m, r, 6, ptr(orders), ptr(sch), ptr(arr), ptr(wts), ptr(info))
 
     for call, text in ((lambda: plan(P=0), "P, T must be positive"), (lambda: plan(T=0), "P, T must be positive"),
                        (lambda: plan(V=0), "V must be in 1..CFZ_MAX_NBR"), (lambda: plan(V=9), "V must be in 1..CFZ_MAX_NBR"),
                        (lambda: plan(m=-1.0), "margin must be finite"), (lambda: plan(m=float("nan")), "margin must be finite"),
-                       (lambda: plan(t=None), "null tables"), (lambda: plan(n=_p(bad_len)), "a length lies outside"),
-                       (lambda: plan(n=_p(bad_len0)), "a length lies outside"), (lambda: plan(H=0), "H, O must be positive"),
+                       (lambda: plan(t=None), "null tables"), (lambda: plan(n=ptr(bad_len)), "a length lies outside"),
+                       (lambda: plan(n=ptr(bad_len0)), "a length lies outside"), (lambda: plan(H=0), "H, O must be positive"),
                        (lambda: plan(O=0), "H, O must be positive"), (lambda: plan(H=39), "H must not be below T"),
                        (lambda: plan(T=2049, H=2049), "T must not exceed CFZ_SCHEDULE_MAX_T"),
                        (lambda: plan(H=32769), "H must not exceed CFZ_SCHEDULE_MAX_H"), (lambda: plan(r=-1), "slack must not be negative"),
                        (lambda: plan(hd=None), "null hold"), (lambda: plan(o=None), "null orders"), (lambda: plan(s=None), "null schedule"),
-                       (lambda: plan(O=1, o=_p(bad_ord)), "an order is not a permutation"),
-                       (lambda: plan(O=1, o=_p(bad_ord2)), "an order is not a permutation"),
+                       (lambda: plan(O=1, o=ptr(bad_ord)), "an order is not a permutation"),
+                       (lambda: plan(O=1, o=ptr(bad_ord2)), "an order is not a permutation"),
                        (lambda: plan(P=30000, H=32768), "schedule too large"),
                        (lambda: coord(P=0), "P, T must be positive"), (lambda: coord(V=9), "V must be in 1..CFZ_MAX_NBR"),
                        (lambda: coord(m=float("inf")), "margin must be finite"), (lambda: coord(t=None), "null tables"),
-                       (lambda: coord(b=None), "null blocked"), (lambda: coord(n=_p(bad_len)), "a length lies outside"),
+                       (lambda: coord(b=None), "null blocked"), (lambda: coord(n=ptr(bad_len)), "a length lies outside"),
                        (lambda: loop(m=-0.1), "margin must be finite"), (lambda: loop(r=-1), "slack must not be negative")):
         assert call() == -1 and text in lib.cfz_last_error().decode(), (text, lib.cfz_last_error().decode())
     assert (sch == 7).all() and (arr == 7).all() and (wts == 7).all() and (info == 7).all() and (blk == 7).all()

@@ -4,16 +4,17 @@ statement of the definitions of include/confrez_hip.h ("score of a realised traj
 ordered merges -- that both the CPU build and the GPU kernel are checked against.  Also the synthetic records both test modules use."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 
 import audit_binding as ab
-from emu_build import build_shared
+from emu_build import load, ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = os.path.join(ROOT, "tests", "_build", "libcfz_score_emu.so")
-_lib = None
+_i, _d, _vp = C.c_int, C.c_double, C.c_void_p
+PROTOTYPES = {  # of tests/emu/cfz_score_emu.cpp
+    "cfz_emu_score_group": (_i, [_i]),
+    "cfz_emu_score": (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _d, _d, _d, _d, _i, _vp, _vp]),
+}
 
 VAL = ("dx2", "dy2", "psi2", "a2", "vw2", "delta2", "da2", "dw2", "absv", "dev2_max")
 CNT = ("steps", "arrive", "failed", "fail_run", "reversals", "waiting", "near_steps", "first_near", "iters_sum", "iters_max", "dev_max_step")
@@ -24,25 +25,8 @@ VS = (1, 2, 3, 4, 5, 8)
 KS = (1, 2, 7, 8, 9, 16, 17, 37, 130)
 
 
-def build(force=False):
-    csrc = os.path.join(ROOT, "conflict_rez_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "emu", "cfz_score_emu.cpp"), os.path.join(csrc, "cfz_score.inl"), os.path.join(csrc, "cfz_audit.inl"), os.path.join(csrc, "cfz_wave.inl")]
-    return build_shared(_LIB, srcs, ["-O2", "-ffp-contract=off"], force)
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(build())
-        vp = C.c_void_p
-        _lib.cfz_emu_score.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_double,
-                                       C.c_double, C.c_int, vp, vp]
-        _lib.cfz_emu_score_group.argtypes = [C.c_int]
-    return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return load("cfz_score_emu", ["tests/emu/cfz_score_emu.cpp"] + ["conflict_rez_amd/csrc/" + f for f in ("cfz_score.inl", "cfz_audit.inl", "cfz_wave.inl")], PROTOTYPES)
 
 
 def group(V):
@@ -60,8 +44,8 @@ def emu_score(traj, status, iters, tables, table_of, k0, g=G, near=NEAR, lanes=0
     iters = None if iters is None else np.ascontiguousarray(iters, np.int32)
     table_of = np.ascontiguousarray(table_of, np.int32); k0 = np.ascontiguousarray(k0, np.int32); g = np.ascontiguousarray(g, float)
     out = dict(val=np.empty((S, V, len(VAL))), cnt=np.empty((S, V, len(CNT)), np.int32))
-    rc = lib().cfz_emu_score(K, S, V, _p(traj), _p(status), _p(iters), P, T, _p(tables), _p(table_of), _p(k0), _p(g), tol["pos_tol"], tol["psi_tol"],
-                             tol["v_tol"], near, lanes, _p(out["val"]), _p(out["cnt"]))
+    rc = lib().cfz_emu_score(K, S, V, ptr(traj), ptr(status), ptr(iters), P, T, ptr(tables), ptr(table_of), ptr(k0), ptr(g), tol["pos_tol"], tol["psi_tol"],
+                             tol["v_tol"], near, lanes, ptr(out["val"]), ptr(out["cnt"]))
     assert rc == 0
     return out
 

@@ -3,16 +3,11 @@ call it, run on an MI355X by tests/hip/block_merge.hip -- a stand-alone program 
 for four wavefronts and for two, over 33 rounds of alternating parity with one barrier each, a wavefront held back in the odd rounds;
 against the header's host form in a g++ build (tests/hip/wave_merge_host.cpp), which the CPU builds of the two kernels call.  The host
 form itself is checked without a GPU against Python's min and sum.  Comparisons are of fields, never of padding."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-from emu_build import build_shared
-from wave_case import CASE, ROOT, key as _key, same as _same
+from emu_build import build_hip_program, ptr, run_program
+from wave_case import CASE, host_lib, key as _key, same as _same
 
 SUM = np.dtype([("sum", "<i4"), ("n", "<i4")])
 ROUNDS = 33
@@ -37,14 +32,13 @@ def _inputs(waves):
 @pytest.fixture(scope="module")
 def host():
     """The header's host form per round: acc [ROUNDS, waves] -> [ROUNDS]."""
-    src = [os.path.join(ROOT, "tests", "hip", f) for f in ("wave_merge_host.cpp", "wave_merge_case.h")] + [os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_wave.inl")]
-    lib = C.CDLL(build_shared(os.path.join(ROOT, "tests", "_build", "libwave_merge_host.so"), src, ["-O2", "-ffp-contract=off"]))
+    lib = host_lib()
 
     def run(acc):
         acc = np.ascontiguousarray(acc)
         out = np.zeros(acc.shape[0], acc.dtype)
         fn = lib.block_host_min if acc.dtype == CASE else lib.block_host_sum
-        assert fn(acc.ctypes.data_as(C.c_void_p), C.c_int(acc.shape[0]), C.c_int(acc.shape[1]), out.ctypes.data_as(C.c_void_p)) == 0
+        assert fn(ptr(acc), acc.shape[0], acc.shape[1], ptr(out)) == 0
         return out
 
     return run
@@ -66,15 +60,12 @@ def test_host_form_against_min_and_sum(host, waves):
 def device(tmp_path_factory):
     """tests/hip/block_merge.hip built for gfx950 and run once -> {waves: (min [ROUNDS, 64 waves] CASE, sum [ROUNDS, 64 waves] SUM)}."""
     d = tmp_path_factory.mktemp("block_merge")
-    exe, fin, fout = str(d / "block_merge"), str(d / "in.bin"), str(d / "out.bin")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-o", exe, os.path.join(ROOT, "tests", "hip", "block_merge.hip")])
+    exe, fin, fout = build_hip_program("tests/hip/block_merge.hip", d / "block_merge"), str(d / "in.bin"), str(d / "out.bin")
     with open(fin, "wb") as f:
         for waves in WAVES:
             c, s = _inputs(waves)
             f.write(c.tobytes() + s.tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr)
+    run_program(exe, [fin, fout])
     raw = open(fout, "rb").read()
     assert len(raw) == sum(ROUNDS * 64 * w * (CASE.itemsize + SUM.itemsize) for w in WAVES)
     out, at = {}, 0

@@ -566,14 +566,9 @@ def test_block_elimination_on_the_matrix_cores_equals_the_lane_per_row_eliminati
     v_mfma_f64_16x16x4_f64) against the lane = row elimination they replaced (wave_lu_regs: one pivot at a time, v_readlane broadcasts), on
     2048 random blocks a third of which have a zero diagonal block with a 1e-7 regularisation like a KKT system: the same pivots and the
     same roundings, so every solution agrees BIT FOR BIT (tools/src/wave_lu_mfma_bench.hip holds both)."""
-    import shutil
-    import subprocess
+    from emu_build import build_hip_program, run_program
 
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "wave_lu_mfma")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-o", exe, os.path.join(root, "tools", "src", "wave_lu_mfma_bench.hip")])
-    out = subprocess.run([exe, "2048", "8"], check=True, capture_output=True, text=True, timeout=300).stdout
+    out = run_program(build_hip_program("tools/src/wave_lu_mfma_bench.hip", tmp_path / "wave_lu_mfma"), ["2048", "8"], timeout=300)
     assert "solutions that differ in any bit: 0 of" in out and out.count("failed 0,") == 2, out
 
 

@@ -21,18 +21,15 @@ found: the copy of block 0's solution to xs took two wavefronts (`if (wv < 2)`),
 unwritten; the product launches eight, and the loop now strides over the wavefronts there are.
 """
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from emu_build import build_hip_program, run_program
 from oracle import separators as sep
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NMS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 15, 16, 17, 31, 50, 51, 255)  # every level count from one to eight, a last block with and without a right neighbour, the product's limit
 SEEDS = (0, 1)
 BOUND_CAP, YARD_CAP = 1e-9, 3e-11
@@ -43,9 +40,7 @@ N_BLOCKS = 256
 def harness(tmp_path_factory):
     """tests/hip/jstruct_blocks.hip built once for gfx950; `run(header, *arrays)` = one invocation, its output as float64."""
     d = tmp_path_factory.mktemp("jstruct_blocks")
-    exe = str(d / "jstruct_blocks")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-o", exe, os.path.join(ROOT, "tests", "hip", "jstruct_blocks.hip")])
+    exe = build_hip_program("tests/hip/jstruct_blocks.hip", d / "jstruct_blocks")
     count = [0]
 
     def run(header, *arrays):
@@ -55,8 +50,7 @@ def harness(tmp_path_factory):
             f.write(np.array(list(header) + [0] * (8 - len(header)), np.int64).tobytes())
             for a in arrays:
                 f.write(np.ascontiguousarray(a).tobytes())
-        r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, (r.returncode, r.stderr)
+        run_program(exe, [fin, fout])
         return np.fromfile(fout, np.float64)
 
     return run

@@ -3,16 +3,11 @@ score_kernel, conflict_kernel and delay_kernel call, run on an MI355X by tests/h
 nothing of the product but that header -- over two test structs with padding words (tests/hip/wave_merge_case.h), against the header's
 host forms in a g++ build (tests/hip/wave_merge_host.cpp), which the CPU builds of the four kernels call.  The host forms themselves are
 checked without a GPU against plain folds over the lanes.  Comparisons are of fields, never of padding."""
-import ctypes as C
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
-from emu_build import build_shared
-from wave_case import CASE, ROOT, key as _key, same as _same
+from emu_build import build_hip_program, ptr, run_program
+from wave_case import CASE, host_lib, key as _key, same as _same
 
 SPAN = np.dtype([("first", "<i4"), ("last", "<i4"), ("count", "<i4"), ("sum", "<f8")], align=True)
 assert SPAN.itemsize == 24  # as the static_asserts of wave_merge_case.h
@@ -39,12 +34,11 @@ def _inputs():
 @pytest.fixture(scope="module")
 def host():
     """The header's host forms: (acc, width) -> the lanes after the butterfly, a new array."""
-    src = [os.path.join(ROOT, "tests", "hip", f) for f in ("wave_merge_host.cpp", "wave_merge_case.h")] + [os.path.join(ROOT, "conflict_rez_amd", "csrc", "cfz_wave.inl")]
-    lib = C.CDLL(build_shared(os.path.join(ROOT, "tests", "_build", "libwave_merge_host.so"), src, ["-O2", "-ffp-contract=off"]))
+    lib = host_lib()
 
     def run(fn, acc, width):
         out = np.ascontiguousarray(acc).copy()
-        assert fn(out.ctypes.data_as(C.c_void_p), C.c_int(len(out)), C.c_int(width)) == 0
+        assert fn(ptr(out), len(out), width) == 0
         return out
 
     return (lambda acc, width: run(lib.wave_host_min, acc, width)), (lambda acc, width: run(lib.wave_host_concat, acc, width))
@@ -76,14 +70,11 @@ def test_host_forms_against_plain_folds(host):
 def device(tmp_path_factory):
     """tests/hip/wave_merge.hip built for gfx950 and run once -> (xor [6, 64] CASE, min [64] CASE, concat [7, 64] SPAN)."""
     d = tmp_path_factory.mktemp("wave_merge")
-    exe, fin, fout = str(d / "wave_merge"), str(d / "in.bin"), str(d / "out.bin")
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-o", exe, os.path.join(ROOT, "tests", "hip", "wave_merge.hip")])
+    exe, fin, fout = build_hip_program("tests/hip/wave_merge.hip", d / "wave_merge"), str(d / "in.bin"), str(d / "out.bin")
     c, s = _inputs()
     with open(fin, "wb") as f:
         f.write(c.tobytes() + s.tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.returncode, r.stderr)
+    run_program(exe, [fin, fout])
     raw = open(fout, "rb").read()
     n_case = (len(OFFS) + 1) * LANES
     assert len(raw) == n_case * CASE.itemsize + len(WIDTHS) * LANES * SPAN.itemsize
