@@ -371,7 +371,8 @@ CFZP_SWEEP int riccati_backward(const PSpec &sp, const PWork &w, SP st_, SP fb_)
 // constants of the value function that feed nothing),  M = T' Pt T + Ht,  Pt <- M_kk - M_ke M_ee^-1 M_ek,  [K kk kl] = -M_ee^-1 M_ek -- five dependent
 // v_mfma_f64_16x16x4_f64 per stage: Y = Pt T (Pt's accumulator is the first operand as it stands: it is symmetric), M = Tt' Y onto Ht (Y's
 // accumulator is the second operand as it stands), Pt = M - U V.  Operands are read from the stage data with one load each (a constant reads
-// a harmless word with mask 0).  Same recursion as riccati_backward above, the sums in another order.
+// a harmless word with mask 0).  Same recursion as riccati_backward above, the sums in another order.  tests/test_sweeps_gpu.py runs it alone, from LDS
+// and from global pointers, against the recursion in longdouble (T up to 510, the horizon of 300 stages at which the symmetrisation below matters).
 struct PlEnt { int off; double c; };  // off >= 0: word off of the stage's data, else the constant c
 CFZP_FN PlEnt pl_T(int r, int j, double dt) {  // T[r][j]: r = 0..6 (z+, 1, e), j a variable
   PlEnt e = {-1, 0.0};

@@ -974,8 +974,8 @@ CFZ_CALL void merit_partials(const KSpec &sp, const KDer &dv, const double *refg
 // Result: gains K_k (12 per stage) into kk, value function of stage 0 into rP (25) and rP + 25 (5).
 // Operands of the sweep in homogeneous coordinates (below), as workspace words or constants, and the sweep itself in plain loops with
 // every sum in the order v_mfma_f64_16x16x4_f64 forms it (k ascending, one fused multiply-add per k onto the accumulator): what the CPU
-// build runs, bit for bit what the matrix-core sweep returns (tools/src/riccati_mfma_bench.hip: 0 of 2,880 gains differ); oracle/cfz_port.c
-// has the same loops.
+// build runs, bit for bit what the matrix-core sweep returns (held by tests/test_sweeps_gpu.py, which runs this file's sweep alone on an
+// MI355X: 0 of 23,184 gain and value-function words differ from these loops built with hardware fma); oracle/cfz_port.c has the same loops.
 struct RicEnt { int off, stride; double c; };  // value at stage k: stride ? m[off + k * stride] : c
 CFZ_FN RicEnt ric_T(int r, int j, double dt, int o_ab, int o_d) {  // T[r][j], r < 6, j < 8
   RicEnt e = {0, 0, 0.0};
@@ -1026,8 +1026,8 @@ static void riccati_backward_dense(wsp_f64 *m, int N, double dt, int o_ab, int o
 }
 #endif
 #if defined(__HIP_DEVICE_COMPILE__)
-// The same sweep on the matrix cores (round 5; tools/src/riccati_mfma_bench.hip is the go / no-go measurement: 1,150 cycles per stage
-// against 1,850 for the hand-pipelined sweep on one lane it replaced, gains equal to 9e-16).  Measured before it and removed (git
+// The same sweep on the matrix cores (round 5; tools/src/riccati_mfma_bench.hip is the go / no-go TIMING: 1,150 cycles per stage
+// against 1,850 for the hand-pipelined sweep on one lane it replaced; what it computes is held by tests/test_sweeps_gpu.py).  Measured before it and removed (git
 // history): entries spread over lanes with exchange through LDS, 2.2x slower than one lane (every exchange a dependent LDS round
 // trip); five lanes on registers only (v_readlane broadcasts, no LDS, no barrier), 70 k cycles per sweep against one lane's 60 k.
 // The first wavefront, all 64 lanes.  Homogeneous coordinates, variables ordered [z (5), 1, u (2)]:

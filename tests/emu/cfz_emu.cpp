@@ -27,4 +27,25 @@ int cfz_emu_solve(const cfz::KSpec *sp, const double *x0, const double *ref, con
   free(m);
   return L.total;
 }
+
+// The Newton step's linear algebra ALONE (tests/test_sweeps_host.py; oracle/sweeps.py): the backward sweep and the two scans of the CPU build, on
+// the caller's workspace of cfz_emu_layout's `total` doubles.
+// out[15] = total, ab, d, hc, gk, kk, rP, p, dp, x0, pi0, dpi0, dpi, pi, cs of cfz::make_layout(N, nb, n_nbr)
+void cfz_emu_layout(int N, int nb, int n_nbr, int *out) {
+  const cfz::Lay L = cfz::make_layout(N, nb, n_nbr);
+  const int v[15] = {L.total, L.ab, L.d, L.hc, L.gk, L.kk, L.rP, L.p, L.dp, L.x0, L.pi0, L.dpi0, L.dpi, L.pi, L.cs};
+  for (int i = 0; i < 15; ++i) out[i] = v[i];
+}
+void cfz_emu_riccati(double *m, int N, int nb, int n_nbr, double dt) {
+  const cfz::Lay L = cfz::make_layout(N, nb, n_nbr);
+  cfz::riccati_backward_dense(m, N, dt, L.ab, L.hc, L.gk, L.d, L.kk, L.rP);  // (what CFZ_RICCATI names in this build)
+}
+void cfz_emu_forward_scan(double *m, int N, int nb, int n_nbr, double dt) {
+  const cfz::Lay L = cfz::make_layout(N, nb, n_nbr);
+  cfz::forward_scan(m, N, dt, L.ab, L.d, L.kk, L.rP, L.p, L.dp, L.x0, L.pi0, L.dpi0);
+}
+void cfz_emu_costate_scan(double *m, int N, int nb, int n_nbr) {
+  const cfz::Lay L = cfz::make_layout(N, nb, n_nbr);
+  cfz::costate_scan(m, N, L.ab, L.hc, L.gk, L.kk, L.dp, L.dpi, L.pi);
+}
 }

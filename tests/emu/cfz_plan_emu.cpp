@@ -13,4 +13,23 @@ int cfzp_emu_state_ws(const cfzp::PSpec *sp, const double *tube, double *X, int 
   free(slab);
   return 0;
 }
+
+// The backward sweep ALONE (tests/test_sweeps_host.py; oracle/sweeps.py) on the caller's stage data st [(T + 1) kSt]; fb [(T + 1) kFb] and
+// vf [(T + 1) kVf] are written for the stages the sweep visits; -> its flag.
+// The plain loops of the homogeneous form; built with -DCFZP_DENSE_TRANSPOSED they take the accumulator as the matrix-core sweep does.
+int cfzp_emu_riccati_dense(int T, double dt, int has_final, double *st, double *fb, double *vf) {
+  cfzp::PSpec sp = {};
+  sp.T = T; sp.dt = dt; sp.has_final = has_final;
+  cfzp::PWork w = {};
+  w.vf = vf;
+  return cfzp::riccati_backward_dense(sp, w, st, fb);
+}
+// The one-lane sweep; ce [n_chk 6]: the pose blocks of the cell ends, stages N, 2 N, .. n_chk N = T.
+int cfzp_emu_riccati(int T, int N, int n_chk, double dt, int has_final, double *st, double *ce, double *fb, double *vf) {
+  cfzp::PSpec sp = {};
+  sp.T = T; sp.N = N; sp.n_chk = n_chk; sp.dt = dt; sp.has_final = has_final;
+  cfzp::PWork w = {};
+  w.vf = vf; w.ce = ce;
+  return cfzp::riccati_backward(sp, w, st, fb);
+}
 }
